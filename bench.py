@@ -73,6 +73,7 @@ def parse():
                                                               # problems fill a round; same box: 10.30 / 10.47 / 10.88 / 10.88 views/s at 2 / 3 / 4 / 7, profiles/r06_cobatch_sweep.txt).  A step stays ONE chunk; 1 = rounds 1-5
     ap.add_argument("--no-secondary", action="store_true")     # skip the short f16 secondary measurement (default workload, N = 1)
     ap.add_argument("--mask", action="store_true")   # BASELINE configs[3]: edits composited through a (synthetic elliptical) mask, gc_pipeline.py:226-234
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR")   # after the timed steps: what the last one computed as DIR/<name>.npy (write_outputs)
     return ap.parse_args()
 
 
@@ -304,6 +305,7 @@ class Bench:
         self.half_events = []           # (start, end of denoise half, end of step) HIP events of the timed steps
         self.record_halves = False
         self.rank0_only = False
+        self.keep = None                # a dict (--dump-outputs): every launch set leaves what it computed here, the last one wins
 
     # ------------------------------------------------------------------------------------------------ pieces of a step
     def new_aux(self):
@@ -454,12 +456,15 @@ class Bench:
                     target = torch.stack([self.sdops.mask_composite(target[jj], evals[jj][0].contiguous(), self.edit_mask) for jj in range(len(views))])
             else:
                 target = self.raster_target.expand(len(views), -1, -1, -1)
-            self.l1_ssim_loss_views(rgb, target, 0.2).sum().backward()      # the chunk's gradient SUM, formed inside the projection backward
+            losses = self.l1_ssim_loss_views(rgb, target, 0.2)
+            losses.sum().backward()                                         # the chunk's gradient SUM, formed inside the projection backward
             self.note_m(aux, sized_on_host=aux.m_cap is None)
             st["renders_done"] += len(views)
             views_iter = []
+            train_rgb, train_loss = [rgb.detach()], [losses.detach()]
         else:
             views_iter = list(enumerate(views))
+            train_rgb, train_loss = [], []
         for jj, i in views_iter:                                                                            # (d), one camera at a time
             aux = self.new_aux()
             aux.grad_into, aux.grad_accumulate = fg.views, jj > 0      # the batch's gradient sum is formed inside the backward kernel
@@ -472,10 +477,17 @@ class Bench:
             loss.backward()
             self.note_m(aux)
             st["renders_done"] += 1
+            if self.keep is not None:
+                train_rgb.append(rgb.detach()[None]); train_loss.append(loss.detach().reshape(1))
         if not views:
             fg.flat.zero_()                       # a rank without a view in this chunk contributes zeros to the reduction
         if self.dist is not None and not self.rank0_only:      # (the instrumented roofline steps run on rank 0 alone: no collective)
             fg.reduce_async(self.world)
+        if self.keep is not None:                 # references only: read after the timed region, before anything else runs a step
+            self.keep.clear()
+            self.keep.update(views=views, last_chunk=len(self.chunks_of(scene)[j1]), grads=fg, train_rgb=train_rgb, train_loss=train_loss)
+            if self.edit and views:
+                self.keep.update(latents=lat, edited=edited)
         if ev:
             ev[2].record()
             self.half_events.append(ev)
@@ -656,10 +668,47 @@ def dry_run(rank, world):
     dist.destroy_process_group()
 
 
+def last_step_outputs(B):
+    """What the last timed step handed back, as host arrays: its chunk's edited latents and images (denoise + VAE decode), training renders
+    and losses, and the summed gradients of the six Gaussian parameter tensors.  The gradients cover the whole launch set of that step: its
+    chunks share one backward pass (--cobatch)."""
+    k, out = B.keep, {}
+    n = k["last_chunk"]
+    if "latents" in k:
+        out["latents"], out["edited"] = k["latents"][-n:], k["edited"][-n:]
+    if k["train_rgb"]:
+        out["train_rgb"], out["train_loss"] = torch.cat(k["train_rgb"])[-n:], torch.cat(k["train_loss"])[-n:]
+    for name, g in k["grads"].views.items():
+        out["grad_" + name] = g
+    return {name: t.detach().float().cpu().numpy() for name, t in out.items()}
+
+
+DUMP_BYTES = 64_000_000
+
+
+def write_outputs(d, arrays, budget=DUMP_BYTES):
+    """arrays -> d/<name>.npy in float32, at most `budget` bytes in all.  When the whole set does not fit, an array larger than its equal
+    share of the budget is replaced by a fixed sample of its elements: flat indices from a seeded generator, ascending, the same positions
+    in every run with the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    fits = sum(a.nbytes for a in arrays.values()) + 1024 * len(arrays) <= budget
+    share = (budget // max(1, len(arrays)) - 1024) // 4          # elements per array (1 KB for the .npy header)
+    for name, a in arrays.items():
+        if not fits and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} outputs of the last timed step written to {d}", file=sys.stderr, flush=True)
+
+
 def main():
     args = parse()
+    # the training renders draw their backgrounds from the default generators: seeded, so that every run of the same arguments has the same inputs
+    torch.manual_seed(0)
     if args.workload == "full":
         assert args.gpus == 1, "--workload full is a single-GPU measurement"
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the edit and raster workloads (the timed steps of Bench.run)")
         return run_full_pipeline(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a bare `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU under torch.distributed.run, rendez-vous on
@@ -709,7 +758,11 @@ def main():
     z0, ctx_neg, ctx_pos = B.z0, B.ctx_neg, B.ctx_pos
     chunks_per_scene = B.cps
     B0_inflight = B.inflight
+    B.keep = {} if (args.dump_outputs and rank == 0) else None
     dt_s, my_views, my_renders = B.run(args.warmup, args.steps)
+    if B.keep is not None:                 # before the instrumented steps below overwrite the gradient buffers
+        write_outputs(args.dump_outputs, last_step_outputs(B))
+        B.keep = None
     g = B.next_step
     if dist is not None:
         tv = torch.tensor([my_views, my_renders], device=dev, dtype=torch.float64)
