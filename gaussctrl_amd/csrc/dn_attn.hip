@@ -795,27 +795,40 @@ void launch_attn3(const AttnArgs &a, int B, hipStream_t s)
 #ifndef ATT80_QT
 #define ATT80_QT 1
 #endif
-template <class T>
-int launch_attn(const AttnArgs &a, int D, int B, bool fast, int variant, hipStream_t s)
+// The kernel of one problem (shared by the launcher and gc_dn_attention_selection); 0 = unsupported head dim
+int attn_route(const AttnArgs &a, int D, int B, int variant)
 {
+    const bool fast = !(variant & 1);      // kernel_variant bit 0: online-softmax kernel everywhere (tests)
     if (fast && (int64_t)a.nsets * ((a.Lk + 63) / 64) >= 4) {   // short key streams: the pipeline's fill / LDS set-up does not amortise
-        switch (D) {
-        case 40:
-            // default: k_attn5 (key-split 8-wave form, dn_attn5.hip) when the tile shapes fit; kernel_variant bit 4 keeps k_attn4 (A/B)
-            if (!(variant & 30) && (a.Lk & 63) == 0 && (a.Lq & 255) == 0)
-                gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, (variant & 32) ? 4 : (variant & 64) ? 8 : 6, s);
-            else if (variant & 2) launch_attn3<T, 40, 2, 3>(a, B, s);     // kernel_variant bit 1: the 16x16x32 form (A/B measurements)
-            else if (variant & 4) launch_attn4<T, 40, 3, 8>(a, B, s);      // bit 2: 8 waves, one workgroup per CU
-            else if (variant & 8) launch_attn4<T, 40, 4, 4, 3, 2>(a, B, s); // bit 3: 64 queries per wave (one wave per SIMD)
-            else launch_attn4<T, 40, 3, 4>(a, B, s);
-            return GC_OK;
-        case 80: launch_attn3<T, 80, ATT80_QT, 3>(a, B, s); return GC_OK;
-        default: break;
-        }
+        // D = 40 default: k_attn5 (key-split 8-wave form, dn_attn5.hip) when the tile shapes fit; kernel_variant bit 4 keeps k_attn4 (A/B)
+        if (D == 40) return (!(variant & 30) && (a.Lk & 63) == 0 && (a.Lq & 255) == 0) ? GC_ATTN_SEL_K5 : (variant & 2) ? GC_ATTN_SEL_K3 : GC_ATTN_SEL_K4;
+        if (D == 80) return GC_ATTN_SEL_K3;
     }
     // Few workgroups and several K/V sets (D = 160 at 16x16 / 8x8: 192 / 48 workgroups of one wave per SIMD, nobody to hide the
     // S -> max -> exp -> P V dependency chain): one workgroup per (query block, set) + a fixed-order fp32 combine
-    if (D == 160 && a.part && a.nsets > 1 && (a.Lq & 255) == 0 && !(variant & 128)) {      // kernel_variant bit 7: the 64-query form (A/B, tests)
+    if (D == 160 && a.part && a.nsets > 1 && (a.Lq & 255) == 0 && !(variant & 128)) return GC_ATTN_SEL_WIDE_SPLIT;   // kernel_variant bit 7: the 64-query form (A/B, tests)
+    if (D != 8 && D != 16 && D != 32 && D != 40 && D != 64 && D != 80 && D != 160) return 0;
+    const int qq = D == 160 ? 1 : 2;                     // (GC_ATT below: queries per workgroup = 64 qq)
+    const int64_t nwg = (int64_t)((a.Lq + 64 * qq - 1) / (64 * qq)) * a.H * B;
+    return (a.part && a.nsets > 1 && nwg < 512) ? GC_ATTN_SEL_SPLIT : GC_ATTN_SEL_ONLINE;
+}
+
+template <class T>
+int launch_attn(const AttnArgs &a, int D, int B, int variant, hipStream_t s)
+{
+    const int route = attn_route(a, D, B, variant);
+    switch (route) {
+    case GC_ATTN_SEL_K5: gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, (variant & 32) ? 4 : (variant & 64) ? 8 : 6, s); return GC_OK;
+    case GC_ATTN_SEL_K4:
+        if (variant & 4) launch_attn4<T, 40, 3, 8>(a, B, s);             // bit 2: 8 waves, one workgroup per CU
+        else if (variant & 8) launch_attn4<T, 40, 4, 4, 3, 2>(a, B, s);  // bit 3: 64 queries per wave (one wave per SIMD)
+        else launch_attn4<T, 40, 3, 4>(a, B, s);
+        return GC_OK;
+    case GC_ATTN_SEL_K3:
+        if (D == 40) launch_attn3<T, 40, 2, 3>(a, B, s);                 // kernel_variant bit 1: the 16x16x32 form (A/B measurements)
+        else launch_attn3<T, 80, ATT80_QT, 3>(a, B, s);
+        return GC_OK;
+    case GC_ATTN_SEL_WIDE_SPLIT: {
         AttnArgs aa = a;
         aa.nqb = a.Lq / 256;
         const unsigned nwg = (unsigned)(aa.nqb * a.H * B);
@@ -825,12 +838,15 @@ int launch_attn(const AttnArgs &a, int D, int B, bool fast, int variant, hipStre
                            n4, n4, a.O, a.ldo, a.o_bs, (int64_t)(a.H * 160) / 4, (int64_t)a.Lq);
         return GC_OK;
     }
+    case 0: gc::set_error("gc_dn_attention: unsupported head dim %d", D); return GC_EINVAL;
+    default: break;
+    }
 #define GC_ATT(DD, QQ)                                                                                  \
     do {                                                                                                \
         AttnArgs aa = a;                                                                                \
         aa.nqb = (a.Lq + 64 * QQ - 1) / (64 * QQ);                                                      \
         const unsigned nwg = (unsigned)(aa.nqb * a.H * B);                                              \
-        if (a.part && a.nsets > 1 && nwg < 512) {                                                       \
+        if (route == GC_ATTN_SEL_SPLIT) {                                                               \
             hipLaunchKernelGGL((k_attn<T, DD, QQ>), dim3(nwg, (unsigned)a.nsets), dim3(256), 0, s, aa); \
             const int64_t n4 = (int64_t)B * a.Lq * (a.H * DD) / 4;                                      \
             hipLaunchKernelGGL((k_attn_combine<T>), dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, a.part, a.nsets, \
@@ -846,7 +862,7 @@ int launch_attn(const AttnArgs &a, int D, int B, bool fast, int variant, hipStre
     case 64: GC_ATT(64, 2); break;
     case 80: GC_ATT(80, 2); break;
     case 160: GC_ATT(160, 1); break;
-    default: gc::set_error("gc_dn_attention: unsupported head dim %d", D); return GC_EINVAL;
+    default: break;
     }
 #undef GC_ATT
     return GC_OK;
@@ -858,6 +874,27 @@ extern "C" size_t gc_dn_attention_workspace_bytes(const gc_attn_desc *d)
 {
     if (!d || d->nsets <= 1 || d->head_dim != 160) return 0;        // the set-split form serves the head size that has no static-offset kernel
     return sizeof(float) * (size_t)d->nsets * (size_t)d->batch * (size_t)d->Lq * (size_t)d->heads * (size_t)d->head_dim;
+}
+
+namespace {
+// the workspace of the set-split forms, when the caller passed one that is large enough
+float *attn_part(const gc_attn_desc *d)
+{
+    const size_t ws_need = gc_dn_attention_workspace_bytes(d);          // 0: this shape never takes the set-split form, whatever is passed
+    return (d->workspace && ws_need > 0 && d->workspace_bytes >= ws_need) ? (float *)d->workspace : nullptr;
+}
+}  // namespace
+
+extern "C" int gc_dn_attention_selection(const gc_attn_desc *d, int *kernel)
+{
+    GC_REQUIRE(d && kernel, "null argument");
+    GC_REQUIRE(d->nsets >= 1 && d->nsets <= 5, "1..5 K/V sets");
+    AttnArgs a{};
+    a.Lq = d->Lq; a.Lk = d->Lk; a.H = d->heads; a.nsets = d->nsets;
+    a.part = attn_part(d);
+    *kernel = attn_route(a, d->head_dim, d->batch, d->kernel_variant);
+    if (!*kernel) { gc::set_error("gc_dn_attention_selection: unsupported head dim %d", d->head_dim); return GC_EINVAL; }
+    return GC_OK;
 }
 
 extern "C" int gc_dn_attention(const gc_attn_desc *d, void *stream)
@@ -882,11 +919,9 @@ extern "C" int gc_dn_attention(const gc_attn_desc *d, void *stream)
     for (int i = 0; i < d->nsets; ++i) GC_REQUIRE(d->set_kind[i] >= -2 && d->set_kind[i] < a.ref_fph, "bad set_kind");
     a.scale_log2e = d->q_prescaled ? 1.f : d->scale * 1.4426950408889634f;
     a.abl = d->kernel_variant >> 8;
-    const size_t ws_need = gc_dn_attention_workspace_bytes(d);          // 0: this shape never takes the set-split form, whatever is passed
-    a.part = (d->workspace && ws_need > 0 && d->workspace_bytes >= ws_need) ? (float *)d->workspace : nullptr;
-    const bool fast = !(d->kernel_variant & 1);      // kernel_variant bit 0: online-softmax kernel everywhere (tests)
-    int rc = d->dtype == DT_BF16 ? launch_attn<BF16>(a, d->head_dim, d->batch, fast, d->kernel_variant, gc::S(stream))
-             : d->dtype == DT_F16 ? launch_attn<F16>(a, d->head_dim, d->batch, fast, d->kernel_variant, gc::S(stream)) : GC_EINVAL;
+    a.part = attn_part(d);
+    int rc = d->dtype == DT_BF16 ? launch_attn<BF16>(a, d->head_dim, d->batch, d->kernel_variant, gc::S(stream))
+             : d->dtype == DT_F16 ? launch_attn<F16>(a, d->head_dim, d->batch, d->kernel_variant, gc::S(stream)) : GC_EINVAL;
     if (rc != GC_OK) return rc;
     return gc::check_launch("gc_dn_attention");
 }

@@ -75,9 +75,12 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
     }
     const float c2 = a.scale_log2e;
     // Experiment hook (kernel_variant bits 16..20, default 0): P = exp2(s - m0 - cshift).  In f16 P must stay below 2^16, so a row whose
-    // later keys beat the first block's maximum by 16 binades sends its workgroup to the safe body; a positive shift widens that margin
-    // but P below 2^-14 is FLUSHED on this path (measured, profiles/r03_attn5_f16_window.txt: relative L2 error 3e-4 -> 5e-3 -> 8e-2 at
-    // shift 0 / 4 / 8), so f16 keeps shift 0 and its data-dependent fallback rate; bf16's 8-bit exponent never gets there.
+    // later keys beat the sampled maximum by 16 binades sends its workgroup to the safe body; a positive shift widens that margin but moves
+    // every P down by as many binades, into f16's subnormal range (fewer significant bits below 2^-14, zero below 2^-24), and the error grew
+    // with it (round 3, profiles/r03_attn5_f16_window.txt: relative L2 3e-4 -> 5e-3 -> 8e-2 at shift 0 / 4 / 8), so f16 keeps shift 0 and its
+    // data-dependent fallback rate; bf16's 8-bit exponent never gets there.  At shift 0 a subnormal P is NOT flushed: a row whose sampled
+    // maximum sits 14 - 16 binades above the rest of its set keeps their ~12 % of the mass
+    // (tests/test_launch_set_kernels_gpu.py::test_attention_keys_far_below_the_sampled_maximum).
     const float cshift = (float)((a.abl >> 8) & 31) / (PRE ? 1.f : c2);
     const int abl = ABL ? __builtin_amdgcn_readfirstlane(a.abl) : 0;
     float abl_x = -(float)(lane & 7);

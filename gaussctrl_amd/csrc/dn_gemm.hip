@@ -266,6 +266,54 @@ extern "C" int gc_dn_gemm_chan_parts_layout(const gc_gemm_desc *d, int64_t *rows
     return GC_OK;
 }
 
+namespace {
+// what gc_dn_gemm launches for a 2-byte problem, from the descriptor alone (shared by the launcher and gc_dn_gemm_selection)
+struct Route { Sel sel; int lnk, persist; };
+void route(const gc_gemm_desc *d, Route *r)
+{
+    Sel &sel = r->sel;
+    select(d, &sel, d->out_chan_parts != nullptr);
+    if (d->out_chan_parts && sel.mt8 == 1) sel.mt8 = 2;           // (the channel-partial epilogues have no 64-row tile)
+    const bool fuse = d->ln_row_stats || d->out_row_stats || d->out_group_stats;
+    r->lnk = (sel.mt8 && sel.splits == 1) ? ln_lean_kind(d) : 0;
+    r->persist = 0;
+    if (sel.mt8 == 4 && sel.ntw == 4 && sel.mode == 0 && sel.splits == 1 && d->K % 64 == 0 && d->K <= 64 * 24 && (!fuse || r->lnk == 2) && !d->out_chan_parts &&
+        !d->rowvec && !d->out_t && !d->out_f32 && d->out && d->act != 2 && !(d->kernel_variant & 0x200)) {
+        // multi-round short-K linear (the GEGLU FF-up projections): persistent workgroups, next tile's fill under this tile's epilogue
+        const int64_t tiles = ((d->M + 255) / 256) * ((d->N + 32 * sel.ntw - 1) / (32 * sel.ntw));
+        if (tiles > 256) r->persist = 256;
+    }
+}
+}  // namespace
+
+extern "C" int gc_dn_gemm_selection(const gc_gemm_desc *d, gc_gemm_selection *out)
+{
+    GC_REQUIRE(d && out, "null argument");
+    GC_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "empty problem");
+    *out = gc_gemm_selection{};
+    int64_t rows = 0; int ns = 0, ct = 0;
+    if (d->fp8) {
+        GC_REQUIRE(d->K % 128 == 0, "fp8: K % 128 == 0");
+        SelQ q;
+        select_fp8(d, &q, false);
+        out->kernel = GC_GEMM_SEL_FP8; out->m_tiles = q.mt; out->splits = q.splits; out->ntw = q.ntw;
+        if (d->out_chan_parts) {
+            chan_parts_layout(d, Sel{}, &rows, &ns, &ct);
+            out->parts = rows > 0 ? (q.splits > 1 ? 1 : 2) : -1;
+        }
+        return GC_OK;
+    }
+    Route r;
+    route(d, &r);
+    out->kernel = !r.sel.mt8 ? GC_GEMM_SEL_K4 : r.sel.splits > 1 ? GC_GEMM_SEL_K8_SLICED : GC_GEMM_SEL_K8;
+    out->m_tiles = r.sel.mt8; out->splits = r.sel.splits; out->ntw = r.sel.ntw; out->ln_kind = r.lnk; out->persist = r.persist;
+    if (d->out_chan_parts) {
+        chan_parts_layout(d, r.sel, &rows, &ns, &ct);
+        out->parts = rows > 0 ? (r.sel.splits > 1 ? 1 : 2) : -1;
+    }
+    return GC_OK;
+}
+
 extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
 {
     GC_REQUIRE(d && d->W && d->A, "null descriptor / operand");
@@ -316,15 +364,15 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     if (d->geglu) GC_REQUIRE(d->N % 32 == 0 && !d->out_t, "geglu needs N % 32 == 0");
     const int force_mt = d->kernel_variant & 7;
     GC_REQUIRE(force_mt >= 0 && force_mt <= 4, "kernel_variant: MT must be 0 .. 4");
-    Sel sel;
-    select(d, &sel, d->out_chan_parts != nullptr);
+    Route rt;
+    route(d, &rt);
+    const Sel &sel = rt.sel;
     g.chan_parts = d->out_chan_parts; g.cp_nslab = 0; g.cp_rows = 0;
     if (d->out_chan_parts) {
         int64_t rows; int ns, ct;
         chan_parts_layout(d, sel, &rows, &ns, &ct);
         GC_REQUIRE(rows > 0, "out_chan_parts: this problem cannot produce channel partials (see gc_dn_gemm_chan_parts_layout)");
         g.cp_nslab = ns; g.cp_rows = (int)rows;
-        if (sel.mt8 == 1) sel.mt8 = 2;
     }
     if (fuse_of(g) && sel.mt8) {     // the 8-wave kernel carries the fused epilogue for conv (generic / fast) and K % 64 == 0 linears only
         const bool upsampled = d->mode == 1 && d->upsample, ragged = d->mode == 0 && d->K % 64 != 0;
@@ -354,17 +402,11 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     g.splits = sel.splits; g.tiles_per_split = sel.tps; g.ws = (float *)d->workspace;
     const int bn = 32 * sel.ntw;
     const int64_t nbn = (d->N + bn - 1) / bn;
-    g.persist = 0;
-    const int lnk = (sel.mt8 && sel.splits == 1) ? ln_lean_kind(d) : 0;
+    g.persist = rt.persist;
+    const int lnk = rt.lnk;
     if (d->w_set_rows > 0 || d->softmax_keys > 0) {
         GC_REQUIRE(lnk != 0, "weight sets / softmax_keys need a lean LayerNorm-fold problem (K % 64 == 0 linear with ln_row_stats or out_row_stats, no forced variant)");
         GC_REQUIRE(d->w_set_rows == 0 || (d->w_set_rows % (64 * sel.mt8) == 0 && d->M % d->w_set_rows == 0), "w_set_rows must be a multiple of the row tile and divide M");
-    }
-    if (sel.mt8 == 4 && sel.ntw == 4 && sel.mode == 0 && sel.splits == 1 && d->K % 64 == 0 && d->K <= 64 * 24 && (!fuse_of(g) || lnk == 2) && !g.chan_parts &&
-        !g.rowvec && !g.out_t && !g.out_f32 && g.out && g.act != 2 && !(d->kernel_variant & 0x200)) {
-        // multi-round short-K linear (the GEGLU FF-up projections): persistent workgroups, next tile's fill under this tile's epilogue
-        const int64_t tiles = ((d->M + 255) / 256) * nbn;
-        if (tiles > 256) g.persist = 256;
     }
     if (sel.mt8) {
         const int64_t nbm8 = (d->M + 64 * sel.mt8 - 1) / (64 * sel.mt8);

@@ -45,6 +45,34 @@ class AttnDesc(C.Structure):
                 ("kernel_variant", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GemmSelection(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kernel", "m_tiles", "splits", "ntw", "parts", "ln_kind", "persist")]
+
+
+GEMM_KERNELS = {1: "k4", 2: "k8", 3: "k8_sliced", 4: "fp8"}                                          # gc_gemm_selection.kernel
+ATTN_KERNELS = {1: "attn5", 2: "attn4", 3: "attn3", 4: "wide+combine", 5: "attn+combine", 6: "attn"}   # gc_dn_attention_selection
+
+
+def gemm_selection(d):
+    """what gc_dn_gemm(d) launches (gc_dn_gemm_selection: a host function, no GPU needed) as a dict"""
+    sel = GemmSelection()
+    L.check(L.lib().gc_dn_gemm_selection(C.byref(d), C.byref(sel)), "gc_dn_gemm_selection")
+    r = {n: getattr(sel, n) for n, _ in GemmSelection._fields_}
+    r["kernel"] = GEMM_KERNELS[sel.kernel]
+    return r
+
+
+def attention_selection(d):
+    """the kernel gc_dn_attention(d) launches (gc_dn_attention_selection), by name"""
+    k = C.c_int(0)
+    L.check(L.lib().gc_dn_attention_selection(C.byref(d), C.byref(k)), "gc_dn_attention_selection")
+    return ATTN_KERNELS[k.value]
+
+
+SELECTION_LOG = None   # tests only: a list that receives (descriptor kind, M | batch, selection) of every GEMM / attention launch, taken from the
+                       # descriptor exactly as it goes to the library
+
+
 @dataclasses.dataclass
 class KernelOptions:
     """Every switch of the denoise host layer in ONE object (the C library holds no such state: kernel-selection overrides travel in the
@@ -228,6 +256,8 @@ def _run_gemm(d, dev, what, row_stats=None, want_parts=False, gn_groups=32):
             d.out_chan_parts = parts.buf.data_ptr()
         else:
             d.gn_groups = 0
+    if SELECTION_LOG is not None:
+        SELECTION_LOG.append(("gemm", d.M, gemm_selection(d)))
     L.check(lib.gc_dn_gemm(C.byref(d), _stream()), what)
     return parts
 
@@ -580,6 +610,8 @@ def attention(q, k, vt, heads, sets, frames_per_half, Lk=None, kref=None, vtref=
                                          # combine rounds differently from the in-register one: batch-invariant mode never offers the workspace
         ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
         d.workspace = ws.data_ptr(); d.workspace_bytes = wsb
+    if SELECTION_LOG is not None:
+        SELECTION_LOG.append(("attn", B, attention_selection(d)))
     L.check(L.lib().gc_dn_attention(C.byref(d), _stream()), "gc_dn_attention")
     return o
 

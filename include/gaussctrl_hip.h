@@ -389,6 +389,22 @@ int gc_dn_gemm_row_stat_slots(const gc_gemm_desc *desc);   /* column slabs per r
  * *rows_per_slab = 0: the kernel this problem selects cannot produce them (GEGLU / transposed / fp32 / fp8 outputs, upsample-fused convs,
  * rows_per_batch < 256 or not a multiple of 32, 4-wave kernel) -- run the stand-alone GroupNorm instead. */
 int gc_dn_gemm_chan_parts_layout(const gc_gemm_desc *desc, int64_t *rows_per_slab, int *nslab, int *col_tile);
+/* What gc_dn_gemm(desc) would launch, without launching anything (pure host function: tests pin the dispatch with it).  Call with the
+ * descriptor as it goes to the launch (workspace, out_chan_parts, statistics pointers set: they steer the choice; their values are not read). */
+enum { GC_GEMM_SEL_K4 = 1,          /* 4-wave kernel, 128-row tiles (split-K + reduce kernel when splits > 1) */
+       GC_GEMM_SEL_K8 = 2,          /* 8-wave LDS-DMA kernel, one pass over K */
+       GC_GEMM_SEL_K8_SLICED = 3,   /* 8-wave kernel in k-slices + reduce kernel */
+       GC_GEMM_SEL_FP8 = 4 };       /* e4m3 kernel (k_gemm8q; k-sliced when splits > 1) */
+typedef struct gc_gemm_selection {
+    int kernel;                     /* GC_GEMM_SEL_* */
+    int m_tiles;                    /* 8-wave / fp8 kernels: m-tiles per wave (workgroup rows = 64 m_tiles); 0 for the 4-wave kernel */
+    int splits;                     /* k-slices (1: unsplit) */
+    int ntw;                        /* n-tiles per wave (workgroup columns = 32 ntw) */
+    int parts;                      /* out_chan_parts producer: 0 none asked, 1 the reduce kernel of a k-sliced problem, 2 the GEMM's epilogue, -1 refused */
+    int ln_kind;                    /* lean LayerNorm-fold epilogue: 0 none, 1 row-statistics producer, 2 LayerNorm-folded consumer, 3 the same + softmax heads */
+    int persist;                    /* persistent workgroups of a multi-round short-K linear (0: one workgroup per tile) */
+} gc_gemm_selection;
+int gc_dn_gemm_selection(const gc_gemm_desc *desc, gc_gemm_selection *out);
 int gc_dn_gemm(const gc_gemm_desc *desc, void *stream);
 
 /* Fused multi-K/V-set attention = CrossViewAttnProcessor core, gaussctrl/utils.py:86-117 (+ compute_attn :25-37). */
@@ -425,6 +441,14 @@ typedef struct gc_attn_desc {
     size_t workspace_bytes;          /* one workgroup per (query block, set) + a fixed-order fp32 combine; NULL: one launch as before */
 } gc_attn_desc;
 size_t gc_dn_attention_workspace_bytes(const gc_attn_desc *desc);
+/* The kernel gc_dn_attention(desc) would launch, without launching anything (pure host function; call with the workspace set as for the launch). */
+enum { GC_ATTN_SEL_K5 = 1,          /* head_dim 40: key-split 8-wave k_attn5 (csrc/dn_attn5.hip) */
+       GC_ATTN_SEL_K4 = 2,          /* head_dim 40: k_attn4 */
+       GC_ATTN_SEL_K3 = 3,          /* head_dim 80 (or 40 with kernel_variant bit 1): the 16x16x32 kernel k_attn3 */
+       GC_ATTN_SEL_WIDE_SPLIT = 4,  /* head_dim 160, several sets: k_attn_wide, one workgroup per (query block, set), + k_attn_combine */
+       GC_ATTN_SEL_SPLIT = 5,       /* online-softmax k_attn per (query block, set) + k_attn_combine (small grids) */
+       GC_ATTN_SEL_ONLINE = 6 };    /* online-softmax k_attn, one launch */
+int gc_dn_attention_selection(const gc_attn_desc *desc, int *kernel);
 int gc_dn_attention(const gc_attn_desc *desc, void *stream);
 
 /* The tail of a level-0 transformer block (C = 320, 8 heads) in ONE launch: attn1.to_out + residual, LayerNorm, attn2 (text cross-

@@ -209,3 +209,136 @@ def test_gemm_planning_matches_the_documented_design(built):
     assert plan(lin(1536, 1280, 5120, 256)) == (4, (32, 8, 64))               # FF down projection, 16 x 16 block
     assert plan(lin(384, 1280, 5120, 64))[0] == 10                            # ... 8 x 8 block
     assert plan(lin(6144, 5120, 640, geglu=1)) == (0, (0, 0, 0))
+
+
+# (H, Cin, Cout, stride) of every 3 x 3 conv of one UNet + ControlNet forward at 64 x 64 latents (conv_in with Cin padded to 8), and
+# (L, K, N, geglu) of its plain linears per level; the table holds, per CFG batch of a launch set (12: the short last set of a scene, 24: the
+# default 4 chunks x 3 views, 40: 4 chunks of the plugin's chunk_size 5), (kernel, m-tiles, k-slices, ntw) as launched, the GroupNorm partials
+# layout (rows per slab, slabs per batch, column tile; None: the stand-alone GroupNorm), and (kernel, m-tiles, k-slices, ntw) in the
+# batch-invariant form (plan_rows = the rows of one frame).  Linears also carry the persistent workgroup count.
+_LAUNCH_SET_CONVS = {
+    (64, 320, 320, 1): {12: (("k8", 3, 1, 5), (192, 23, 160), ("k8_sliced", 2, 3, 5)), 24: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 3, 5)), 40: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 3, 5))},
+    (64, 640, 320, 1): {12: (("k8", 3, 1, 5), (192, 23, 160), ("k8_sliced", 2, 4, 5)), 24: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 4, 5)), 40: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 4, 5))},
+    (64, 960, 320, 1): {12: (("k8", 3, 1, 5), (192, 23, 160), ("k8_sliced", 2, 4, 5)), 24: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 4, 5)), 40: (("k8", 4, 1, 5), (256, 16, 160), ("k8_sliced", 2, 4, 5))},
+    (64, 320, 320, 2): {12: (("k8", 2, 1, 5), (128, 8, 160), ("k8_sliced", 2, 3, 5)), 24: (("k8", 3, 1, 5), (192, 7, 160), ("k8_sliced", 2, 3, 5)), 40: (("k8", 3, 1, 5), (192, 7, 160), ("k8_sliced", 2, 3, 5))},
+    (32, 320, 640, 1): {12: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 3, 4)), 24: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 3, 4)), 40: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 3, 4))},
+    (32, 640, 640, 1): {12: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 24: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 40: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4))},
+    (32, 1280, 640, 1): {12: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 24: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 40: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4))},
+    (32, 1920, 640, 1): {12: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 24: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 40: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4))},
+    (32, 960, 640, 1): {12: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 24: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4)), 40: (("k8", 4, 1, 4), (256, 4, 128), ("k8_sliced", 2, 6, 4))},
+    (32, 640, 640, 2): {12: (("k8_sliced", 3, 3, 4), (32, 8, 64), ("k8_sliced", 2, 7, 4)), 24: (("k8", 2, 1, 4), (128, 2, 128), ("k8_sliced", 2, 7, 4)), 40: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 7, 4))},
+    (16, 640, 1280, 1): {12: (("k8", 2, 1, 4), (128, 2, 128), ("k8_sliced", 2, 7, 4)), 24: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 7, 4)), 40: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 7, 4))},
+    (16, 1280, 1280, 1): {12: (("k8", 2, 1, 4), (128, 2, 128), ("k8_sliced", 2, 12, 4)), 24: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4)), 40: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4))},
+    (16, 2560, 1280, 1): {12: (("k8", 2, 1, 4), (128, 2, 128), ("k8_sliced", 2, 12, 4)), 24: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4)), 40: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4))},
+    (16, 1920, 1280, 1): {12: (("k8", 2, 1, 4), (128, 2, 128), ("k8_sliced", 2, 12, 4)), 24: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4)), 40: (("k8", 4, 1, 4), (256, 1, 128), ("k8_sliced", 2, 12, 4))},
+    (16, 1280, 1280, 2): {12: (("k8_sliced", 2, 4, 4), None, ("k8_sliced", 2, 15, 4)), 24: (("k8_sliced", 4, 4, 4), None, ("k8_sliced", 2, 15, 4)), 40: (("k8", 2, 1, 4), None, ("k8_sliced", 2, 15, 4))},
+    (8, 1280, 1280, 1): {12: (("k8_sliced", 2, 4, 4), None, ("k8_sliced", 2, 15, 4)), 24: (("k8_sliced", 4, 4, 4), None, ("k8_sliced", 2, 15, 4)), 40: (("k8", 2, 1, 4), None, ("k8_sliced", 2, 15, 4))},
+    (8, 2560, 1280, 1): {12: (("k8_sliced", 2, 4, 4), None, ("k4", 0, 16, 4)), 24: (("k8_sliced", 4, 4, 4), None, ("k4", 0, 16, 4)), 40: (("k8", 2, 1, 4), None, ("k4", 0, 16, 4))},
+    (64, 8, 320, 1): {12: (("k8", 3, 1, 5), (192, 23, 160), ("k4", 0, 1, 5)), 24: (("k8", 4, 1, 5), (256, 16, 160), ("k4", 0, 1, 5)), 40: (("k8", 4, 1, 5), (256, 16, 160), ("k4", 0, 1, 5))},
+}
+_LAUNCH_SET_LINEARS = {
+    (4096, 320, 320, 0): {12: (("k8", 3, 1, 5), 0, (192, 23, 160), ("k8", 2, 1, 5)), 24: (("k8", 4, 1, 5), 0, (256, 16, 160), ("k8", 2, 1, 5)), 40: (("k8", 4, 1, 5), 0, (256, 16, 160), ("k8", 2, 1, 5))},
+    (4096, 320, 2560, 1): {12: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 24: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 40: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4))},
+    (4096, 1280, 320, 0): {12: (("k8", 3, 1, 5), 0, (192, 23, 160), ("k8", 2, 1, 5)), 24: (("k8", 4, 1, 5), 0, (256, 16, 160), ("k8", 2, 1, 5)), 40: (("k8", 4, 1, 5), 0, (256, 16, 160), ("k8", 2, 1, 5))},
+    (1024, 640, 640, 0): {12: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8", 2, 1, 4)), 24: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8", 2, 1, 4)), 40: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8", 2, 1, 4))},
+    (1024, 640, 5120, 1): {12: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 24: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 40: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4))},
+    (1024, 2560, 640, 0): {12: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8_sliced", 2, 3, 4)), 24: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8_sliced", 2, 3, 4)), 40: (("k8", 4, 1, 4), 0, (256, 4, 128), ("k8_sliced", 2, 3, 4))},
+    (256, 1280, 1280, 0): {12: (("k8", 2, 1, 4), 0, (128, 2, 128), ("k8", 1, 1, 4)), 24: (("k8", 4, 1, 4), 0, (256, 1, 128), ("k8", 2, 1, 4)), 40: (("k8", 4, 1, 4), 0, (256, 1, 128), ("k8", 2, 1, 4))},
+    (256, 1280, 10240, 1): {12: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 24: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4)), 40: (("k8", 4, 1, 4), 256, None, ("k8", 4, 1, 4))},
+    (256, 5120, 1280, 0): {12: (("k8", 2, 1, 4), 0, (128, 2, 128), ("k8_sliced", 2, 6, 4)), 24: (("k8", 4, 1, 4), 0, (256, 1, 128), ("k8_sliced", 2, 6, 4)), 40: (("k8", 4, 1, 4), 0, (256, 1, 128), ("k8_sliced", 2, 6, 4))},
+    (64, 1280, 1280, 0): {12: (("k8", 2, 1, 4), 0, None, ("k8", 2, 1, 4)), 24: (("k8", 1, 1, 4), 0, None, ("k8", 1, 1, 4)), 40: (("k8", 1, 1, 4), 0, None, ("k8", 1, 1, 4))},
+    (64, 5120, 1280, 0): {12: (("k8_sliced", 2, 4, 4), 0, None, ("k8_sliced", 2, 6, 4)), 24: (("k8_sliced", 2, 2, 4), 0, None, ("k8_sliced", 2, 6, 4)), 40: (("k8", 2, 1, 4), 0, None, ("k8_sliced", 2, 6, 4))},
+    (64, 1280, 10240, 1): {12: (("k8", 4, 1, 4), 0, None, ("k8", 2, 1, 4)), 24: (("k8", 4, 1, 4), 256, None, ("k8", 2, 1, 4)), 40: (("k8", 4, 1, 4), 256, None, ("k8", 2, 1, 4))},
+}
+
+
+@pytest.mark.parametrize("B", [12, 24, 40])
+def test_gemm_planning_at_launch_set_batches(built, B):
+    """gc_dn_gemm_selection at the CFG batches of a launch set (DESIGN.md 3.2 "Launch sets"), for the descriptors ops.conv3x3 / ops.linear build
+    (workspace from gc_dn_gemm_workspace_bytes, channel partials asked for where the layout allows them).  The 8 x 8-map convs and the 16 -> 8
+    stride-2 conv of a 24-frame set take the k-sliced 8-wave kernel on 256-row tiles (four whole images) x 4 slices (`img8`); at 12 frames the
+    grid is small (128-row tiles), at 40 it fills a round unsliced.  Pure functions of the descriptor: no GPU needed."""
+    from gaussctrl_amd.sd import ops
+    lib = ctypes.CDLL(built)
+    lib.gc_dn_gemm_workspace_bytes.restype = ctypes.c_size_t
+
+    def finish(d, parts):
+        ws = lib.gc_dn_gemm_workspace_bytes(ctypes.byref(d))
+        if ws:
+            d.workspace = 1; d.workspace_bytes = ws
+        lay = None
+        if parts and d.rows_per_batch >= 256:              # as ops._run_gemm: ask for partials where the layout exists (and <= 64 slabs)
+            d.gn_groups = 32
+            rows, ns, ct = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+            assert lib.gc_dn_gemm_chan_parts_layout(ctypes.byref(d), ctypes.byref(rows), ctypes.byref(ns), ctypes.byref(ct)) == 0
+            if rows.value > 0 and ns.value <= 64:
+                d.out_chan_parts = 1; lay = (rows.value, ns.value, ct.value)
+            else:
+                d.gn_groups = 0
+        s = ops.gemm_selection(d)
+        if lay is not None:           # partials of a k-sliced problem come from the reduce kernel (32-row slabs, 64-column blocks), else from the epilogue
+            assert s["parts"] == (1 if s["splits"] > 1 else 2) and (lay[0] == 32) == (s["splits"] > 1), (s, lay)
+            assert s["splits"] > 1 or lay[0] == 64 * s["m_tiles"], (s, lay)
+        return s, lay
+
+    def conv(H, cin, cout, stride, plan):
+        d = ops.GemmDesc()
+        Ho = H // stride
+        d.dtype = 1; d.mode = 1; d.M, d.N, d.K = B * Ho * Ho, cout, 9 * cin
+        d.B, d.Hi, d.Wi, d.Cin, d.Ho, d.Wo, d.stride, d.pad_lo = B, H, H, cin, Ho, Ho, stride, 1
+        d.rows_per_batch = Ho * Ho; d.out = 1; d.ldc = cout; d.lda = cin; d.zeros = 1
+        d.plan_rows = Ho * Ho if plan else 0
+        return finish(d, not plan)
+
+    def lin(L, K, N, geglu, plan):
+        d = ops.GemmDesc()
+        d.dtype = 1; d.mode = 0; d.M, d.N, d.K = B * L, N, K
+        d.lda = K; d.out = 1; d.ldc = N; d.zeros = 1; d.rows_per_batch = L; d.geglu = geglu
+        d.plan_rows = L if plan else 0
+        return finish(d, not plan and not geglu)
+
+    key = lambda s: (s["kernel"], s["m_tiles"], s["splits"], s["ntw"])
+    got, want = {}, {}
+    for shape, row in _LAUNCH_SET_CONVS.items():
+        (s, lay), (p, _) = conv(*shape, False), conv(*shape, True)
+        got[("conv",) + shape] = (key(s), lay, key(p)); want[("conv",) + shape] = row[B]
+    for shape, row in _LAUNCH_SET_LINEARS.items():
+        (s, lay), (p, _) = lin(*shape, False), lin(*shape, True)
+        got[("linear",) + shape] = (key(s), s["persist"], lay, key(p)); want[("linear",) + shape] = row[B]
+    bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not bad, bad
+    if B == 24:      # the issue's anchor: the bench's 8 x 8-map convs, four whole images per 256-row tile x 4 slices
+        for cin in (1280, 2560):
+            assert got[("conv", 8, cin, 1280, 1)][0] == ("k8_sliced", 4, 4, 4)
+
+
+def test_attention_selection_at_launch_set_batches(built):
+    """gc_dn_attention_selection for the attention problems of a launch set (product form: self set + 4 sets from the cached reference bank; the
+    text attention against 77 shared keys), with and without the set-split workspace (batch-invariant mode never offers it)."""
+    from gaussctrl_amd.sd import ops
+    lib = ctypes.CDLL(built)
+    lib.gc_dn_attention_workspace_bytes.restype = ctypes.c_size_t
+
+    def sel(B, L, D, nsets=5, Lk=None, ws=True, variant=0):
+        d = ops.AttnDesc()
+        d.dtype = 1; d.batch, d.heads, d.head_dim, d.Lq, d.Lk = B, 8, D, L, L if Lk is None else Lk
+        d.frames_per_half = B // 2; d.nsets = nsets; d.q_prescaled = 1; d.kernel_variant = variant
+        wsb = lib.gc_dn_attention_workspace_bytes(ctypes.byref(d))
+        if ws and wsb:
+            d.workspace = 1; d.workspace_bytes = wsb
+        return ops.attention_selection(d)
+
+    for B in (12, 24, 40):
+        assert sel(B, 4096, 40) == "attn5" and sel(B, 4096, 40, nsets=4) == "attn5"
+        assert sel(B, 4096, 40, variant=16) == "attn4" and sel(B, 4096, 40, variant=2) == "attn3" and sel(B, 4096, 40, variant=1) == "attn"
+        assert sel(B, 1024, 80) == "attn3"
+        assert sel(B, 256, 160) == "wide+combine" and sel(B, 256, 160, ws=False) == "attn"
+        assert sel(B, 256, 160, variant=128) == ("attn+combine" if B == 12 else "attn")   # the 64-query form: set split while 4 x 8 x B < 512 workgroups
+        assert sel(B, 64, 160) == "attn+combine" and sel(B, 64, 160, ws=False) == "attn"
+        assert sel(B, 4096, 40, nsets=1, Lk=77) == "attn"                 # text keys: 2 key tiles, the pipelined kernels do not amortise
+    assert sel(64, 64, 160) == "attn"                                     # 512 workgroups: a full grid, no set split
+    assert sel(64, 256, 160, variant=128) == "attn"
+    d = ops.AttnDesc()
+    d.batch, d.heads, d.head_dim, d.Lq, d.Lk, d.nsets = 2, 8, 48, 64, 64, 1
+    with pytest.raises(Exception):
+        ops.attention_selection(d)
