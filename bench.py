@@ -20,6 +20,11 @@ configs[2]); a step is one chunk on every rank.  Collectives on the measured pat
      (`--ref-mode owner0` pins the owner, `--ref-mode replicate` is the A/B without the collective);
   2. one flat all-reduce of the chunk's N x 59 fp32 gradient sum, posted asynchronously from the buffer the backward
      kernel wrote into (two buffers alternate; it completes under the next chunk's denoise).
+
+A plain run does what the headline needs and nothing else: setup, the untimed priming and `--warmup` steps, the `--steps` timed steps,
+`--dump-outputs` if given, and the JSON line.  `--full` adds, after the timed steps and on rank 0: the roofline of the dominant denoise
+kernel and of the rasterizer chain (instrumented extra steps; GC_BENCH_SHAPES=1 prints the per-shape GEMM table of the first), the f16 and
+fp8 secondary measurements (N = 1, bf16 runs) and the CPU baseline (N = 1).  Without it those fields of the line are null.
 """
 from __future__ import annotations
 
@@ -74,6 +79,8 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true")     # skip the short f16 secondary measurement (default workload, N = 1)
     ap.add_argument("--mask", action="store_true")   # BASELINE configs[3]: edits composited through a (synthetic elliptical) mask, gc_pipeline.py:226-234
     ap.add_argument("--dump-outputs", default=None, metavar="DIR")   # after the timed steps: what the last one computed as DIR/<name>.npy (write_outputs)
+    ap.add_argument("--full", action="store_true")   # also the rooflines, the f16 / fp8 secondaries and the CPU baseline (--no-secondary / --no-cpu-baseline
+                                                     # drop one of them again); not the same thing as `--workload full`
     return ap.parse_args()
 
 
@@ -774,15 +781,16 @@ def main():
     dn_s, rs_s = B.halves()          # this rank's GPU time in the two halves (rank 0 reports; ranks run in lock step)
     step = B.step
 
+    # ---------------------------------------------------------------- --full only: everything below up to the result line
     # ---------------------------------------------------------------- roofline of the dominant kernel (instrumented extra step)
     roof = roof_fp8 = None
-    if args.workload == "edit" and rank == 0:
+    if args.full and args.workload == "edit" and rank == 0:
         roof, _ = denoise_roofline(args, args.dtype, pipe, sdops, z0, ctx_neg, ctx_pos, state["bank"], dev)
         if args.dtype == "fp8":
             roof_fp8, _ = denoise_roofline(args, args.dtype, pipe, sdops, z0, ctx_neg, ctx_pos, state["bank"], dev, fp8_class=True)
 
     roof_raster = None
-    if rank == 0:
+    if args.full and rank == 0:
         B.rank0_only = True
         if args.workload == "raster":
             roof = raster_roofline(args, B, g, stats, H * W)
@@ -800,7 +808,7 @@ def main():
 
     # ---------------------------------------------------------------- secondary: the f16 activation path (the dtype that meets north_star's 1e-3)
     secondary = None
-    if rank == 0 and world == 1 and args.workload == "edit" and args.dtype == "bf16" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.workload == "edit" and args.dtype == "bf16" and not args.no_secondary:
         del B, pipe, state, z0, step
         torch.cuda.empty_cache()
         B2 = Bench(args, "f16", rank, world, dev, None, None)
@@ -814,7 +822,7 @@ def main():
     # (+ with --fp8-linears 7 the transformer linears of the C = 640 / 1280 levels), bf16 elsewhere (latents 2.7e-2 from the fp32 oracle: a
     # reported variant, never `value`).  A failure here must not cost the headline line.
     secondary_fp8 = None
-    if rank == 0 and world == 1 and args.workload == "edit" and args.dtype == "bf16" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.workload == "edit" and args.dtype == "bf16" and not args.no_secondary:
         try:
             B3 = Bench(args, "fp8", rank, world, dev, None, None)
             n3 = min(args.steps, B3.cps)
@@ -841,7 +849,7 @@ def main():
 
     # ---------------------------------------------------------------- CPU baseline (oracle, rank 0, bounded sample)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:
@@ -900,6 +908,7 @@ def main():
                           "note": "spans = GPU time between HIP events on each chunk's launch stream (they overlap when several chunks are in flight; the rates above apportion the wall time by their ratio); denoise half = eval renders + disparity + 20-step denoise + VAE decode + reference share; raster half = training render fwd + L1/SSIM + bwd"},
                "mfma_util_step": None if mfma_util is None else round(mfma_util, 4),
                "algorithmic_tflop_timed_region": None if flop is None else round(flop / 1e12, 1),
+               "full": bool(args.full),              # the five fields below are measured with --full only (null otherwise)
                "secondary": secondary, "secondary_fp8": secondary_fp8,
                "roofline": roof, "roofline_raster": roof_raster, "cpu_baseline": cpu}
         if roof_fp8 is not None:          # --dtype fp8: the e4m3 GEMM class against the 5 PF e4m3 peak, and the step against the mixed peak
@@ -907,7 +916,7 @@ def main():
             out["mfma_util_step_mixed_peak"] = round(flop / dt_s / (world * roof_fp8["mixed_peak_tflops"] * 1e12), 4)
         print(json.dumps(out), flush=True)
     if dist is not None:
-        dist.barrier()                      # ranks leave together (rank 0 ran more instrumented steps)
+        dist.barrier()                      # ranks leave together (with --full rank 0 ran more instrumented steps)
         dist.destroy_process_group()
 
 
@@ -983,7 +992,7 @@ def denoise_roofline(args, dtype_name, pipe, sdops, z0, ctx_neg, ctx_pos, bank, 
             g_ = groups.setdefault((fr, lq, ns), [0, 0.0]); g_[0] += 1; g_[1] += s_.elapsed_time(e_)
         roof["rocprofv3_note"] = ("avg_launch_us / launch_kinds are single-stream HIP-event durations of ONE full launch set; a rocprofv3 trace of this command averages every "
                                   "k_attn5 launch of the run (2-chunk sets, 8- / 4-frame reference trajectories: smaller) and times them while a second launch set shares "
-                                  "the GPU (--inflight 2: longer) -- compare per workgroup count with the trace of `bench.py --inflight 1` "
+                                  "the GPU (--inflight 2: longer) -- compare per workgroup count with the trace of `bench.py --full --inflight 1` "
                                   "(profiles/r06_bench_kernel_stats_bf16_single_stream.txt: 2 717 us in the trace vs 2 724 us live for the 3 072-workgroup launches; `scripts/rocpd_stats.py <db> 70 k_attn5`)")
         roof["launch_kinds"] = [{"frames": fr, "queries_per_frame": lq, "kv_sets": ns, "workgroups": fr * 8 * max(1, lq // 256), "launches": n_,
                                  "avg_us": round(1e3 * ms_ / n_, 1)} for (fr, lq, ns), (n_, ms_) in sorted(groups.items(), reverse=True)]

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_denoise_kernels_gpu.py -m gpu -q -x -k "layernorm_folded" 2>&1 | tail -5 > $O/tests_ln.log; tail -2 $O/tests_ln.log
 for V in "GC_X=0" "GC_DN_FOLD_LN=2" "GC_X=0" "GC_DN_FOLD_LN=2"; do
   T=$(echo $V | tr '= ' '__')
-  env $V timeout 600 python bench.py --no-cpu-baseline --no-secondary > $O/bench_$T.json 2> $O/bench_$T.err
+  env $V timeout 600 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_$T.json 2> $O/bench_$T.err
   python -c "
 import json; d=json.loads(open('$O/bench_$T.json').read().strip().splitlines()[-1]); print('$V', d['value'], d['ms_per_step'], {k:(v['launches'], v['ms']) for k,v in d['roofline']['other'].items() if 'linear' in k})"
 done

@@ -12,7 +12,7 @@ GC_GEMM_CONVSPLIT=2 timeout 600 python scripts/bench_kernels.py conv > $O/ubench
 paste -d'|' $O/ubench_conv_default.txt $O/ubench_conv_split2.txt | awk -F'|' '{split($1,a,":"); split($2,b,":"); print a[1] ":" substr(a[2],1,22) " |" substr(b[2],1,22)}'
 for V in "GC_X=0" "GC_GEMM_CONVSPLIT=2" "GC_X=0" "GC_GEMM_CONVSPLIT=2"; do
   T=$(echo $V | tr '= ' '__')
-  env $V timeout 600 python bench.py --no-cpu-baseline --no-secondary > $O/bench_$T.json 2> $O/bench_$T.err
+  env $V timeout 600 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_$T.json 2> $O/bench_$T.err
   python -c "
 import json; d=json.loads(open('$O/bench_$T.json').read().strip().splitlines()[-1]); print('$V', d['value'], d['ms_per_step'], {k:(v['launches'], v['ms']) for k,v in d['roofline']['other'].items() if 'conv' in k})"
 done

@@ -11,7 +11,7 @@ timeout 600 python scripts/bench_kernels.py conv > $O/ubench_conv.txt 2>&1; grep
 timeout 600 python scripts/bench_kernels.py linear > $O/ubench_linear.txt 2>&1; grep -E "M=" $O/ubench_linear.txt
 for L in prev new prev new; do
   if [ $L = prev ]; then export GC_HIP_LIB=$R/gaussctrl_amd/libgaussctrl_hip_prev.so; else unset GC_HIP_LIB; fi
-  GC_BENCH_SHAPES=1 timeout 600 python bench.py --no-cpu-baseline --no-secondary > $O/bench_$L.json 2> $O/bench_$L.err
+  GC_BENCH_SHAPES=1 timeout 600 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_$L.json 2> $O/bench_$L.err
   python -c "
 import json; d=json.loads(open('$O/bench_$L.json').read().strip().splitlines()[-1]); print('$L', d['value'], d['ms_per_step'], {k:(v['launches'], v['ms']) for k,v in d['roofline']['other'].items() if 'gemm' in k})"
 done

@@ -14,7 +14,7 @@ done
 paste -d'|' $O/ubench_conv_0.txt $O/ubench_conv_1.txt | awk -F'|' '{split($1,a,":"); split($2,b,":"); print a[1] ":" substr(a[2],1,22) " |" substr(b[2],1,22)}' | grep -E "16x16|8x8|s2"
 paste -d'|' $O/ubench_linear_0.txt $O/ubench_linear_1.txt | awk -F'|' '{split($1,a,":"); split($2,b,":"); print a[1] ":" substr(a[2],1,22) " |" substr(b[2],1,22)}' | grep -E "K= 5120|K= 2560"
 for V in 0 1 0 1; do
-  GC_FUSED_REDUCE=$V timeout 600 python bench.py --no-cpu-baseline --no-secondary > $O/bench_$V.json 2> $O/bench_$V.err
+  GC_FUSED_REDUCE=$V timeout 600 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_$V.json 2> $O/bench_$V.err
   python -c "
 import json; d=json.loads(open('$O/bench_$V.json').read().strip().splitlines()[-1]); print('FUSED_REDUCE=$V', d['value'], d['ms_per_step'], {k:(v['launches'], v['ms']) for k,v in d['roofline']['other'].items() if 'gemm' in k and 'generic' not in k})"
 done

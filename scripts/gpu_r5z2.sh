@@ -10,7 +10,7 @@ for V in 32 0; do
   GC_ATTN_V=$V timeout 600 python scripts/bench_kernels.py attn 2>&1 | grep -E "L=  256|L=   64" | sed "s/^/ATTN_V=$V /"
 done
 for V in 32 0 32 0; do
-  GC_ATTN_V=$V timeout 600 python bench.py --no-cpu-baseline --no-secondary > $O/bench_$V.json 2> $O/bench_$V.err
+  GC_ATTN_V=$V timeout 600 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_$V.json 2> $O/bench_$V.err
   python -c "
 import json; d=json.loads(open('$O/bench_$V.json').read().strip().splitlines()[-1]); print('ATTN_V=$V', d['value'], d['ms_per_step'], {k:(v['launches'], v['ms'], v['tflops']) for k,v in d['roofline']['other'].items() if 'k_attn' in k})"
 done

@@ -5,9 +5,9 @@ R=$PWD
 O=gpurun_out/${1:-r5zf}
 mkdir -p $O
 export TMPDIR=/tmp
-timeout 1200 python bench.py > $O/bench_bf16.json 2> $O/bench_bf16.err
+timeout 1200 python bench.py --full > $O/bench_bf16.json 2> $O/bench_bf16.err
 for DT in bf16 fp8; do
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof_$DT -o bench -- python $R/bench.py --dtype $DT --no-cpu-baseline --no-secondary > $R/$O/bench_${DT}_profiled.json 2> $R/$O/bench_${DT}_profiled.err)
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof_$DT -o bench -- python $R/bench.py --full --dtype $DT --no-cpu-baseline --no-secondary > $R/$O/bench_${DT}_profiled.json 2> $R/$O/bench_${DT}_profiled.err)
   DB=$(find $O/prof_$DT -name "*.db" | head -1)
   python scripts/rocpd_stats.py $DB 70 > $O/bench_kernel_stats_$DT.txt
   rm -rf $O/prof_$DT

@@ -1,9 +1,10 @@
 #!/bin/bash
 # round 6, call F: chunks per launch set (co-batching) sweep on one box: 2 (default) / 3 / 4 / 7 / 14, in-flight 2 and 1
 mkdir -p gpurun_out/r6f
+O=$_                 # the folder made above
 for cfg in "2 2" "3 2" "4 2" "7 2" "7 1" "14 1" "14 2"; do
   set -- $cfg
-  timeout 400 python bench.py --steps 28 --warmup 14 --cobatch $1 --inflight $2 --no-secondary --no-cpu-baseline > gpurun_out/r6f/bench_cb$1_if$2.json 2> gpurun_out/r6f/bench_cb$1_if$2.err
+  timeout 400 python bench.py --full --steps 28 --warmup 14 --cobatch $1 --inflight $2 --no-secondary --no-cpu-baseline > $O/bench_cb$1_if$2.json 2> $O/bench_cb$1_if$2.err
   python - <<PY
 import json
 try:

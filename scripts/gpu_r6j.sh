@@ -18,7 +18,7 @@ json.dump(out, open("profiles/r06_raster_traffic_views8.json","w"))
 json.dump(out, open("$O/r06_raster_traffic_views8.json","w"))
 PY
 for NG in 1000000 4000000; do
-  timeout 600 python bench.py --workload raster --gaussians $NG --steps 32 --warmup 2 --no-cpu-baseline > $O/raster_${NG}.json 2> $O/raster_${NG}.err
+  timeout 600 python bench.py --full --workload raster --gaussians $NG --steps 32 --warmup 2 --no-cpu-baseline > $O/raster_${NG}.json 2> $O/raster_${NG}.err
   python -c "
 import json; d=json.loads(open('$O/raster_${NG}.json').read().strip().splitlines()[-1]); c=d['roofline']['chain']; print('$NG', d['value'], c['kernel_us_per_view'], 'frac', c['frac'], 'counters', c['frac_counters'], 'ratio', c['traffic_ratio'])
 print({k:(v['avg_us'], v.get('traffic_MB'), v.get('traffic_GBps')) for k,v in d['roofline']['stages'].items()})"

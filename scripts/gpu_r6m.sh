@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r6m
 mkdir -p $O
 for v in 0 32 0 32; do
-  GC_GEMM_DBG=$v timeout 400 python bench.py --steps 28 --warmup 14 --no-secondary --no-cpu-baseline > $O/bench_dbg$v.json 2> $O/bench_dbg$v.err
+  GC_GEMM_DBG=$v timeout 400 python bench.py --full --steps 28 --warmup 14 --no-secondary --no-cpu-baseline > $O/bench_dbg$v.json 2> $O/bench_dbg$v.err
   python -c "
 import json
 d=json.loads([l for l in open('$O/bench_dbg$v.json') if l.startswith('{')][-1])

@@ -23,7 +23,7 @@ PY
 done 2>&1 | grep -v "^timing" | tee $O/attn5_ab.txt
 for b in old new old new; do
   if [ $b = old ]; then cp gaussctrl_amd/attn5_old_build.so.bak gaussctrl_amd/libgaussctrl_hip.so; else cp /tmp/new.so gaussctrl_amd/libgaussctrl_hip.so; fi
-  timeout 400 python bench.py --steps 28 --warmup 14 --no-secondary --no-cpu-baseline > $O/bench_$b.json 2> $O/bench_$b.err
+  timeout 400 python bench.py --full --steps 28 --warmup 14 --no-secondary --no-cpu-baseline > $O/bench_$b.json 2> $O/bench_$b.err
   python -c "
 import json
 d=json.loads([l for l in open('$O/bench_$b.json') if l.startswith('{')][-1])

@@ -7,11 +7,11 @@ O=gpurun_out/r6q
 mkdir -p $O
 export TMPDIR=/tmp
 export GC_BENCH_ONE_GPU=1 GC_BENCH_BACKEND=gloo
-timeout 900 python bench.py --gpus 2 --steps 8 --warmup 2 --denoise-steps 4 --gaussians 200000 --no-secondary --no-cpu-baseline > $O/bench_2_selflaunch.json 2> $O/bench_2_selflaunch.err
+timeout 900 python bench.py --full --gpus 2 --steps 8 --warmup 2 --denoise-steps 4 --gaussians 200000 --no-secondary --no-cpu-baseline > $O/bench_2_selflaunch.json 2> $O/bench_2_selflaunch.err
 echo "self-launch --gpus 2 rc=$?"; tail -1 $O/bench_2_selflaunch.json | cut -c1-260; tail -2 $O/bench_2_selflaunch.err | cut -c1-300
 for CFG in "4 rotate" "2 allgather" "8 replicate"; do
   set -- $CFG; N=$1; MODE=$2
-  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --steps 8 --warmup 2 --ref-mode $MODE --denoise-steps 4 --gaussians 200000 --no-secondary --no-cpu-baseline > $O/bench_${N}_$MODE.json 2> $O/bench_${N}_$MODE.err
+  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --full --gpus $N --steps 8 --warmup 2 --ref-mode $MODE --denoise-steps 4 --gaussians 200000 --no-secondary --no-cpu-baseline > $O/bench_${N}_$MODE.json 2> $O/bench_${N}_$MODE.err
   echo "$N $MODE rc=$?"; tail -1 $O/bench_${N}_$MODE.json | cut -c1-260; tail -2 $O/bench_${N}_$MODE.err | cut -c1-300
 done
 unset GC_BENCH_ONE_GPU GC_BENCH_BACKEND
@@ -23,8 +23,8 @@ for qs in (0.5, 0.7, 0.84, 1.0):
     for dt in (torch.bfloat16, torch.float16):
         a.timing(dt, 0, iters=10, qscale=qs)
 PY
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_bf16.json 2> $O/bench_bf16.err
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err)
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_bf16.json 2> $O/bench_bf16.err
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o bench -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err)
 DB=$(find $O/prof -name "*.db" | head -1)
 python scripts/rocpd_stats.py $DB 70 k_attn5 > $O/bench_kernel_stats_bf16.txt
 rm -rf $O/prof

@@ -6,7 +6,7 @@ R=$PWD
 O=gpurun_out/r6za
 mkdir -p $O
 export TMPDIR=/tmp
-(cd /tmp && GC_DN_STREAMS=0 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline --no-secondary > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err)
+(cd /tmp && GC_DN_STREAMS=0 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o bench -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline --no-secondary > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err)
 DB=$(find $O/prof -name "*.db" | head -1)
 python scripts/rocpd_stats.py $DB 70 k_attn5 > $O/bench_kernel_stats_single_stream.txt
 rm -rf $O/prof

@@ -45,3 +45,15 @@ def test_mismatched_rank_count_is_a_clear_error():
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stdout + r.stderr) and "AssertionError" not in r.stderr
+
+
+def test_full_is_opt_in(monkeypatch):
+    """a plain run measures the headline alone; the rooflines, secondaries and CPU baseline run only with --full"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert b.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert b.parse().full is True
