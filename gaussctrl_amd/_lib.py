@@ -20,6 +20,7 @@ SYMBOLS = [
     "gc_raster_map_intersects", "gc_raster_pad_intersects", "gc_raster_sort_workspace_bytes",
     "gc_raster_sort_intersects", "gc_raster_tile_bins",
     "gc_raster_depth_order_workspace_bytes", "gc_raster_depth_order", "gc_raster_bin_workspace_bytes", "gc_raster_bin_tiles", "gc_raster_bin_tiles_dev", "gc_raster_bin_tiles_boxes", "gc_rasterize_fwd", "gc_rasterize_bwd", "gc_rasterize_bwd_clamped",
+    "gc_rasterize_nd_fwd", "gc_rasterize_nd_bwd",
     "gc_project_sh_fwd", "gc_project_sh_fwd_boxes", "gc_project_sh_bwd", "gc_project_sh_bwd_accumulate", "gc_raster_finalize", "gc_raster_finalize_into",
     "gc_l1_ssim_workspace_bytes", "gc_l1_ssim_fwd_bwd", "gc_adam_step",
     # batched views (round 5)

@@ -251,20 +251,50 @@ def _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, backgrou
     return v_xy, v_conic, v_col, v_op
 
 
+def _rasterize_nd_fwd(H, W, tb, ids_s, bins, xys, conics, colors, opac, background):
+    """colors[N,C] for any C (gc_rasterize_nd_fwd) -> out_img[H,W,C], final_Ts, final_index"""
+    dev = xys.device
+    C = colors.shape[1]
+    out = torch.empty(H, W, C, device=dev)
+    fT = torch.empty(H, W, device=dev)
+    fi = torch.empty(H, W, dtype=torch.int32, device=dev)
+    L.check(L.lib().gc_rasterize_nd_fwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i32(C), L.ptr(ids_s), L.ptr(bins),
+                                        L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(out),
+                                        L.ptr(fT), L.ptr(fi), L.stream_ptr()), "gc_rasterize_nd_fwd")
+    return out, fT, fi
+
+
+def _rasterize_nd_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, background, fT, fi, v_out, v_alpha):
+    dev = xys.device
+    C = colors.shape[1]
+    v_xy = torch.zeros(N, 2, device=dev); v_conic = torch.zeros(N, 3, device=dev)
+    v_col = torch.zeros(N, C, device=dev); v_op = torch.zeros(N, device=dev)
+    L.check(L.lib().gc_rasterize_nd_bwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.i32(C), L.ptr(ids_s), L.ptr(bins),
+                                        L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT), L.ptr(fi),
+                                        L.ptr(v_out), L.ptr(v_alpha), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
+                                        L.stream_ptr()), "gc_rasterize_nd_bwd")
+    return v_xy, v_conic, v_col, v_op
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, H, W, background, return_alpha):
         _need_gpu(xys, colors)
-        if colors.dim() != 2 or colors.shape[1] != 3:
-            raise ValueError("rasterize_gaussians: colors must be [N,3] (the reference only uses 3 channels)")
-        N = xys.shape[0]
+        if colors.dim() != 2 or colors.shape[1] < 1:
+            raise ValueError("rasterize_gaussians: colors must be [N,C] with C >= 1")
+        N, C = xys.shape[0], colors.shape[1]
+        if background is not None and background.numel() != C:
+            raise ValueError(f"rasterize_gaussians: background has {background.numel()} values, colors has {C} channels")
         dev = xys.device
         tb = ((W + TILE - 1) // TILE, (H + TILE - 1) // TILE, 1)
         x, d, r, c, nth = _c(xys), _c(depths), _c(radii, torch.int32), _c(conics), _c(num_tiles_hit, torch.int32)
         col, op = _c(colors), _c(opacity).reshape(-1)
-        bg = _c(background) if background is not None else torch.ones(3, device=dev)
+        bg = _c(background).reshape(-1) if background is not None else torch.ones(C, device=dev)
         M, keys_s, ids_s, bins, _ = bin_and_sort_gaussians(N, x, d, r, nth, tb)
-        out, _, fT, fi = _rasterize_fwd(H, W, tb, ids_s, bins, x, c, col, op, None, bg)
+        if C == 3:
+            out, _, fT, fi = _rasterize_fwd(H, W, tb, ids_s, bins, x, c, col, op, None, bg)
+        else:                                   # gsplat's nd_rasterize_forward
+            out, fT, fi = _rasterize_nd_fwd(H, W, tb, ids_s, bins, x, c, col, op, bg)
         ctx.save_for_backward(ids_s, bins, x, c, col, op, bg, fT, fi)
         ctx.meta = (H, W, tb, N)
         if return_alpha:
@@ -277,13 +307,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         H, W, tb, N = ctx.meta
         vo = _c(v_out)
         va = _c(v_alpha) if v_alpha is not None else None
-        v_xy, v_conic, v_col, v_op = _rasterize_bwd(H, W, tb, N, ids_s, bins, x, c, col, op, bg, fT, fi, vo, va)
+        bwd = _rasterize_bwd if col.shape[1] == 3 else _rasterize_nd_bwd
+        v_xy, v_conic, v_col, v_op = bwd(H, W, tb, N, ids_s, bins, x, c, col, op, bg, fT, fi, vo, va)
         return v_xy, None, None, v_conic, None, v_col, v_op[:, None], None, None, None, None
 
 
 def rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
                         background=None, return_alpha=False):
-    """gsplat 0.1.3 signature; out_img[H,W,3] (, out_alpha[H,W])."""
+    """gsplat 0.1.3 signature; colors[N,C] for any C >= 1 -> out_img[H,W,C] (, out_alpha[H,W]).  C == 3 runs the RGB kernels
+    (gc_rasterize_fwd / _bwd), every other C the N-channel ones (gc_rasterize_nd_fwd / _bwd), as gsplat dispatches.  background[C]
+    defaults to ones(C); uint8 colours are divided by 255."""
+    if colors.dtype == torch.uint8:
+        colors = colors.float() / 255
     return _RasterizeGaussians.apply(xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
                                      background, return_alpha)
 

@@ -160,6 +160,25 @@ int gc_rasterize_bwd_clamped(int img_h, int img_w, int tiles_x, int tiles_y, int
                              const float *v_out, const float *v_out_alpha, const float *pre_clamp,
                              float *v_xy, float *v_conic, float *v_colors, float *v_opacity, void *stream);
 
+/* gsplat.rasterize_gaussians for any channel count (its nd_rasterize_forward): colors[N,C] and background[C] (device) ->
+ * out_img[H,W,C], final_Ts[H,W], final_index[H,W] (both bit-identical to gc_rasterize_fwd's on the same lists).  Channels are
+ * composited in chunks of at most 32 (grid.z): C <= 32 is one chunk of the smallest width in {1, 2, 4, 8, 16, 32} >= C, larger C is
+ * C / 32 chunks of 32 plus one narrower chunk for the rest; every chunk re-walks the tile list.  GC_EINVAL unless channels >= 1,
+ * channels / 32 < 65536 and H * W * channels < 2^31 elements (checked before any launch). */
+int gc_rasterize_nd_fwd(int img_h, int img_w, int tiles_x, int tiles_y, int channels,
+                        const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                        const float *xys, const float *conics, const float *colors, const float *opacities,
+                        const float *background, float *out_img, float *final_Ts, int32_t *final_index, void *stream);
+/* its backward (nd_rasterize_backward): v_out[H,W,C], v_out_alpha[H,W] or NULL -> v_xy[N,2], v_conic[N,3], v_colors[N,C],
+ * v_opacity[N], which must be zero-filled by the caller (accumulated atomically).  Same chunking and limits as the forward, and
+ * also N * channels < 2^31 elements. */
+int gc_rasterize_nd_bwd(int img_h, int img_w, int tiles_x, int tiles_y, int64_t N, int channels,
+                        const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                        const float *xys, const float *conics, const float *colors, const float *opacities,
+                        const float *background, const float *final_Ts, const int32_t *final_index,
+                        const float *v_out, const float *v_out_alpha,
+                        float *v_xy, float *v_conic, float *v_colors, float *v_opacity, void *stream);
+
 /* Fused per-Gaussian front end of GaussCtrlModel.get_outputs (gaussctrl/gc_model.py:138-169,181):
  * exp(scales), quat normalisation, projection, view directions, SH(+0.5, clamp min 0), sigmoid(opacity)
  * in ONE pass over the 59-float parameter record.
