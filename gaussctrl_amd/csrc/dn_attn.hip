@@ -796,17 +796,16 @@ void launch_attn3(const AttnArgs &a, int B, hipStream_t s)
 #define ATT80_QT 1
 #endif
 // The kernel of one problem (shared by the launcher and gc_dn_attention_selection); 0 = unsupported head dim
-int attn_route(const AttnArgs &a, int D, int B, int variant)
+int attn_route(const AttnArgs &a, int D, int B, const AttnVariant &v)
 {
-    const bool fast = !(variant & 1);      // kernel_variant bit 0: online-softmax kernel everywhere (tests)
-    if (fast && (int64_t)a.nsets * ((a.Lk + 63) / 64) >= 4) {   // short key streams: the pipeline's fill / LDS set-up does not amortise
-        // D = 40 default: k_attn5 (key-split 8-wave form, dn_attn5.hip) when the tile shapes fit; kernel_variant bit 4 keeps k_attn4 (A/B)
-        if (D == 40) return (!(variant & 30) && (a.Lk & 63) == 0 && (a.Lq & 255) == 0) ? GC_ATTN_SEL_K5 : (variant & 2) ? GC_ATTN_SEL_K3 : GC_ATTN_SEL_K4;
+    if (!v.online_only && (int64_t)a.nsets * ((a.Lk + 63) / 64) >= 4) {   // short key streams: the pipeline's fill / LDS set-up does not amortise
+        // D = 40 default: k_attn5 (key-split 8-wave form, dn_attn5.hip) when the tile shapes fit and no switch keeps it off (A/B)
+        if (D == 40) return (!v.off_k5() && (a.Lk & 63) == 0 && (a.Lq & 255) == 0) ? GC_ATTN_SEL_K5 : v.d40_k3 ? GC_ATTN_SEL_K3 : GC_ATTN_SEL_K4;
         if (D == 80) return GC_ATTN_SEL_K3;
     }
     // Few workgroups and several K/V sets (D = 160 at 16x16 / 8x8: 192 / 48 workgroups of one wave per SIMD, nobody to hide the
     // S -> max -> exp -> P V dependency chain): one workgroup per (query block, set) + a fixed-order fp32 combine
-    if (D == 160 && a.part && a.nsets > 1 && (a.Lq & 255) == 0 && !(variant & 128)) return GC_ATTN_SEL_WIDE_SPLIT;   // kernel_variant bit 7: the 64-query form (A/B, tests)
+    if (D == 160 && a.part && a.nsets > 1 && (a.Lq & 255) == 0 && !v.d160_q64) return GC_ATTN_SEL_WIDE_SPLIT;   // (d160_q64: the 64-query form, A/B and tests)
     if (D != 8 && D != 16 && D != 32 && D != 40 && D != 64 && D != 80 && D != 160) return 0;
     const int qq = D == 160 ? 1 : 2;                     // (GC_ATT below: queries per workgroup = 64 qq)
     const int64_t nwg = (int64_t)((a.Lq + 64 * qq - 1) / (64 * qq)) * a.H * B;
@@ -814,18 +813,18 @@ int attn_route(const AttnArgs &a, int D, int B, int variant)
 }
 
 template <class T>
-int launch_attn(const AttnArgs &a, int D, int B, int variant, hipStream_t s)
+int launch_attn(const AttnArgs &a, int D, int B, const AttnVariant &v, hipStream_t s)
 {
-    const int route = attn_route(a, D, B, variant);
+    const int route = attn_route(a, D, B, v);
     switch (route) {
-    case GC_ATTN_SEL_K5: gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, (variant & 32) ? 4 : (variant & 64) ? 8 : 6, s); return GC_OK;
+    case GC_ATTN_SEL_K5: gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, v.ring, s); return GC_OK;
     case GC_ATTN_SEL_K4:
-        if (variant & 4) launch_attn4<T, 40, 3, 8>(a, B, s);             // bit 2: 8 waves, one workgroup per CU
-        else if (variant & 8) launch_attn4<T, 40, 4, 4, 3, 2>(a, B, s);  // bit 3: 64 queries per wave (one wave per SIMD)
+        if (v.k4_8wave) launch_attn4<T, 40, 3, 8>(a, B, s);              // 8 waves, one workgroup per CU
+        else if (v.k4_q64) launch_attn4<T, 40, 4, 4, 3, 2>(a, B, s);     // 64 queries per wave (one wave per SIMD)
         else launch_attn4<T, 40, 3, 4>(a, B, s);
         return GC_OK;
     case GC_ATTN_SEL_K3:
-        if (D == 40) launch_attn3<T, 40, 2, 3>(a, B, s);                 // kernel_variant bit 1: the 16x16x32 form (A/B measurements)
+        if (D == 40) launch_attn3<T, 40, 2, 3>(a, B, s);                 // GC_ATTN_VAR_D40_K3: the 16x16x32 form (A/B measurements)
         else launch_attn3<T, 80, ATT80_QT, 3>(a, B, s);
         return GC_OK;
     case GC_ATTN_SEL_WIDE_SPLIT: {
@@ -889,10 +888,12 @@ extern "C" int gc_dn_attention_selection(const gc_attn_desc *d, int *kernel)
 {
     GC_REQUIRE(d && kernel, "null argument");
     GC_REQUIRE(d->nsets >= 1 && d->nsets <= 5, "1..5 K/V sets");
+    const AttnVariant v = decode_variant(d->kernel_variant);
+    if (const int rc = refuse_variant_bits(__func__, v.undefined)) return rc;
     AttnArgs a{};
     a.Lq = d->Lq; a.Lk = d->Lk; a.H = d->heads; a.nsets = d->nsets;
     a.part = attn_part(d);
-    *kernel = attn_route(a, d->head_dim, d->batch, d->kernel_variant);
+    *kernel = attn_route(a, d->head_dim, d->batch, v);
     if (!*kernel) { gc::set_error("gc_dn_attention_selection: unsupported head dim %d", d->head_dim); return GC_EINVAL; }
     return GC_OK;
 }
@@ -904,6 +905,8 @@ extern "C" int gc_dn_attention(const gc_attn_desc *d, void *stream)
     GC_REQUIRE(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldvt % 8 == 0 && d->ldo % 4 == 0 && d->head_dim % 8 == 0,
                "leading dimensions must keep 16-byte alignment");
     GC_REQUIRE(d->ldvt >= (d->Lk + 7) / 8 * 8, "Vt rows must hold round_up(Lk, 8) tokens (zero padded)");
+    const AttnVariant v = decode_variant(d->kernel_variant);
+    if (const int rc = refuse_variant_bits(__func__, v.undefined)) return rc;
     AttnArgs a;
     a.Q = (const unsigned short *)d->Q; a.ldq = d->ldq; a.q_bs = d->q_batch_stride;
     a.K = (const unsigned short *)d->K; a.ldk = d->ldk; a.k_bs = d->k_batch_stride;
@@ -918,10 +921,10 @@ extern "C" int gc_dn_attention(const gc_attn_desc *d, void *stream)
     GC_REQUIRE((d->Kref == nullptr) == (d->Vtref == nullptr), "Kref and Vtref must be given together");
     for (int i = 0; i < d->nsets; ++i) GC_REQUIRE(d->set_kind[i] >= -2 && d->set_kind[i] < a.ref_fph, "bad set_kind");
     a.scale_log2e = d->q_prescaled ? 1.f : d->scale * 1.4426950408889634f;
-    a.abl = d->kernel_variant >> 8;
+    a.abl = v.abl | v.cshift << ABL_CSHIFT_SHIFT;
     a.part = attn_part(d);
-    int rc = d->dtype == DT_BF16 ? launch_attn<BF16>(a, d->head_dim, d->batch, d->kernel_variant, gc::S(stream))
-             : d->dtype == DT_F16 ? launch_attn<F16>(a, d->head_dim, d->batch, d->kernel_variant, gc::S(stream)) : GC_EINVAL;
+    int rc = d->dtype == DT_BF16 ? launch_attn<BF16>(a, d->head_dim, d->batch, v, gc::S(stream))
+             : d->dtype == DT_F16 ? launch_attn<F16>(a, d->head_dim, d->batch, v, gc::S(stream)) : GC_EINVAL;
     if (rc != GC_OK) return rc;
     return gc::check_launch("gc_dn_attention");
 }

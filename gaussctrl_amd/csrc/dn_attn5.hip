@@ -74,14 +74,14 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
         if (hg == HS) qf[qb][KSS].x = pack2<T>(0.f, -BIG);
     }
     const float c2 = a.scale_log2e;
-    // Experiment hook (kernel_variant bits 16..20, default 0): P = exp2(s - m0 - cshift).  In f16 P must stay below 2^16, so a row whose
+    // Experiment hook (GC_ATTN_VAR_CSHIFT_*, default 0): P = exp2(s - m0 - cshift).  In f16 P must stay below 2^16, so a row whose
     // later keys beat the sampled maximum by 16 binades sends its workgroup to the safe body; a positive shift widens that margin but moves
     // every P down by as many binades, into f16's subnormal range (fewer significant bits below 2^-14, zero below 2^-24), and the error grew
     // with it (round 3, profiles/r03_attn5_f16_window.txt: relative L2 3e-4 -> 5e-3 -> 8e-2 at shift 0 / 4 / 8), so f16 keeps shift 0 and its
     // data-dependent fallback rate; bf16's 8-bit exponent never gets there.  At shift 0 a subnormal P is NOT flushed: a row whose sampled
     // maximum sits 14 - 16 binades above the rest of its set keeps their ~12 % of the mass
     // (tests/test_launch_set_kernels_gpu.py::test_attention_keys_far_below_the_sampled_maximum).
-    const float cshift = (float)((a.abl >> 8) & 31) / (PRE ? 1.f : c2);
+    const float cshift = (float)((a.abl >> ABL_CSHIFT_SHIFT) & ABL_CSHIFT_MAX) / (PRE ? 1.f : c2);
     const int abl = ABL ? __builtin_amdgcn_readfirstlane(a.abl) : 0;
     float abl_x = -(float)(lane & 7);
     unsigned abl_sink = 0;
@@ -629,7 +629,7 @@ void gc_dn_launch_attn5(const void *args, int dtype, int B, int depth, hipStream
 {
     (void)depth;       // ring depths 4 / 6 / 8 measured equal (profiles/r03_attn5_ablation.txt): 4 stages, which divides the 64 tiles of L = 4096
     const AttnArgs &a = *static_cast<const AttnArgs *>(args);
-    if (a.abl & 0xff) { launch_attn5_<BF16, true, 4, true>(a, B, s); return; }
+    if (a.abl & ABL_BYTE) { launch_attn5_<BF16, true, 4, true>(a, B, s); return; }
     if (dtype == DT_BF16) launch_attn5<BF16, 4>(a, B, s);
     else launch_attn5<F16, 4>(a, B, s);
 }

@@ -21,7 +21,7 @@ struct AttnArgs {
     int nsets; int set_kind[5]; float set_w[5];      // kind -1: own frame; -2: frame b / f (shared text K/V); r >= 0: reference r of the half
     float scale_log2e;
     int nqb;                                         // query blocks per (batch, head)
-    int abl;                                         // timing ablations of k_attn5's instrumented instantiation (kernel_variant >> 8; 0 in production)
+    int abl;                                         // k_attn5 experiments (0 in production): ablation byte & ABL_BYTE, cshift at ABL_CSHIFT_SHIFT
     float *part;                                     // set-split launches (k_attn, gridDim.y = nsets): fp32 [nsets][B][Lq][H*D] weighted per-set outputs
 };
 
@@ -36,6 +36,30 @@ __device__ __forceinline__ void block_coords(const AttnArgs &a, int QT, int &qbl
     h = bh % a.H; b = bh / a.H;
 }
 
+
+// AttnArgs.abl keeps the two experiment fields as gc_attn_desc.kernel_variant packs them, the ablation byte lowest
+constexpr int ABL_BYTE = GC_ATTN_VAR_ABL_MASK >> GC_ATTN_VAR_ABL_SHIFT, ABL_CSHIFT_SHIFT = GC_ATTN_VAR_CSHIFT_SHIFT - GC_ATTN_VAR_ABL_SHIFT,
+              ABL_CSHIFT_MAX = GC_ATTN_VAR_CSHIFT_MASK >> GC_ATTN_VAR_CSHIFT_SHIFT;
+
+// gc_attn_desc.kernel_variant decoded (GC_ATTN_VAR_* in gaussctrl_hip.h; all zero = the product)
+struct AttnVariant {
+    bool online_only, d40_k3, k4_8wave, k4_q64, k4;
+    int ring;              // stages asked of k_attn5's LDS ring: 4, 8 or the default 6
+    bool d160_q64;
+    int abl, cshift;       // -> AttnArgs.abl
+    int undefined;         // bits no switch owns: refused where there is an error channel (dn::refuse_variant_bits)
+    bool off_k5() const { return d40_k3 || k4_8wave || k4_q64 || k4; }      // a switch sends head_dim 40 to another kernel than k_attn5
+};
+inline AttnVariant decode_variant(int kv)
+{
+    const auto bit = [kv](int b) { return (kv & b) != 0; };
+    constexpr int flags = GC_ATTN_VAR_ONLINE_ONLY | GC_ATTN_VAR_D40_K3 | GC_ATTN_VAR_K4_8WAVE | GC_ATTN_VAR_K4_Q64 | GC_ATTN_VAR_K4 | GC_ATTN_VAR_RING4 |
+                          GC_ATTN_VAR_RING8 | GC_ATTN_VAR_D160_Q64;
+    return {bit(GC_ATTN_VAR_ONLINE_ONLY), bit(GC_ATTN_VAR_D40_K3), bit(GC_ATTN_VAR_K4_8WAVE), bit(GC_ATTN_VAR_K4_Q64), bit(GC_ATTN_VAR_K4),
+            bit(GC_ATTN_VAR_RING4) ? 4 : bit(GC_ATTN_VAR_RING8) ? 8 : 6, bit(GC_ATTN_VAR_D160_Q64),
+            (kv & GC_ATTN_VAR_ABL_MASK) >> GC_ATTN_VAR_ABL_SHIFT, (kv & GC_ATTN_VAR_CSHIFT_MASK) >> GC_ATTN_VAR_CSHIFT_SHIFT,
+            kv & ~(flags | GC_ATTN_VAR_ABL_MASK | GC_ATTN_VAR_CSHIFT_MASK)};
+}
 
 template <class T> struct One;
 template <> struct One<BF16> { static constexpr unsigned short v = 0x3F80; };

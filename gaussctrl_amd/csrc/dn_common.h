@@ -12,6 +12,14 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 // dtype codes of the C ABI
 enum { DT_BF16 = 0, DT_F16 = 1 };
 
+// kernel_variant bits that no GC_GEMM_VAR_* / GC_ATTN_VAR_* switch owns (`bad`, from the decode): GC_EINVAL with a message naming them
+inline int refuse_variant_bits(const char *fn, int bad)
+{
+    if (!bad) return GC_OK;
+    gc::set_error("%s: kernel_variant bits 0x%x belong to no switch", fn, (unsigned)bad);
+    return GC_EINVAL;
+}
+
 struct BF16 {
     using elem = __bf16;
     using vec8 = bf16x8;

@@ -6,6 +6,28 @@
 
 namespace {
 
+// gc_gemm_desc.kernel_variant decoded (GC_GEMM_VAR_* in gaussctrl_hip.h; the product: use8 1, convsplit 2, everything else 0)
+struct GemmVariant {
+    int force_mt;          // 2 | 3 | 4: forced m-tiles per wave of the 8-wave kernel
+    int use8;              // 0: 4-wave kernel only, 1: automatic, 2: force the 8-wave kernel
+    int convsplit;         // k-slices on the 8-wave kernel for part-filled conv grids: 0 none, 1 not the small ones, 2 all
+    bool no_wg2, no_persist, full_epilogue, no_lean_ln, tap_outer;
+    int forced_pw, slice_mt, epi_abl;      // panel width + 1; m-tiles per wave of the k-sliced problems; -> GemmArgs.dbg
+    int undefined;         // bits no switch owns: refused where there is an error channel (refuse_variant_bits)
+};
+GemmVariant decode_variant(int kv)
+{
+    const auto bit = [kv](int b) { return (kv & b) != 0; };
+    const auto field = [kv](int mask, int shift) { return (kv & mask) >> shift; };
+    constexpr int flags = GC_GEMM_VAR_K4_ONLY | GC_GEMM_VAR_FORCE_K8 | GC_GEMM_VAR_NO_CONV_SLICES | GC_GEMM_VAR_NO_SMALL_CONV_SLICES | GC_GEMM_VAR_NO_WG2 |
+                          GC_GEMM_VAR_NO_PERSIST | GC_GEMM_VAR_FULL_EPILOGUE | GC_GEMM_VAR_NO_LEAN_LN | GC_GEMM_VAR_TAP_OUTER;
+    return {field(GC_GEMM_VAR_MT_MASK, GC_GEMM_VAR_MT_SHIFT), bit(GC_GEMM_VAR_K4_ONLY) ? 0 : bit(GC_GEMM_VAR_FORCE_K8) ? 2 : 1,
+            bit(GC_GEMM_VAR_NO_CONV_SLICES) ? 0 : bit(GC_GEMM_VAR_NO_SMALL_CONV_SLICES) ? 1 : 2,
+            bit(GC_GEMM_VAR_NO_WG2), bit(GC_GEMM_VAR_NO_PERSIST), bit(GC_GEMM_VAR_FULL_EPILOGUE), bit(GC_GEMM_VAR_NO_LEAN_LN), bit(GC_GEMM_VAR_TAP_OUTER),
+            field(GC_GEMM_VAR_PW_MASK, GC_GEMM_VAR_PW_SHIFT), field(GC_GEMM_VAR_SLICE_MT_MASK, GC_GEMM_VAR_SLICE_MT_SHIFT), field(GC_GEMM_VAR_EPI_ABL_MASK, GC_GEMM_VAR_EPI_ABL_SHIFT),
+            kv & ~(flags | GC_GEMM_VAR_MT_MASK | GC_GEMM_VAR_PW_MASK | GC_GEMM_VAR_SLICE_MT_MASK | GC_GEMM_VAR_EPI_ABL_MASK)};
+}
+
 int choose_splits(int64_t blocks, int nk)
 {
     // split only long-K / few-tile problems (3x3 convs on 16x16 and 8x8 maps): each slice keeps >= 8 k-tiles and the
@@ -55,11 +77,10 @@ int choose_pw(int64_t nbm, int64_t nbn, int64_t total_wgs, int conc, int64_t bm,
     return best;
 }
 
-// kernel_variant bits 16..23: n + 1 forces panel width n (0 = whole rows) -- experiments / the bit-identity test
-int pw_of(const gc_gemm_desc *d, int64_t nbm, int64_t nbn, int64_t total_wgs, int conc, int64_t bm, int64_t bn)
+// (a forced panel width: experiments / the bit-identity test)
+int pw_of(const gc_gemm_desc *d, const GemmVariant &v, int64_t nbm, int64_t nbn, int64_t total_wgs, int conc, int64_t bm, int64_t bn)
 {
-    const int f = (d->kernel_variant >> 16) & 0xff;
-    if (f) return f - 1;
+    if (v.forced_pw) return v.forced_pw - 1;
     return choose_pw(nbm, nbn, total_wgs, conc, bm, bn, d->mode == 1);
 }
 
@@ -83,9 +104,9 @@ void plan(const gc_gemm_desc *d, int *ntw, int *splits, int *tps)
 // split-K reduce kernels of the 2-byte path finish them (and leave the GroupNorm partials).  assume_ws: size query before the caller
 // has a workspace.
 struct SelQ { int ntw, mt, splits, tps; };
-void select_fp8(const gc_gemm_desc *d, SelQ *o, bool assume_ws)
+void select_fp8(const gc_gemm_desc *d, const GemmVariant &v, SelQ *o, bool assume_ws)
 {
-    const int force_mt = d->kernel_variant & 7;
+    const int force_mt = v.force_mt;
     o->ntw = (d->N % 160 == 0 && d->N % 128 != 0 && !d->geglu) ? 5 : 4;      // (GEGLU pairs n-tiles inside a wave: even count)
     // the e4m3 fragments are 8 registers each (32 k per lane): only the variants that stay under 256 VGPRs without spilling are
     // instantiated -- (NTW 5, MT 2), (NTW 4, MT 2 | 3); a spill reload is a VM load that stalls behind the LDS-DMA queue
@@ -98,7 +119,7 @@ void select_fp8(const gc_gemm_desc *d, SelQ *o, bool assume_ws)
     // (plan_rows: the k-slices -- the accumulation order of every output row -- follow the rows ONE frame contributes, as in the 2-byte path)
     const int64_t Msel = d->plan_rows > 0 ? d->plan_rows : d->M;
     const int64_t nbn = (d->N + 32 * o->ntw - 1) / (32 * o->ntw), tiles = ((Msel + 127) / 128) * nbn;
-    if (plain && !force_mt && !(d->kernel_variant & 0x40) && tiles <= 128 && nkq >= 16) {
+    if (plain && !force_mt && v.convsplit && tiles <= 128 && nkq >= 16) {
         int s = (int)std::min<int64_t>(tiles < 96 ? (256 + tiles - 1) / tiles : 256 / tiles, nkq / 8);
         if (s > 16) s = 16;
         if (s >= 2 && (assume_ws || (d->workspace && d->workspace_bytes >= sizeof(float) * (size_t)s * (size_t)d->M * (size_t)d->N))) {
@@ -114,8 +135,9 @@ extern "C" size_t gc_dn_gemm_workspace_bytes(const gc_gemm_desc *d)
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
     if (d->fp8) {
         if (d->K % 128 != 0) return 0;
+        const GemmVariant v = decode_variant(d->kernel_variant);
         SelQ q;
-        select_fp8(d, &q, true);
+        select_fp8(d, v, &q, true);
         return q.splits > 1 ? sizeof(float) * (size_t)q.splits * (size_t)d->M * (size_t)d->N : 0;
     }
     int ntw, splits, tps;
@@ -125,10 +147,10 @@ extern "C" size_t gc_dn_gemm_workspace_bytes(const gc_gemm_desc *d)
 
 namespace {
 // lean LayerNorm fold (dn_gemm_ln.hip): 1 = this problem is a producer of row partials on the lean epilogue, 2 = a LayerNorm-folded consumer,
-// 0 = neither (or kernel_variant bit 0x800 asks for the round-2 FUSE epilogue: A/B and tests)
-int ln_lean_kind(const gc_gemm_desc *d)
+// 0 = neither (or GC_GEMM_VAR_NO_LEAN_LN asks for the round-2 FUSE epilogue: A/B and tests)
+int ln_lean_kind(const gc_gemm_desc *d, const GemmVariant &v)
 {
-    if ((d->kernel_variant & 0x800) || d->fp8 || d->mode != 0 || d->K % 64 != 0 || d->out_group_stats || d->out_chan_parts || d->N < 4) return 0;
+    if (v.no_lean_ln || d->fp8 || d->mode != 0 || d->K % 64 != 0 || d->out_group_stats || d->out_chan_parts || d->N < 4) return 0;
     if (d->out_row_stats && !d->ln_row_stats)
         return (!d->geglu && d->act == 0 && !d->out_f32 && !d->out_t && d->out && (!d->rowvec || d->rows_per_batch >= 256)) ? 1 : 0;
     if (d->ln_row_stats && !d->out_row_stats) return d->softmax_keys > 0 ? 3 : 2;
@@ -136,7 +158,7 @@ int ln_lean_kind(const gc_gemm_desc *d)
 }
 // kernel choice of one problem (shared by the launcher and the row-statistics layout query)
 struct Sel { int mode, ntw, splits, tps, mt8; };     // mt8 > 0: 8-wave kernel with MT = mt8; 0: 4-wave kernel
-int select(const gc_gemm_desc *d, Sel *o, bool want_parts)
+int select(const gc_gemm_desc *d, const GemmVariant &v, Sel *o, bool want_parts)
 {
     int mode = 0;
     if (d->mode == 1) mode = (d->Cin % 64 == 0) ? 2 : 1;
@@ -149,10 +171,7 @@ int select(const gc_gemm_desc *d, Sel *o, bool want_parts)
     const int64_t nbn = (d->N + bn - 1) / bn;
     const int nk_host = (int)((d->K + BK - 1) / BK);
     // kernel selection overrides travel in the descriptor (tests / experiments); 0 = automatic.  No process-wide state.
-    const int kv = d->kernel_variant;
-    const int force_mt = kv & 7;                                   // 2 | 3 | 4: force the 8-wave kernel's m-tiles per wave
-    const int use8 = (kv & 0x10) ? 0 : ((kv & 0x20) ? 2 : 1);      // 0x10: 4-wave kernel only; 0x20: force the 8-wave kernel
-    const int convsplit = (kv & 0x40) ? 0 : ((kv & 0x80) ? 1 : 2); // 0x40: no k-slices for part-filled conv grids; 0x80: not for the small ones (8x8 maps, stride-2 convs: 4-wave split-K kernel, the round-2..4 choice)
+    const int force_mt = v.force_mt, use8 = v.use8;
     o->mode = mode; o->ntw = ntw; o->splits = splits; o->tps = tps; o->mt8 = 0;
     // 8-wave LDS-DMA kernel (one workgroup per CU, software-pipelined): workgroup tile (64 MT) x (32 NTW).
     if (use8 && d->zeros) {
@@ -164,12 +183,12 @@ int select(const gc_gemm_desc *d, Sel *o, bool want_parts)
         const int64_t tiles8 = ((Msel + 127) / 128) * nbn;
         // long-K problems with a part-filled grid (16x16-map convs, the 5120 -> 1280 FF projection): k-slices of >= 12 k-tiles
         // fill the CUs, the small grids too (M = 384: 30 tiles x 8 slices, every XCD owns one slice -- round 5: 34.4 -> 25.3 us per 8 x 8-map conv,
-        // profiles/r05_conv8x8_slices_ab.txt); variant 0x40 sends such convs back to the 4-wave split-K kernel, 0x80 only the small ones
+        // profiles/r05_conv8x8_slices_ab.txt); convsplit 0 sends such convs back to the 4-wave split-K kernel, 1 only the small ones
         const bool small = tiles8 < 96;
         if (!mt && mode == 0 && !force_mt) mt = 2;       // small linears: the 8-wave kernel's fill + epilogue is the shorter one (12.6 vs 20.9 us at M = 384)
         // part-filled single-round grids of short-K linears: 64-row tiles, two workgroups per CU (all resident when <= 512 tiles)
-        if (mode == 0 && !force_mt && ntw == 4 && d->K % 64 == 0 && !d->geglu && !d->out_t && !(kv & 0x100) &&
-            (!(d->ln_row_stats || d->out_row_stats || d->out_group_stats) || ln_lean_kind(d)) && !want_parts) {
+        if (mode == 0 && !force_mt && ntw == 4 && d->K % 64 == 0 && !d->geglu && !d->out_t && !v.no_wg2 &&
+            (!(d->ln_row_stats || d->out_row_stats || d->out_group_stats) || ln_lean_kind(d, v)) && !want_parts) {
             const int64_t t1 = ((d->M + 63) / 64) * nbn, t2 = ((d->M + 127) / 128) * nbn;
             if (mt == 2 && t2 <= 256 && t1 <= 512 && t1 > 128 && nk_host <= 24) mt = 1;      // (same accumulation order as MT 2)
         }
@@ -179,14 +198,13 @@ int select(const gc_gemm_desc *d, Sel *o, bool want_parts)
             for (int c = 0; c < 5 && !pick; ++c) if (d->w_set_rows % (64 * cand[c]) == 0) pick = cand[c];
             mt = pick ? pick : mt;
         }
-        const bool want_split = !force_mt && use8 != 2 && !d->geglu && d->w_set_rows == 0 && d->softmax_keys == 0 && d->workspace && tiles8 <= 128 && (mode == 0 ? (!small || nk_host >= 24) : (convsplit >= (small ? 2 : 1)));
+        const bool want_split = !force_mt && use8 != 2 && !d->geglu && d->w_set_rows == 0 && d->softmax_keys == 0 && d->workspace && tiles8 <= 128 && (mode == 0 ? (!small || nk_host >= 24) : (v.convsplit >= (small ? 2 : 1)));
         int s8 = 1, tps8 = nk_host;
         if (want_split) {
-            const int smt = (kv >> 24) & 7;                                  // experiments: forced m-tiles per wave of the k-sliced problems
             // 16 x 16-map convs: 192-row tiles x 3 slices (60.4 vs 63.7 us); the small grids and the linears: 128 rows; round 6: the 8 x 8-map convs of a 4-chunk launch
             // set (M = 1 536 = 24 whole images) 256-row tiles x 4 slices = four whole images per tile (profiles/r06_gemm_mt_scan_launch_sets.txt: 73.4 -> 65.8 us, 126.7 -> 111.4 us)
             const bool img8 = mode != 0 && !small && d->Ho * d->Wo <= 64 && Msel % 256 == 0;
-            const int mts = (smt >= 2 && smt <= 4) ? smt : (img8 ? 4 : ((mode != 0 && !small) ? 3 : 2));
+            const int mts = (v.slice_mt >= 2 && v.slice_mt <= 4) ? v.slice_mt : (img8 ? 4 : ((mode != 0 && !small) ? 3 : 2));
             const int64_t tiles_s = ((Msel + 64 * mts - 1) / (64 * mts)) * nbn;
             s8 = (int)std::min<int64_t>(std::max<int64_t>(256 / tiles_s, 2), nk_host / 12);         // one round: tiles x slices <= 256 workgroups
             if (s8 >= 2 && d->workspace_bytes >= sizeof(float) * (size_t)s8 * (size_t)d->M * (size_t)d->N) {
@@ -205,20 +223,21 @@ extern "C" int gc_dn_gemm_row_stat_slots(const gc_gemm_desc *d)
 {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
     if (d->fp8) { const int ntw = (d->N % 160 == 0 && d->N % 128 != 0) ? 5 : 4; return (int)((d->N + 16 * ntw - 1) / (16 * ntw)); }
+    const GemmVariant v = decode_variant(d->kernel_variant);
     Sel sel;
-    select(d, &sel, false);
+    select(d, v, &sel, false);
     return sel.splits > 1 ? (int)((d->N / 4 + 63) / 64) : (int)((d->N + 16 * sel.ntw - 1) / (16 * sel.ntw));
 }
 
 namespace {
 // channel-partial layout of one problem: rows per slab (0 = unsupported) and slab slots per batch
-void chan_parts_layout(const gc_gemm_desc *d, const Sel &sel, int64_t *rows, int *nslab, int *col_tile)
+void chan_parts_layout(const gc_gemm_desc *d, const GemmVariant &v, const Sel &sel, int64_t *rows, int *nslab, int *col_tile)
 {
     *rows = 0; *nslab = 0; *col_tile = 0;
     const int64_t rpb = d->rows_per_batch;
     if (d->fp8) {                    // k_gemm8q: only the k-sliced problems (their reduce kernel is the 2-byte path's)
         SelQ q;
-        select_fp8(d, &q, false);
+        select_fp8(d, v, &q, false);
         if (d->K % 128 != 0 || rpb < 256 || rpb % 32 != 0 || d->M % rpb != 0 || d->gn_groups < 1 || d->N % d->gn_groups != 0) return;
         const int64_t cpg = d->N / d->gn_groups;
         if (q.splits > 1) {          // the reduce-epilogue kernel produces them (64-column blocks)
@@ -260,25 +279,26 @@ extern "C" int gc_dn_gemm_chan_parts_layout(const gc_gemm_desc *d, int64_t *rows
     GC_REQUIRE(d && rows_per_slab && nslab && col_tile, "null argument");
     *rows_per_slab = 0; *nslab = 0; *col_tile = 0;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->rows_per_batch <= 0) return GC_OK;
+    const GemmVariant v = decode_variant(d->kernel_variant);
     Sel sel;
-    select(d, &sel, true);
-    chan_parts_layout(d, sel, rows_per_slab, nslab, col_tile);
+    select(d, v, &sel, true);
+    chan_parts_layout(d, v, sel, rows_per_slab, nslab, col_tile);
     return GC_OK;
 }
 
 namespace {
 // what gc_dn_gemm launches for a 2-byte problem, from the descriptor alone (shared by the launcher and gc_dn_gemm_selection)
 struct Route { Sel sel; int lnk, persist; };
-void route(const gc_gemm_desc *d, Route *r)
+void route(const gc_gemm_desc *d, const GemmVariant &v, Route *r)
 {
     Sel &sel = r->sel;
-    select(d, &sel, d->out_chan_parts != nullptr);
+    select(d, v, &sel, d->out_chan_parts != nullptr);
     if (d->out_chan_parts && sel.mt8 == 1) sel.mt8 = 2;           // (the channel-partial epilogues have no 64-row tile)
     const bool fuse = d->ln_row_stats || d->out_row_stats || d->out_group_stats;
-    r->lnk = (sel.mt8 && sel.splits == 1) ? ln_lean_kind(d) : 0;
+    r->lnk = (sel.mt8 && sel.splits == 1) ? ln_lean_kind(d, v) : 0;
     r->persist = 0;
     if (sel.mt8 == 4 && sel.ntw == 4 && sel.mode == 0 && sel.splits == 1 && d->K % 64 == 0 && d->K <= 64 * 24 && (!fuse || r->lnk == 2) && !d->out_chan_parts &&
-        !d->rowvec && !d->out_t && !d->out_f32 && d->out && d->act != 2 && !(d->kernel_variant & 0x200)) {
+        !d->rowvec && !d->out_t && !d->out_f32 && d->out && d->act != 2 && !v.no_persist) {
         // multi-round short-K linear (the GEGLU FF-up projections): persistent workgroups, next tile's fill under this tile's epilogue
         const int64_t tiles = ((d->M + 255) / 256) * ((d->N + 32 * sel.ntw - 1) / (32 * sel.ntw));
         if (tiles > 256) r->persist = 256;
@@ -290,25 +310,27 @@ extern "C" int gc_dn_gemm_selection(const gc_gemm_desc *d, gc_gemm_selection *ou
 {
     GC_REQUIRE(d && out, "null argument");
     GC_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "empty problem");
+    const GemmVariant v = decode_variant(d->kernel_variant);
+    if (const int rc = refuse_variant_bits(__func__, v.undefined)) return rc;
     *out = gc_gemm_selection{};
     int64_t rows = 0; int ns = 0, ct = 0;
     if (d->fp8) {
         GC_REQUIRE(d->K % 128 == 0, "fp8: K % 128 == 0");
         SelQ q;
-        select_fp8(d, &q, false);
+        select_fp8(d, v, &q, false);
         out->kernel = GC_GEMM_SEL_FP8; out->m_tiles = q.mt; out->splits = q.splits; out->ntw = q.ntw;
         if (d->out_chan_parts) {
-            chan_parts_layout(d, Sel{}, &rows, &ns, &ct);
+            chan_parts_layout(d, v, Sel{}, &rows, &ns, &ct);
             out->parts = rows > 0 ? (q.splits > 1 ? 1 : 2) : -1;
         }
         return GC_OK;
     }
     Route r;
-    route(d, &r);
+    route(d, v, &r);
     out->kernel = !r.sel.mt8 ? GC_GEMM_SEL_K4 : r.sel.splits > 1 ? GC_GEMM_SEL_K8_SLICED : GC_GEMM_SEL_K8;
     out->m_tiles = r.sel.mt8; out->splits = r.sel.splits; out->ntw = r.sel.ntw; out->ln_kind = r.lnk; out->persist = r.persist;
     if (d->out_chan_parts) {
-        chan_parts_layout(d, r.sel, &rows, &ns, &ct);
+        chan_parts_layout(d, v, r.sel, &rows, &ns, &ct);
         out->parts = rows > 0 ? (r.sel.splits > 1 ? 1 : 2) : -1;
     }
     return GC_OK;
@@ -321,6 +343,8 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     GC_REQUIRE(d->K % 8 == 0, "K must be a multiple of 8 (pad channels on the host)");
     GC_REQUIRE(d->N % 4 == 0, "N must be a multiple of 4 (pad output channels on the host)");
     GC_REQUIRE(d->dtype == DT_BF16 || d->dtype == DT_F16, "dtype must be 0 (bf16) or 1 (f16)");
+    const GemmVariant v = decode_variant(d->kernel_variant);
+    if (const int rc = refuse_variant_bits(__func__, v.undefined)) return rc;
     GemmArgs g;
     g.pw = 0;
     g.M = d->M; g.N = d->N; g.K = d->K; g.A = d->A; g.lda = d->lda;
@@ -339,8 +363,8 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     GC_REQUIRE(!d->out_fp8 || (d->fp8 && d->mode == 0 && d->out && !d->out_f32 && !d->out_t && !d->out_chan_parts && !d->ln_row_stats && !d->out_row_stats &&
                                !d->out_group_stats && d->ldc % 4 == 0),
                "out_fp8: an fp8 linear with a plain output (no fp32 / transposed output, no statistics, no LayerNorm fold), ldc % 4 == 0");
-    g.dbg = (d->kernel_variant >> 8) & 0x0f;
-    g.conv_korder = (d->kernel_variant & 0x1000) ? 0 : 1;
+    g.dbg = v.epi_abl;
+    g.conv_korder = v.tap_outer ? 0 : 1;
     g.w_set_rows = d->w_set_rows; g.w_set_stride = d->w_set_stride; g.sm_keys = d->softmax_keys;
     GC_REQUIRE(d->w_set_rows >= 0 && d->softmax_keys >= 0 && d->softmax_keys <= 80, "bad weight-set / softmax arguments");
     GC_REQUIRE(!d->softmax_keys || (d->ln_row_stats && d->N % 80 == 0 && d->out && !d->out_f32 && !d->out_t && !d->geglu && !d->residual && d->act == 0),
@@ -362,15 +386,14 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     GC_REQUIRE((d->mode == 1 ? (int64_t)d->B * d->Hi * d->Wi * d->Cin : d->M * d->lda) < ((int64_t)1 << 31) && (int64_t)d->N * d->K < ((int64_t)1 << 31),
                "operand too large for 32-bit element offsets: split the batch");
     if (d->geglu) GC_REQUIRE(d->N % 32 == 0 && !d->out_t, "geglu needs N % 32 == 0");
-    const int force_mt = d->kernel_variant & 7;
-    GC_REQUIRE(force_mt >= 0 && force_mt <= 4, "kernel_variant: MT must be 0 .. 4");
+    GC_REQUIRE(v.force_mt <= 4, "kernel_variant: MT must be 0 .. 4");
     Route rt;
-    route(d, &rt);
+    route(d, v, &rt);
     const Sel &sel = rt.sel;
     g.chan_parts = d->out_chan_parts; g.cp_nslab = 0; g.cp_rows = 0;
     if (d->out_chan_parts) {
         int64_t rows; int ns, ct;
-        chan_parts_layout(d, sel, &rows, &ns, &ct);
+        chan_parts_layout(d, v, sel, &rows, &ns, &ct);
         GC_REQUIRE(rows > 0, "out_chan_parts: this problem cannot produce channel partials (see gc_dn_gemm_chan_parts_layout)");
         g.cp_nslab = ns; g.cp_rows = (int)rows;
     }
@@ -388,13 +411,13 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
         GC_REQUIRE(d->mode == 1 || d->lda % 16 == 0, "fp8 linear: lda % 16 == 0");
         GC_REQUIRE((int64_t)d->N * d->K < ((int64_t)1 << 31) && (d->mode == 1 ? (int64_t)d->B * d->Hi * d->Wi * d->Cin : d->M * d->lda) < ((int64_t)1 << 31), "fp8: 32-bit offsets");
         SelQ q;
-        select_fp8(d, &q, false);
+        select_fp8(d, v, &q, false);
         const int ntw = q.ntw, mt = q.mt;
         g.splits = q.splits; g.tiles_per_split = q.tps; g.ws = q.splits > 1 ? (float *)d->workspace : nullptr;
         GC_REQUIRE(!d->out_chan_parts || q.splits > 1 || (d->mode == 1 && !fuse_of(g)), "fp8: channel partials come from k-sliced problems and fast convs");
         const int64_t nbn_q = (d->N + 32 * ntw - 1) / (32 * ntw), nbm_q = (d->M + 64 * mt - 1) / (64 * mt);
         const dim3 gq((unsigned)(nbm_q * nbn_q), (unsigned)q.splits);
-        g.pw = pw_of(d, nbm_q, nbn_q, nbm_q * nbn_q * q.splits, 32, 64 * mt, 32 * ntw);
+        g.pw = pw_of(d, v, nbm_q, nbn_q, nbm_q * nbn_q * q.splits, 32, 64 * mt, 32 * ntw);
         dn_gemm_launch_fp8(g, d->dtype, d->mode == 1 ? 2 : 3, ntw, mt, gq, s);
         if (q.splits > 1) { if (g.chan_parts) dn_gemm_launch_splitk_epilogue_cs(g, d->dtype, s); else dn_gemm_launch_splitk_epilogue(g, d->dtype, s); }
         return gc::check_launch("gc_dn_gemm(fp8)");
@@ -411,16 +434,16 @@ extern "C" int gc_dn_gemm(const gc_gemm_desc *d, void *stream)
     if (sel.mt8) {
         const int64_t nbm8 = (d->M + 64 * sel.mt8 - 1) / (64 * sel.mt8);
         const dim3 grid8((unsigned)(nbm8 * nbn), (unsigned)sel.splits);
-        g.pw = pw_of(d, nbm8, nbn, g.persist ? 8 * 32 : nbm8 * nbn * sel.splits, sel.mt8 == 1 ? 64 : 32, 64 * sel.mt8, bn);
+        g.pw = pw_of(d, v, nbm8, nbn, g.persist ? 8 * 32 : nbm8 * nbn * sel.splits, sel.mt8 == 1 ? 64 : 32, 64 * sel.mt8, bn);
         if (lnk) dn_gemm_launch_ln(g, d->dtype, lnk, lean_of(g, sel.mode) && g.persist == 0, sel.ntw, sel.mt8, grid8, s);
         else if (fuse_of(g)) dn_gemm_launch_fuse(g, d->dtype, sel.mode, sel.ntw, sel.mt8 < 2 ? 2 : sel.mt8, grid8, s);
         else if (g.chan_parts && sel.splits == 1) dn_gemm_launch_cs(g, d->dtype, sel.mode, sel.ntw, sel.mt8, grid8, s);
-        else if (lean_of(g, sel.mode) && g.persist == 0 && !(d->kernel_variant & 0x400)) dn_gemm_launch_lean(g, d->dtype, sel.mode, sel.ntw, sel.mt8, grid8, s);
+        else if (lean_of(g, sel.mode) && g.persist == 0 && !v.full_epilogue) dn_gemm_launch_lean(g, d->dtype, sel.mode, sel.ntw, sel.mt8, grid8, s);
         else dn_gemm_launch_plain(g, d->dtype, sel.mode, sel.ntw, sel.mt8, grid8, s);
     } else {
         const int64_t nbm = (d->M + BM - 1) / BM;
         const dim3 grid((unsigned)(nbm * nbn), (unsigned)sel.splits);
-        g.pw = pw_of(d, nbm, nbn, nbm * nbn * sel.splits, 64, BM, bn);
+        g.pw = pw_of(d, v, nbm, nbn, nbm * nbn * sel.splits, 64, BM, bn);
         if (fuse_of(g)) dn_gemm_launch_fuse(g, d->dtype, sel.mode, sel.ntw, 0, grid, s); else dn_gemm_launch_plain(g, d->dtype, sel.mode, sel.ntw, 0, grid, s);
     }
     if (sel.splits > 1) { if (g.chan_parts) dn_gemm_launch_splitk_epilogue_cs(g, d->dtype, s); else dn_gemm_launch_splitk_epilogue(g, d->dtype, s); }

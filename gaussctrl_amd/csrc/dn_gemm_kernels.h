@@ -54,7 +54,7 @@ struct GemmArgs {
     int a_scale;                        // fp8 path: E8M0 scale byte of the whole activation tensor
     int out_fp8; float out_qscale;      // fp8 path, plain epilogue: store e4m3 BYTES of v * out_qscale (= 2^(127 - out_fp8)) at out[m * ldc + n]: the
                                         // e4m3 activation operand of the next fp8 GEMM (GEGLU hidden -> FF down projection)
-    int dbg;                            // experiment switches (kernel_variant bits 8..): 1 no global group atomics, 2 no LDS atomics, 4 no DPP
+    int dbg;                            // timing ablations (GC_GEMM_VAR_EPI_ABL_*): 1 no global group atomics, 2 no LDS atomics, 4 no DPP
     // partial GroupNorm-group sums of the stored output, the statistics pass of the GroupNorm that follows (k_gemm8 CS = true,
     // k_splitk_epilogue_cs): chan_parts[b][slab][group][half] = (sum, sum^2) over the rows of batch b inside the slab-th row tile (cp_rows
     // rows each, tiles counted over all M rows) that overlaps batch b and over the group's channels inside this workgroup's column tile:
@@ -68,7 +68,7 @@ struct GemmArgs {
     int64_t w_set_rows, w_set_stride;
     int pw;                             // column-panel width of the tile order (tile_coords below); 0 = m-major
     int sm_keys;
-    int conv_korder;                    // k_gemm8 fast convs: 1 = tap-inner k-tile sequence (default), 0 = tap-outer (kernel_variant 0x1000)
+    int conv_korder;                    // k_gemm8 fast convs: 1 = tap-inner k-tile sequence (default), 0 = tap-outer (GC_GEMM_VAR_TAP_OUTER)
 };
 
 // (blockIdx.x, blockIdx.y) of a (tiles, k-slices) launch grid -> (m block, n block, k-slice) of this workgroup.

@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import os
+import sys
+import types
 
 import torch
 
@@ -51,6 +53,19 @@ class GemmSelection(C.Structure):
 
 GEMM_KERNELS = {1: "k4", 2: "k8", 3: "k8_sliced", 4: "fp8"}                                          # gc_gemm_selection.kernel
 ATTN_KERNELS = {1: "attn5", 2: "attn4", 3: "attn3", 4: "wide+combine", 5: "attn+combine", 6: "attn"}   # gc_dn_attention_selection
+
+# gc_gemm_desc.kernel_variant / gc_attn_desc.kernel_variant: the GC_GEMM_VAR_* / GC_ATTN_VAR_* enumerators of include/gaussctrl_hip.h, where each is
+# described (tests/test_abi.py holds the two lists equal).  *_MASK fields sit at *_SHIFT; every other constant is one bit.
+GC_GEMM_VAR_MT_MASK, GC_GEMM_VAR_MT_SHIFT = 0x7, 0
+GC_GEMM_VAR_K4_ONLY, GC_GEMM_VAR_FORCE_K8, GC_GEMM_VAR_NO_CONV_SLICES, GC_GEMM_VAR_NO_SMALL_CONV_SLICES = 0x10, 0x20, 0x40, 0x80
+GC_GEMM_VAR_NO_WG2, GC_GEMM_VAR_NO_PERSIST, GC_GEMM_VAR_FULL_EPILOGUE, GC_GEMM_VAR_NO_LEAN_LN, GC_GEMM_VAR_TAP_OUTER = 0x100, 0x200, 0x400, 0x800, 0x1000
+GC_GEMM_VAR_PW_MASK, GC_GEMM_VAR_PW_SHIFT = 0xff0000, 16
+GC_GEMM_VAR_SLICE_MT_MASK, GC_GEMM_VAR_SLICE_MT_SHIFT = 0x7000000, 24
+GC_GEMM_VAR_EPI_ABL_MASK, GC_GEMM_VAR_EPI_ABL_SHIFT = 0x70000000, 28
+GC_ATTN_VAR_ONLINE_ONLY, GC_ATTN_VAR_D40_K3, GC_ATTN_VAR_K4_8WAVE, GC_ATTN_VAR_K4_Q64, GC_ATTN_VAR_K4 = 1, 2, 4, 8, 16
+GC_ATTN_VAR_RING4, GC_ATTN_VAR_RING8, GC_ATTN_VAR_D160_Q64 = 32, 64, 128
+GC_ATTN_VAR_ABL_MASK, GC_ATTN_VAR_ABL_SHIFT = 0xff00, 8
+GC_ATTN_VAR_CSHIFT_MASK, GC_ATTN_VAR_CSHIFT_SHIFT = 0x1f0000, 16
 
 
 def gemm_selection(d):
@@ -107,46 +122,57 @@ OPTIONS = KernelOptions()
 
 def configure(options: KernelOptions | None = None, **kw) -> KernelOptions:
     """Replace (options=) or update (**kw) the process-wide kernel options; returns the active object."""
-    global OPTIONS, BATCH_INVARIANT
+    global OPTIONS
     if options is not None:
         OPTIONS = options
     if kw:
         OPTIONS = dataclasses.replace(OPTIONS, **kw)
-    BATCH_INVARIANT = OPTIONS.batch_invariant
-    KERNEL_VARIANT["gemm"], KERNEL_VARIANT["attn"] = OPTIONS.gemm_variant, OPTIONS.attn_variant
     return OPTIONS
 
 
 def options_from_env(env=None) -> KernelOptions:
     """The experiment switches of bench.py / scripts / the spawned ranks of the tests, decoded from GC_* variables (NOT called on
-    import and never by the plugin path):  GC_GEMM_MT / GC_GEMM8 / GC_GEMM_CONVSPLIT / GC_GEMM_DBG / GC_GEMM_PW -> gemm_variant;  GC_ATTN_SAFE /
+    import and never by the plugin path):  GC_GEMM_MT / GC_GEMM8 / GC_GEMM_CONVSPLIT / GC_GEMM_DBG / GC_GEMM_EPI_ABL / GC_GEMM_SPLIT_MT / GC_GEMM_PW -> gemm_variant;  GC_ATTN_SAFE /
     GC_ATTN_16 / GC_ATTN_V -> attn_variant;  GC_BATCH_INVARIANT, GC_FUSED_HEAD, GC_FUSED_TAIL, GC_DN_STREAMS, GC_GN_PARTS, GC_ABLATE=a,b,c."""
     e = os.environ if env is None else env
     on = lambda k, d: e.get(k, d) not in ("", "0")
-    g = int(e.get("GC_GEMM_MT", "0")) & 7
-    use8 = e.get("GC_GEMM8")
-    if use8 == "0":
-        g |= 0x10
-    elif use8 == "2":
-        g |= 0x20
-    cs = e.get("GC_GEMM_CONVSPLIT")
-    if cs == "0":
-        g |= 0x40
-    elif cs == "1":            # (2 = default: also the small grids -- 8 x 8 maps, stride-2 convs -- on the k-sliced 8-wave kernel)
-        g |= 0x80
-    g |= (int(e.get("GC_GEMM_DBG", "0")) & 0xff) << 8
-    g |= (int(e.get("GC_GEMM_SPLIT_MT", "0")) & 7) << 24                  # m-tiles per wave of the k-sliced 8-wave problems (default 2)
-    if e.get("GC_GEMM_PW", "") != "":            # forced column-panel width of the GEMM tile order (0 = whole rows, the round-1..4 order)
-        g |= ((int(e["GC_GEMM_PW"]) + 1) & 0xff) << 16
-    a = (1 if on("GC_ATTN_SAFE", "0") else 0) | (2 if on("GC_ATTN_16", "0") else 0) | (int(e.get("GC_ATTN_V", "0")) << 2)
+    field = lambda k, mask, shift, bias=0: ((int(e[k]) + bias) << shift) & mask if e.get(k, "") != "" else 0
+    g = field("GC_GEMM_MT", GC_GEMM_VAR_MT_MASK, GC_GEMM_VAR_MT_SHIFT)
+    g |= {"0": GC_GEMM_VAR_K4_ONLY, "2": GC_GEMM_VAR_FORCE_K8}.get(e.get("GC_GEMM8"), 0)
+    # (GC_GEMM_CONVSPLIT=2 = default: also the small grids -- 8 x 8 maps, stride-2 convs -- on the k-sliced 8-wave kernel)
+    g |= {"0": GC_GEMM_VAR_NO_CONV_SLICES, "1": GC_GEMM_VAR_NO_SMALL_CONV_SLICES}.get(e.get("GC_GEMM_CONVSPLIT"), 0)
+    dbg = int(e.get("GC_GEMM_DBG", "0"))         # 1 | 2 | 4 | 8 | 16: the router / epilogue / k-order A/B switches, in this order
+    dbg_bits = (GC_GEMM_VAR_NO_WG2, GC_GEMM_VAR_NO_PERSIST, GC_GEMM_VAR_FULL_EPILOGUE, GC_GEMM_VAR_NO_LEAN_LN, GC_GEMM_VAR_TAP_OUTER)
+    if dbg < 0 or dbg >> len(dbg_bits):
+        raise ValueError(f"GC_GEMM_DBG={dbg}: an OR of 1 (no two-workgroup linears), 2 (no persistent GEMM), 4 (full epilogue), 8 (no lean LayerNorm fold), 16 (tap-outer convs)")
+    g |= sum(b for i, b in enumerate(dbg_bits) if dbg >> i & 1)
+    g |= field("GC_GEMM_EPI_ABL", GC_GEMM_VAR_EPI_ABL_MASK, GC_GEMM_VAR_EPI_ABL_SHIFT)         # timing ablations of the fused-statistics epilogue
+    g |= field("GC_GEMM_SPLIT_MT", GC_GEMM_VAR_SLICE_MT_MASK, GC_GEMM_VAR_SLICE_MT_SHIFT)      # m-tiles per wave of the k-sliced 8-wave problems (default 2)
+    g |= field("GC_GEMM_PW", GC_GEMM_VAR_PW_MASK, GC_GEMM_VAR_PW_SHIFT, 1)   # forced column-panel width of the GEMM tile order (0 = whole rows, the round-1..4 order)
+    a = (GC_ATTN_VAR_ONLINE_ONLY if on("GC_ATTN_SAFE", "0") else 0) | (GC_ATTN_VAR_D40_K3 if on("GC_ATTN_16", "0") else 0)
+    a |= int(e.get("GC_ATTN_V", "0")) * GC_ATTN_VAR_K4_8WAVE     # 1 | 2 | 4 | 8 | 16 | 32: GC_ATTN_VAR_K4_8WAVE .. GC_ATTN_VAR_D160_Q64
     return KernelOptions(gemm_variant=g, attn_variant=a, batch_invariant=on("GC_BATCH_INVARIANT", "0"),
                          fused_head=on("GC_FUSED_HEAD", "1"), fused_tail=on("GC_FUSED_TAIL", "1"), two_streams=on("GC_DN_STREAMS", "1"),
                          gn_parts=on("GC_GN_PARTS", "1"), cfg_share=on("GC_CFG_SHARE", "1"), text_fold=on("GC_TEXT_FOLD", "1"), ffout_merge=on("GC_FFOUT_MERGE", "1"), q_only=on("GC_Q_ONLY", "1"), tail_in_rows=on("GC_TAIL_INROWS", "1"),
                          ablate=frozenset(x for x in e.get("GC_ABLATE", "").split(",") if x))
 
 
-KERNEL_VARIANT = {"gemm": 0, "attn": 0}     # mirrors of OPTIONS kept as module attributes (read on every launch; tests patch them)
-BATCH_INVARIANT = False
+class _CompatNames(types.ModuleType):
+    """Two older module attributes, kept as names over OPTIONS (which stays the only state)."""
+    @property
+    def KERNEL_VARIANT(self):          # READ-ONLY view (bench.py reads it): a fresh dict per read, writing to it changes nothing -- use configure()
+        return {"gemm": OPTIONS.gemm_variant, "attn": OPTIONS.attn_variant}
+
+    @property
+    def BATCH_INVARIANT(self):
+        return OPTIONS.batch_invariant
+
+    @BATCH_INVARIANT.setter
+    def BATCH_INVARIANT(self, on):     # (callers that still assign the old global: the assignment lands in OPTIONS)
+        configure(batch_invariant=bool(on))
+
+
+sys.modules[__name__].__class__ = _CompatNames
 
 
 DT = {torch.bfloat16: 0, torch.float16: 1}
@@ -231,7 +257,7 @@ def _run_gemm(d, dev, what, row_stats=None, want_parts=False, gn_groups=32):
     if z is None:
         z = _zero_page[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
     d.zeros = z.data_ptr()
-    d.kernel_variant = KERNEL_VARIANT["gemm"]
+    d.kernel_variant = OPTIONS.gemm_variant
     wsb = lib.gc_dn_gemm_workspace_bytes(C.byref(d))
     ws = None
     if wsb:
@@ -295,7 +321,7 @@ def linear(x, w, bias=None, residual=None, act=0, geglu=False, out_f32=False, sc
     if rowvec is not None:
         d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0) if ld_rowvec is None else ld_rowvec
     d.rows_per_batch = rows_per_batch
-    if BATCH_INVARIANT and x.dim() >= 3:
+    if OPTIONS.batch_invariant and x.dim() >= 3:
         d.plan_rows = M // x.shape[0]                 # the rows one frame contributes
     No = N // 2 if geglu else (N if out_cols is None else out_cols)
     if OPTIONS.ablate and out is None and row_stats is None and M >= 256:
@@ -313,7 +339,7 @@ def linear(x, w, bias=None, residual=None, act=0, geglu=False, out_f32=False, sc
     if out_t is not None:
         d.out_t = out_t.data_ptr(); d.ldt = ldt; d.t_batch_stride = t_batch_stride; d.t_col0 = t_col0
     _stats_args(d, ln, group_stats)
-    parts = _run_gemm(d, x.device, "gc_dn_gemm", row_stats, want_parts=chan_parts and not BATCH_INVARIANT, gn_groups=gn_groups)
+    parts = _run_gemm(d, x.device, "gc_dn_gemm", row_stats, want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -341,14 +367,14 @@ def conv3x3(x, w, bias=None, stride=1, upsample=False, rowvec=None, ld_rowvec=No
     if rowvec is not None:
         d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0) if ld_rowvec is None else ld_rowvec
     d.rows_per_batch = Ho * Wo
-    if BATCH_INVARIANT:
+    if OPTIONS.batch_invariant:
         d.plan_rows = Ho * Wo
     if residual is not None:
         d.residual = residual.data_ptr(); d.ldr = N
     d.out_scale = scale; d.act = act
     d.out = out.data_ptr(); d.ldc = N; d.out_f32 = int(out_f32)
     _stats_args(d, None, group_stats)
-    parts = _run_gemm(d, x.device, "gc_dn_gemm(conv3x3)", want_parts=chan_parts and not BATCH_INVARIANT, gn_groups=gn_groups)
+    parts = _run_gemm(d, x.device, "gc_dn_gemm(conv3x3)", want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -378,7 +404,7 @@ def groupnorm(x, gamma, beta, groups, eps, silu, parts=None):
         ws = _gn_ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
     y = torch.empty_like(x)
     L.check(L.lib().gc_dn_groupnorm(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta),
-                                    C.c_float(eps), int(silu) | (0x100 if BATCH_INVARIANT else 0), _p(ws), _stream()), "gc_dn_groupnorm")
+                                    C.c_float(eps), int(silu) | (0x100 if OPTIONS.batch_invariant else 0), _p(ws), _stream()), "gc_dn_groupnorm")
     return y
 
 
@@ -462,7 +488,7 @@ def conv3x3_fp8(x8, w8, w_scale, out_dtype, bias=None, stride=1, rowvec=None, ld
     if rowvec is not None:
         d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0) if ld_rowvec is None else ld_rowvec
     d.rows_per_batch = Ho * Wo
-    if BATCH_INVARIANT:
+    if OPTIONS.batch_invariant:
         d.plan_rows = Ho * Wo
     if residual is not None:
         d.residual = residual.data_ptr(); d.ldr = N
@@ -471,7 +497,7 @@ def conv3x3_fp8(x8, w8, w_scale, out_dtype, bias=None, stride=1, rowvec=None, ld
     d.fp8 = 1; d.w_scale = w_scale.data_ptr(); d.a_scale = int(a_scale)
     _stats_args(d, None, group_stats)
     # chan_parts=True: returns (out, ChanParts | None) -- the k-sliced problems (16 x 16 maps) leave the GroupNorm partials of their output
-    parts = _run_gemm(d, x8.device, "gc_dn_gemm(conv3x3 fp8)", want_parts=chan_parts and not BATCH_INVARIANT, gn_groups=gn_groups)
+    parts = _run_gemm(d, x8.device, "gc_dn_gemm(conv3x3 fp8)", want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -491,7 +517,7 @@ def linear_fp8(x8, w8, w_scale, out_dtype, bias=None, residual=None, act=0, scal
     d.A = x8.data_ptr(); d.lda = x8.stride(-2) if x8.dim() > 1 else K; d.W = w8.data_ptr()
     d.bias = None if bias is None else bias.data_ptr()
     d.rows_per_batch = rows_per_batch
-    if BATCH_INVARIANT and x8.dim() >= 3:
+    if OPTIONS.batch_invariant and x8.dim() >= 3:
         d.plan_rows = M // x8.shape[0]                # the rows one frame contributes
     if residual is not None:
         d.residual = residual.data_ptr(); d.ldr = residual.stride(-2)
@@ -537,7 +563,7 @@ def concat_add(a, b, c=None, group_stats=None, chan_parts=False, gn_groups=32):
     out = torch.empty(a.shape[:-1] + (C1 + C2,), dtype=a.dtype, device=a.device)
     if chan_parts:
         rpb = M // a.shape[0]
-        if rpb < 256 or BATCH_INVARIANT or "gn" in OPTIONS.ablate:
+        if rpb < 256 or OPTIONS.batch_invariant or "gn" in OPTIONS.ablate:
             return concat_add(a, b, c), None
         rows, ns, ct = C.c_int64(0), C.c_int(0), C.c_int(0)
         L.check(L.lib().gc_dn_concat_parts_layout(C.c_int64(rpb), C1 + C2, gn_groups, C.byref(rows), C.byref(ns), C.byref(ct)), "gc_dn_concat_parts_layout")
@@ -597,7 +623,7 @@ def attention(q, k, vt, heads, sets, frames_per_half, Lk=None, kref=None, vtref=
         d.set_kind[i] = kind; d.set_weight[i] = w
     d.scale = (D ** -0.5) if scale is None else scale
     d.q_prescaled = int(q_prescaled)     # Q carries scale*log2(e) already (weights.prepare(..., fold_attn_scale_heads=...))
-    d.kernel_variant = KERNEL_VARIANT["attn"]
+    d.kernel_variant = OPTIONS.attn_variant
     d.Q = q.data_ptr(); d.ldq = q.stride(1); d.q_batch_stride = q.stride(0)
     d.K = k.data_ptr(); d.ldk = k.stride(1); d.k_batch_stride = k.stride(0)
     d.Vt = vt.data_ptr(); d.ldvt = vt.stride(1); d.vt_batch_stride = vt.stride(0)
@@ -606,7 +632,7 @@ def attention(q, k, vt, heads, sets, frames_per_half, Lk=None, kref=None, vtref=
         d.Kref = kref.data_ptr(); d.kref_batch_stride = kref.stride(0)
         d.Vtref = vtref.data_ptr(); d.vtref_batch_stride = vtref.stride(0); d.ref_frames_per_half = ref_fph
     wsb = L.lib().gc_dn_attention_workspace_bytes(C.byref(d))      # head size 160 with several K/V sets: one workgroup per (query block, set)
-    if wsb and not BATCH_INVARIANT:      # the library takes the set-split form only while the grid is small (nwg < 512: a function of B) and its fp32
+    if wsb and not OPTIONS.batch_invariant:      # the library takes the set-split form only while the grid is small (nwg < 512: a function of B) and its fp32
                                          # combine rounds differently from the in-register one: batch-invariant mode never offers the workspace
         ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
         d.workspace = ws.data_ptr(); d.workspace_bytes = wsb

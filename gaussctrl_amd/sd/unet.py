@@ -425,7 +425,7 @@ class SDNet:
             fb = torch.empty(B, H * W_, 5 * Cc, dtype=h.dtype, device=h.device)
         h_out = None if fb is None else fb[..., 4 * Cc:]
         tf = None
-        if fold and self.text_fold and not ops.BATCH_INVARIANT:
+        if fold and self.text_fold and not ops.OPTIONS.batch_invariant:
             Mh = (B // 2) * H * W_
             if B % 2 == 0 and any(Mh % (64 * mt) == 0 for mt in (2, 3, 4)):
                 tf = self._text_fold(t, ctx, actx)

@@ -327,6 +327,22 @@ int gc_l1_ssim_fwd_bwd_views(int B, const float *pred, const float *target, int 
 /* Activations are channels-last ("tokens x channels") 2-byte tensors; dtype 0 = bf16, 1 = f16;    */
 /* accumulation and statistics are fp32.                                                          */
 
+/* gc_gemm_desc.kernel_variant: kernel-selection overrides and experiment switches (tests, A/B measurements; 0 = the product).  The
+ * *_MASK fields sit at *_SHIFT; every other constant is one bit.  Bits outside these constants are refused. */
+enum { GC_GEMM_VAR_MT_MASK = 0x7, GC_GEMM_VAR_MT_SHIFT = 0,            /* force the 8-wave kernel's m-tiles per wave (2, 3, 4); fp8 (k_gemm8q) honours it too, and then takes no k-slices */
+       GC_GEMM_VAR_K4_ONLY = 0x10,                                     /* 4-wave kernel only */
+       GC_GEMM_VAR_FORCE_K8 = 0x20,                                    /* force the 8-wave kernel (and no k-slices) */
+       GC_GEMM_VAR_NO_CONV_SLICES = 0x40,                              /* no k-slices for part-filled conv grids: the 4-wave split-K kernel (fp8: unsliced) */
+       GC_GEMM_VAR_NO_SMALL_CONV_SLICES = 0x80,                        /* the small conv grids (8x8 maps, stride-2 convs), k-sliced by default, go back to the 4-wave split-K kernel */
+       GC_GEMM_VAR_NO_WG2 = 0x100,                                     /* no 64-row tiles / two workgroups per CU for part-filled short-K linears */
+       GC_GEMM_VAR_NO_PERSIST = 0x200,                                 /* no persistent workgroups for the multi-round short-K linears (GEGLU FF-up) */
+       GC_GEMM_VAR_FULL_EPILOGUE = 0x400,                              /* the full epilogue where the lean one would do */
+       GC_GEMM_VAR_NO_LEAN_LN = 0x800,                                 /* LayerNorm fold / row statistics on the fused (FUSE) epilogue, not the lean one */
+       GC_GEMM_VAR_TAP_OUTER = 0x1000,                                 /* fast 3x3 convs walk K tap-outer, not tap-inner (same products, other summation order) */
+       GC_GEMM_VAR_PW_MASK = 0xff0000, GC_GEMM_VAR_PW_SHIFT = 16,      /* n + 1 forces column-panel width n of the tile order (n = 0: whole rows) */
+       GC_GEMM_VAR_SLICE_MT_MASK = 0x7000000, GC_GEMM_VAR_SLICE_MT_SHIFT = 24,   /* m-tiles per wave (2, 3, 4) of the k-sliced 8-wave problems */
+       GC_GEMM_VAR_EPI_ABL_MASK = 0x70000000, GC_GEMM_VAR_EPI_ABL_SHIFT = 28 };  /* TIMING ablations of the fused-statistics epilogue (results wrong by construction): */
+                                                                       /* 1 no global group atomics, 2 no LDS atomics, 4 no DPP row sum */
 /* GEMM / implicit-GEMM 3x3 convolution with fused epilogue (torch.nn.Linear / Conv2d of the UNet,  */
 /* ControlNet and VAE).  out[m][n] = (act(acc + bias[n] + rowvec[m / rows_per_batch][n])) * out_scale */
 /*                                   + residual[m][n];  acc = sum_k Act[m][k] * W[n][k].            */
@@ -376,10 +392,7 @@ typedef struct gc_gemm_desc {
     int fp8;
     const void *w_scale;       /* [N] E8M0 bytes */
     int a_scale;               /* E8M0 byte of the activation tensor */
-    int kernel_variant;        /* 0 = automatic.  Overrides for tests / experiments: bits 0-2 force the 8-wave kernel's m-tiles per wave (2,3,4); */
-                               /* 0x10 4-wave kernel only; 0x20 force the 8-wave kernel; 0x40 no k-slices for part-filled conv grids; 0x80 slice 8x8-map convs too. */
-                               /* fp8 problems (k_gemm8q) honour bits 0-2 (a forced tile height also disables their k-slices) and 0x40 */
-                               /* 0x1000: fast 3x3 convs walk K tap-outer (rounds 1-5) instead of tap-inner (round 6 default: same products, other summation order) */
+    int kernel_variant;        /* 0 = automatic (the product).  A/B and test overrides: an OR of GC_GEMM_VAR_* above; undefined bits are refused (GC_EINVAL) */
     float *out_chan_parts;     /* NULL or [M / rows_per_batch][nslab][gn_groups][2][2]: partial (sum, sum of squares) of the stored output per row slab,  */
                                /* GroupNorm group (N / gn_groups channels) and half (1: rest of a group straddling two column tiles); layout:          */
                                /* gc_dn_gemm_chan_parts_layout.  PLAIN stores -- no atomics, no zero-init -> gc_dn_groupnorm_apply_parts /              */
@@ -426,6 +439,16 @@ typedef struct gc_gemm_selection {
 int gc_dn_gemm_selection(const gc_gemm_desc *desc, gc_gemm_selection *out);
 int gc_dn_gemm(const gc_gemm_desc *desc, void *stream);
 
+/* gc_attn_desc.kernel_variant: A/B and test overrides (0 = the product); layout rules as for GC_GEMM_VAR_*. */
+enum { GC_ATTN_VAR_ONLINE_ONLY = 1,                                    /* the online-softmax kernel k_attn for every shape */
+       GC_ATTN_VAR_D40_K3 = 2,                                         /* head_dim 40 on the 16x16x32 kernel (k_attn3) */
+       GC_ATTN_VAR_K4_8WAVE = 4,                                       /* head_dim 40 on k_attn4 with 8 waves, one workgroup per CU */
+       GC_ATTN_VAR_K4_Q64 = 8,                                         /* head_dim 40 on k_attn4 with 64 queries per wave (25 % slower: DESIGN.md 7.1) */
+       GC_ATTN_VAR_K4 = 16,                                            /* head_dim 40 on k_attn4 instead of k_attn5 */
+       GC_ATTN_VAR_RING4 = 32, GC_ATTN_VAR_RING8 = 64,                 /* k_attn5 asked for an LDS ring of 4 / 8 tiles instead of 6 */
+       GC_ATTN_VAR_D160_Q64 = 128,                                     /* head_dim 160 on the 64-query form (k_attn), not k_attn_wide */
+       GC_ATTN_VAR_ABL_MASK = 0xff00, GC_ATTN_VAR_ABL_SHIFT = 8,       /* TIMING ablations of k_attn5's instrumented instantiation (results wrong by construction; csrc/dn_attn5.hip) */
+       GC_ATTN_VAR_CSHIFT_MASK = 0x1f0000, GC_ATTN_VAR_CSHIFT_SHIFT = 16 };      /* k_attn5: P = exp2(s - m0 - cshift) (experiment; csrc/dn_attn5.hip) */
 /* Fused multi-K/V-set attention = CrossViewAttnProcessor core, gaussctrl/utils.py:86-117 (+ compute_attn :25-37). */
 /* O[b] = sum_s set_weight[s] * softmax(scale * Q[b] K[kv(b,s)]^T) V[kv(b,s)],                                   */
 /* kv(b,s) = b if set_kind[s] == -1; b / frames_per_half if -2 (text K/V shared by a CFG half);                  */
@@ -451,11 +474,8 @@ typedef struct gc_attn_desc {
     int q_prescaled;                 /* Q is already multiplied by scale*log2(e) (folded into the Q projection weights): `scale` is ignored */
     int kernel_variant;              /* 0 = automatic.  head_dim 40 then runs k_attn5 (key-split 8-wave kernel, csrc/dn_attn5.hip) when
                                         Lk % 64 == 0 and Lq % 256 == 0 and nsets * ceil(Lk / 64) >= 4, else k_attn4; head_dim 80 k_attn3; every
-                                        other head_dim and short key streams the online-softmax kernel k_attn.  A/B and test overrides:
-                                        bit 0: k_attn for every shape; bit 1: head_dim 40 on the 16x16x32 kernel (k_attn3); bit 2: k_attn4 with
-                                        8 waves; bit 3: k_attn4 with 64 queries per wave (25 % slower: DESIGN.md 7.1); bit 4: k_attn4 instead of
-                                        k_attn5; bits 5 / 6: k_attn5 with an LDS ring of 4 / 8 tiles instead of 6; bits 8..: timing ablations of
-                                        instrumented builds (ignored by the product build) */
+                                        other head_dim and short key streams the online-softmax kernel k_attn.  A/B and test overrides: an OR of
+                                        GC_ATTN_VAR_* (undefined bits are refused with GC_EINVAL) */
     void *workspace;                 /* optional, >= gc_dn_attention_workspace_bytes(desc) (0 unless head_dim == 160 and nsets > 1; ignored when 0): lets small grids with several K/V sets run */
     size_t workspace_bytes;          /* one workgroup per (query block, set) + a fixed-order fp32 combine; NULL: one launch as before */
 } gc_attn_desc;
@@ -463,7 +483,7 @@ size_t gc_dn_attention_workspace_bytes(const gc_attn_desc *desc);
 /* The kernel gc_dn_attention(desc) would launch, without launching anything (pure host function; call with the workspace set as for the launch). */
 enum { GC_ATTN_SEL_K5 = 1,          /* head_dim 40: key-split 8-wave k_attn5 (csrc/dn_attn5.hip) */
        GC_ATTN_SEL_K4 = 2,          /* head_dim 40: k_attn4 */
-       GC_ATTN_SEL_K3 = 3,          /* head_dim 80 (or 40 with kernel_variant bit 1): the 16x16x32 kernel k_attn3 */
+       GC_ATTN_SEL_K3 = 3,          /* head_dim 80 (or 40 with GC_ATTN_VAR_D40_K3): the 16x16x32 kernel k_attn3 */
        GC_ATTN_SEL_WIDE_SPLIT = 4,  /* head_dim 160, several sets: k_attn_wide, one workgroup per (query block, set), + k_attn_combine */
        GC_ATTN_SEL_SPLIT = 5,       /* online-softmax k_attn per (query block, set) + k_attn_combine (small grids) */
        GC_ATTN_SEL_ONLINE = 6 };    /* online-softmax k_attn, one launch */

@@ -1,4 +1,4 @@
-"""k_attn5 (the default D = 40 kernel; kernel_variant bit 4 = 16 selects k_attn4) vs k_attn4 and a torch fp32 reference: parity at small sizes, timing at the production launch
+"""k_attn5 (the default D = 40 kernel; GC_ATTN_VAR_K4 selects k_attn4) vs k_attn4 and a torch fp32 reference: parity at small sizes, timing at the production launch
 (L = 4096, 8 heads x D = 40, B = 6 frames, 5 K/V sets incl. a cached reference bank).   python scripts/attn5_check.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,13 +17,15 @@ def ref_attn(q, k, v, heads, scale):
     p = (qh @ kh.transpose(-1, -2) * scale).softmax(-1)
     return (p @ vh).transpose(1, 2).reshape(B, L, C)
 
+K4 = ops.GC_ATTN_VAR_K4
+
 
 def run(variant, *a, **kw):
-    ops.KERNEL_VARIANT["attn"] = variant
+    ops.configure(attn_variant=variant)
     try:
         return ops.attention(*a, **kw)
     finally:
-        ops.KERNEL_VARIANT["attn"] = 0
+        ops.configure(attn_variant=0)
 
 
 def parity(dt, f, L, heads, coeff, spike=False, pre=False):
@@ -43,7 +45,7 @@ def parity(dt, f, L, heads, coeff, spike=False, pre=False):
     for r in range(4):
         idx = torch.arange(B, device=DEV) // f * f + r
         ref = ref + (1 - coeff) / 4 * ref_attn(qq, k[idx], v[idx], heads, sc)
-    a4 = run(16, qq, k, vt, heads, sets, f, Lk=L, q_prescaled=pre).float()
+    a4 = run(K4, qq, k, vt, heads, sets, f, Lk=L, q_prescaled=pre).float()
     a5 = run(0, qq, k, vt, heads, sets, f, Lk=L, q_prescaled=pre).float()
     e4 = float((a4 - ref).norm() / ref.norm()); e5 = float((a5 - ref).norm() / ref.norm())
     d45 = float((a5 - a4).abs().max())
@@ -66,12 +68,12 @@ def timing(dt, variant, iters=20, qscale=0.5):
         run(variant, q, k, vt, heads, sets, f, Lk=L, kref=kr, vtref=vtr, ref_fph=4, q_prescaled=True)
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ops.KERNEL_VARIANT["attn"] = variant
+    ops.configure(attn_variant=variant)
     s.record()
     for _ in range(iters):
         ops.attention(q, k, vt, heads, sets, f, Lk=L, kref=kr, vtref=vtr, ref_fph=4, q_prescaled=True)
     e.record(); torch.cuda.synchronize()
-    ops.KERNEL_VARIANT["attn"] = 0
+    ops.configure(attn_variant=0)
     us = s.elapsed_time(e) * 1e3 / iters
     fl = 4.0 * B * L * L * C * 5
     print(f"timing {str(dt):16s} qscale {qscale} variant {variant:2d}: {us:8.1f} us   {fl / us / 1e6:7.1f} TF/s   frac of 2.5 PF {fl / us / 1e6 / 2500:.3f}")
@@ -88,9 +90,9 @@ if __name__ == "__main__":
         timing(torch.bfloat16, 0)
         for bits, nm in names.items():
             print(f"ablation {bits:3d} {nm:46s}", end=" ")
-            timing(torch.bfloat16, (bits or 256) << 8)          # (256: no ablation bit set, instrumented instantiation)
+            timing(torch.bfloat16, (bits or 256) << ops.GC_ATTN_VAR_ABL_SHIFT)          # (256: no ablation bit set, instrumented instantiation)
         sys.exit(0)
-    if len(sys.argv) > 1 and sys.argv[1] == "shift":          # f16: offset shift c (kernel_variant bits 16..20): fallback rate (time) and accuracy
+    if len(sys.argv) > 1 and sys.argv[1] == "shift":          # f16: offset shift c (GC_ATTN_VAR_CSHIFT_*): fallback rate (time) and accuracy
         import numpy as np
         for qs in (0.35, 0.6, 1.0):
             for c in (0, 4, 8, 12, 14):
@@ -104,14 +106,14 @@ if __name__ == "__main__":
                 for r in range(4):
                     idx = torch.arange(B, device=DEV) // f * f + r
                     ref = ref + 0.1 * ref_attn(q, k[idx], v[idx], heads, float(np.log(2.0)))
-                got = run(c << 16, q, k, vt, heads, sets, f, Lk=L, q_prescaled=True).float()
+                got = run(c << ops.GC_ATTN_VAR_CSHIFT_SHIFT, q, k, vt, heads, sets, f, Lk=L, q_prescaled=True).float()
                 err = float((got - ref).norm() / ref.norm())
                 print(f"qscale {qs} shift {c:2d}: rel L2 {err:.3e}", end="   ")
-                timing(torch.float16, c << 16, iters=5, qscale=qs)
+                timing(torch.float16, c << ops.GC_ATTN_VAR_CSHIFT_SHIFT, iters=5, qscale=qs)
         sys.exit(0)
-    if len(sys.argv) > 1 and sys.argv[1] == "f16":            # why is f16 slower at wide logit spreads?  safe kernel (1), k_attn4 (16), k_attn5 (0)
+    if len(sys.argv) > 1 and sys.argv[1] == "f16":            # why is f16 slower at wide logit spreads?  safe kernel, k_attn4, k_attn5
         for qs in (0.25, 0.5, 0.7):
-            for v in (1, 16, 0):
+            for v in (ops.GC_ATTN_VAR_ONLINE_ONLY, K4, 0):
                 timing(torch.float16, v, iters=5, qscale=qs)
                 timing(torch.bfloat16, v, iters=5, qscale=qs)
         sys.exit(0)
@@ -126,10 +128,10 @@ if __name__ == "__main__":
             ok = ok and e5 <= max(1.5 * e4, 2e-3 if dt == torch.float16 else 1.2e-2)
     print("PARITY", "OK" if ok else "FAIL")
     for dt in (torch.bfloat16, torch.float16):
-        for v in (16, 0, 16, 0):
+        for v in (K4, 0, K4, 0):
             timing(dt, v)
     for qs in (0.25, 0.35):
-        for v in (16, 0):
+        for v in (K4, 0):
             timing(torch.float16, v, qscale=qs)
-    for v in (0, 16, 0, 16):       # k_attn5, k_attn4
+    for v in (0, K4, 0, K4):       # k_attn5, k_attn4
         timing(torch.bfloat16, v)

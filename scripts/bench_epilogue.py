@@ -34,5 +34,5 @@ for (L, K, N) in [(4096, 320, 320), (1024, 640, 640), (256, 1280, 1280), (64, 12
         tc = timeit(lambda: ops.layernorm(xo, g1, b1))
         print(f"       consumer N={N2:5d} geglu{int(geglu)}: plain {ta:6.1f} us  LN-folded {tb:6.1f} ({tb - ta:+.1f})   [layernorm alone {tc:5.1f} us]")
 import os
-if os.environ.get("GC_GEMM_DBG"):
-    print("GC_GEMM_DBG =", os.environ["GC_GEMM_DBG"], "(1: no global group atomics, 2: no LDS atomics, 4: no DPP reduce)")
+if os.environ.get("GC_GEMM_EPI_ABL"):
+    print("GC_GEMM_EPI_ABL =", os.environ["GC_GEMM_EPI_ABL"], "(1: no global group atomics, 2: no LDS atomics, 4: no DPP reduce)")

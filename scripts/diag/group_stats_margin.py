@@ -17,7 +17,7 @@ for dt in (torch.float16, torch.bfloat16):
         g = torch.Generator(device="cpu").manual_seed(2)
         w = conv3x3_weight((torch.randn((Cout, Cin, 3, 3), generator=g) * (9 * Cin) ** -0.5).to(dt).to(dev), dt)
         worst, worst_abs, over = 0.0, 0.0, 0
-        ops.KERNEL_VARIANT["gemm"] = mt
+        ops.configure(gemm_variant=mt << ops.GC_GEMM_VAR_MT_SHIFT)
         for it in range(draws):
             b = torch.randn(Cout, device=dev); rv = torch.randn(B, Cout, device=dev)
             gs = torch.zeros(B, 32, 2, device=dev)
@@ -30,5 +30,5 @@ for dt in (torch.float16, torch.bfloat16):
             if r > worst:
                 worst = r; idx = tuple((rel == rel.max()).nonzero()[0].tolist()); worst_abs = float(err[idx]); wref = float(ref[idx]); wmax = float(ref.abs().max())
             over += r >= 2e-5
-        ops.KERNEL_VARIANT["gemm"] = 0
+        ops.configure(gemm_variant=0)
         print(f"{dt} B{B} {H}x{H}: worst rel {worst:.3e} of bar 2e-5 (abs err {worst_abs:.4g} on ref {wref:.6g}, max|ref| {wmax:.5g}); {over} of {draws} draws over the bar")

@@ -16,7 +16,7 @@ for dt in (torch.float16, torch.bfloat16):
       x = torch.randn(B, H, H, Cin, device=dev, generator=g).to(dt)
       w = conv3x3_weight((torch.randn(Cout, Cin, 3, 3, device=dev, generator=g) * (9 * Cin) ** -0.5).to(dt), dt)
       b = torch.randn(Cout, device=dev, generator=g); rv = torch.randn(B, Cout, device=dev, generator=g)
-      ops.KERNEL_VARIANT["gemm"] = mt
+      ops.configure(gemm_variant=mt << ops.GC_GEMM_VAR_MT_SHIFT)
       ref_out = None
       for it in range(iters):
           gs = torch.zeros(B, 32, 2, device=dev)
@@ -32,5 +32,5 @@ for dt in (torch.float16, torch.bfloat16):
               bad += 1
               idx = (err == err.max()).nonzero()[0].tolist()
               print(dt, it, "STATS off: rel", float(err.max()), "at (batch, group, which)", idx, "got", float(gs[tuple(idx)]), "want", float(ref[tuple(idx)]))
-      ops.KERNEL_VARIANT["gemm"] = 0
+      ops.configure(gemm_variant=0)
 print("bad", bad, "of", 2 * iters)

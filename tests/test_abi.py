@@ -129,6 +129,7 @@ def test_fp8_gemm_planning_queries(built):
     reduce kernel (32-row slabs, 64-column blocks); full grids are not sliced and leave them through k_gemm8q's own epilogue (row-tile
     slabs); GEGLU / e4m3-output / statistics problems are never sliced; with plan_rows (batch-invariant mode) the slice count depends on the
     rows ONE frame contributes, not on the batch."""
+    from gaussctrl_amd.sd import ops
     from gaussctrl_amd.sd.ops import GemmDesc
     lib = ctypes.CDLL(built)
     lib.gc_dn_gemm_workspace_bytes.restype = ctypes.c_size_t
@@ -160,7 +161,7 @@ def test_fp8_gemm_planning_queries(built):
     assert splits(conv(6, 32, 640, 640)) == 0 and splits(conv(6, 64, 384, 320)) == 0
     assert splits(conv(6, 16, 1280, 1280, geglu=1)) == 0 and splits(conv(6, 16, 1280, 1280, out_fp8=127)) == 0
     assert splits(conv(6, 16, 1280, 1280, out_group_stats=1)) == 0
-    assert splits(conv(6, 16, 1280, 1280, kernel_variant=2)) == 0          # a forced tile height does not slice
+    assert splits(conv(6, 16, 1280, 1280, kernel_variant=2 << ops.GC_GEMM_VAR_MT_SHIFT)) == 0          # a forced tile height (MT 2) does not slice
     assert layout(conv(6, 16, 1280, 1280)) == (32, 8, 64)       # reduce kernel: 32-row slabs, 64-column blocks
     assert layout(conv(6, 16, 1280, 1280), with_ws=False) == (128, 2, 128)   # no workspace -> unsliced, k_gemm8q's own partial epilogue
     assert layout(conv(14, 16, 1280, 1280)) == (192, 3, 128)    # MT 3 tiles of 192 rows straddle the 256-row batches
@@ -330,15 +331,151 @@ def test_attention_selection_at_launch_set_batches(built):
 
     for B in (12, 24, 40):
         assert sel(B, 4096, 40) == "attn5" and sel(B, 4096, 40, nsets=4) == "attn5"
-        assert sel(B, 4096, 40, variant=16) == "attn4" and sel(B, 4096, 40, variant=2) == "attn3" and sel(B, 4096, 40, variant=1) == "attn"
+        assert sel(B, 4096, 40, variant=ops.GC_ATTN_VAR_K4) == "attn4" and sel(B, 4096, 40, variant=ops.GC_ATTN_VAR_D40_K3) == "attn3"
+        assert sel(B, 4096, 40, variant=ops.GC_ATTN_VAR_ONLINE_ONLY) == "attn"
         assert sel(B, 1024, 80) == "attn3"
         assert sel(B, 256, 160) == "wide+combine" and sel(B, 256, 160, ws=False) == "attn"
-        assert sel(B, 256, 160, variant=128) == ("attn+combine" if B == 12 else "attn")   # the 64-query form: set split while 4 x 8 x B < 512 workgroups
+        assert sel(B, 256, 160, variant=ops.GC_ATTN_VAR_D160_Q64) == ("attn+combine" if B == 12 else "attn")   # the 64-query form: set split while 4 x 8 x B < 512 workgroups
         assert sel(B, 64, 160) == "attn+combine" and sel(B, 64, 160, ws=False) == "attn"
         assert sel(B, 4096, 40, nsets=1, Lk=77) == "attn"                 # text keys: 2 key tiles, the pipelined kernels do not amortise
     assert sel(64, 64, 160) == "attn"                                     # 512 workgroups: a full grid, no set split
-    assert sel(64, 256, 160, variant=128) == "attn"
+    assert sel(64, 256, 160, variant=ops.GC_ATTN_VAR_D160_Q64) == "attn"
     d = ops.AttnDesc()
     d.batch, d.heads, d.head_dim, d.Lq, d.Lk, d.nsets = 2, 8, 48, 64, 64, 1
     with pytest.raises(Exception):
         ops.attention_selection(d)
+
+
+def _header_variant_enumerators():
+    src = open(os.path.join(ROOT, "include", "gaussctrl_hip.h")).read()
+    return sorted(set(re.findall(r"\b(GC_(?:GEMM|ATTN)_VAR_[A-Z0-9_]+) =", src)))
+
+
+def test_variant_constants_match_the_header_and_do_not_overlap(tmp_path):
+    """the GC_GEMM_VAR_* / GC_ATTN_VAR_* constants of gaussctrl_amd/sd/ops.py have the values the C compiler gives the header's enumerators, every
+    enumerator has a Python counterpart and the reverse, and inside one kernel_variant field no two switches share a bit (bits 8..10 of the GEMM
+    field once meant two things at once); every *_MASK field sits at its *_SHIFT."""
+    import subprocess
+    from gaussctrl_amd.sd import ops
+    names = _header_variant_enumerators()
+    assert len(names) >= 29, names            # 17 GEMM + 12 attention enumerators when this was written
+    assert names == sorted(n for n in vars(ops) if re.match(r"GC_(GEMM|ATTN)_VAR_", n))
+    src = tmp_path / "var.c"
+    src.write_text('#include <stdio.h>\n#include "gaussctrl_hip.h"\nint main(void) {\n'
+                   + "".join(f'    printf("{n} %d\\n", {n});\n' for n in names) + "    return 0;\n}\n")
+    exe = tmp_path / "var"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    assert got == {n: getattr(ops, n) for n in names}
+    for kind in ("GC_GEMM_VAR_", "GC_ATTN_VAR_"):
+        bits = {n: v for n, v in got.items() if n.startswith(kind) and not n.endswith("_SHIFT")}
+        assert all(v > 0 for v in bits.values())
+        clash = [(a, b) for a in bits for b in bits if a < b and bits[a] & bits[b]]
+        assert not clash, clash
+        for n, v in bits.items():
+            if n.endswith("_MASK"):
+                sh = got[n[:-5] + "_SHIFT"]
+                assert v >> sh << sh == v and (v >> sh) & 1 and ((v >> sh) + 1) & (v >> sh) == 0, (n, v, sh)     # contiguous, lowest bit at the shift
+            else:
+                assert v & (v - 1) == 0, (n, v)
+
+
+def test_options_from_env_keeps_every_documented_value():
+    """options_from_env gives the integers it gave before the switches had names, for every GC_* variable of the README's table (literals:
+    the values are frozen by bench.py, recorded profiles and the README); the epilogue timing ablations have a variable and bits of their own."""
+    from gaussctrl_amd.sd import ops
+    g = lambda **e: ops.options_from_env(e).gemm_variant
+    a = lambda **e: ops.options_from_env(e).attn_variant
+    assert g() == 0 and a() == 0 and ops.options_from_env({}) == ops.KernelOptions()
+    assert [g(GC_GEMM_MT=v) for v in "234"] == [2, 3, 4]
+    assert [g(GC_GEMM8=v) for v in "012"] == [0x10, 0, 0x20]
+    assert [g(GC_GEMM_CONVSPLIT=v) for v in "012"] == [0x40, 0x80, 0]
+    assert [g(GC_GEMM_DBG=v) for v in ("1", "2", "4", "8", "16", "31")] == [0x100, 0x200, 0x400, 0x800, 0x1000, 0x1f00]
+    assert [g(GC_GEMM_SPLIT_MT=v) for v in "234"] == [2 << 24, 3 << 24, 4 << 24]
+    assert [g(GC_GEMM_PW=v) for v in ("0", "1", "3", "7")] == [1 << 16, 2 << 16, 4 << 16, 8 << 16]
+    assert g(GC_GEMM_MT="3", GC_GEMM8="2", GC_GEMM_DBG="5", GC_GEMM_PW="1") == 3 | 0x20 | 0x500 | (2 << 16)
+    assert a(GC_ATTN_SAFE="1") == 1 and a(GC_ATTN_16="1") == 2 and [a(GC_ATTN_V=v) for v in ("1", "2", "4", "8", "16", "32")] == [4, 8, 16, 32, 64, 128]
+    assert a(GC_ATTN_SAFE="1", GC_ATTN_16="1", GC_ATTN_V="4") == 19
+    # the fused-statistics epilogue's timing ablations: bits 28..30 and nothing else; GC_GEMM_DBG no longer reaches them
+    assert [g(GC_GEMM_EPI_ABL=v) for v in "124"] == [1 << 28, 2 << 28, 4 << 28]
+    for v in "124":
+        assert g(GC_GEMM_EPI_ABL=v) & ~ops.GC_GEMM_VAR_EPI_ABL_MASK == 0 and g(GC_GEMM_DBG=v) & ops.GC_GEMM_VAR_EPI_ABL_MASK == 0
+    for v in ("32", "64", "128", "33", "-1"):              # (32 was passed by an old job script; nothing read it)
+        with pytest.raises(ValueError):
+            g(GC_GEMM_DBG=v)
+    o = ops.options_from_env({"GC_BATCH_INVARIANT": "1", "GC_FUSED_HEAD": "0", "GC_FUSED_TAIL": "0", "GC_ABLATE": "gn,ln"})
+    assert o.batch_invariant and not o.fused_head and not o.fused_tail and o.two_streams and o.ablate == frozenset({"gn", "ln"})
+
+
+def test_undefined_variant_bits_are_refused(built):
+    """kernel_variant bits no switch owns: gc_dn_gemm_selection / gc_dn_attention_selection return GC_EINVAL and name the bits (gc_dn_gemm and
+    gc_dn_attention make the same two calls -- decode_variant, refuse_variant_bits -- among their argument checks, before anything is launched); the size and layout queries, which have no error
+    channel, keep ignoring them; every defined bit passes."""
+    from gaussctrl_amd.sd import ops
+    lib = ctypes.CDLL(built)
+    lib.gc_dn_gemm_workspace_bytes.restype = ctypes.c_size_t
+    lib.gc_last_error_string.restype = ctypes.c_char_p
+    d = ops.GemmDesc()
+    d.dtype = 1; d.mode = 0; d.M, d.N, d.K = 6144, 640, 640
+    d.lda = 640; d.out = 1; d.ldc = 640; d.zeros = 1; d.rows_per_batch = 1024
+    sel = ops.GemmSelection()
+    for bad in (0x8, 0x2000, 0x4000, 0x8000, 1 << 27, -(1 << 31)):
+        d.kernel_variant = bad | ops.GC_GEMM_VAR_K4_ONLY
+        assert lib.gc_dn_gemm_selection(ctypes.byref(d), ctypes.byref(sel)) == -1
+        assert b"kernel_variant" in lib.gc_last_error_string() and ("0x%x" % (bad & 0xffffffff)).encode() in lib.gc_last_error_string()
+        sizes = lib.gc_dn_gemm_workspace_bytes(ctypes.byref(d)), lib.gc_dn_gemm_row_stat_slots(ctypes.byref(d))
+        d.kernel_variant = ops.GC_GEMM_VAR_K4_ONLY
+        assert sizes == (lib.gc_dn_gemm_workspace_bytes(ctypes.byref(d)), lib.gc_dn_gemm_row_stat_slots(ctypes.byref(d))) and sizes[1] > 0
+    a = ops.AttnDesc()
+    a.dtype = 1; a.batch, a.heads, a.head_dim, a.Lq, a.Lk, a.nsets = 12, 8, 40, 4096, 4096, 5
+    k = ctypes.c_int(0)
+    for bad in (1 << 21, 1 << 24, -(1 << 31)):
+        a.kernel_variant = bad | ops.GC_ATTN_VAR_K4
+        assert lib.gc_dn_attention_selection(ctypes.byref(a), ctypes.byref(k)) == -1
+        assert ("0x%x" % (bad & 0xffffffff)).encode() in lib.gc_last_error_string()
+    all_gemm = 0
+    for n, v in vars(ops).items():
+        if n.startswith("GC_GEMM_VAR_") and not n.endswith("_SHIFT"):
+            all_gemm |= v
+    d.kernel_variant = all_gemm & ~(ops.GC_GEMM_VAR_MT_MASK ^ 4)       # every defined bit (MT field = 4)
+    assert lib.gc_dn_gemm_selection(ctypes.byref(d), ctypes.byref(sel)) == 0
+    a.kernel_variant = ops.GC_ATTN_VAR_ABL_MASK | ops.GC_ATTN_VAR_CSHIFT_MASK | 0xff
+    assert lib.gc_dn_attention_selection(ctypes.byref(a), ctypes.byref(k)) == 0
+
+
+def test_options_is_the_only_switch_state(built, monkeypatch):
+    """ops.OPTIONS owns the switches: what configure() sets is what the compatibility view ops.KERNEL_VARIANT shows (bench.py reads it) and what
+    the descriptors built by the launch path carry; KernelOptions keeps its fields (bench.py prints dataclasses.asdict(OPTIONS))."""
+    import dataclasses
+    from gaussctrl_amd.sd import ops
+    assert list(dataclasses.asdict(ops.KernelOptions())) == ["gemm_variant", "attn_variant", "batch_invariant", "fused_head", "fused_tail", "two_streams", "gn_parts",
+                                                            "tail_in_rows", "q_only", "ffout_merge", "text_fold", "cfg_share", "fp8_min_hw", "ablate"]
+    assert ops.KernelOptions() == ops.KernelOptions(0, 0, False, True, True, True, True, True, True, True, True, True, 256, frozenset())
+    keep = ops.OPTIONS
+    X = ops.GC_GEMM_VAR_NO_PERSIST | 3
+    try:
+        got = ops.configure(gemm_variant=X, attn_variant=ops.GC_ATTN_VAR_K4, batch_invariant=True)
+        assert got is ops.OPTIONS and ops.KERNEL_VARIANT == {"gemm": X, "attn": ops.GC_ATTN_VAR_K4}
+        view = ops.KERNEL_VARIANT
+        view["gemm"] = 0                                   # a view: writing to it changes nothing
+        assert ops.KERNEL_VARIANT == {"gemm": X, "attn": ops.GC_ATTN_VAR_K4} and ops.OPTIONS.gemm_variant == X
+        ops.BATCH_INVARIANT = False                        # the old global's name: an assignment lands in OPTIONS
+        assert ops.OPTIONS.batch_invariant is False and ops.OPTIONS.gemm_variant == X
+        monkeypatch.setattr(ops, "BATCH_INVARIANT", True)
+        assert ops.OPTIONS.batch_invariant is True and ops.BATCH_INVARIANT is True
+
+        class Stop(Exception):
+            pass
+
+        class Lib:                                         # the library as _run_gemm sees it, stopped at its first query
+            def gc_dn_gemm_workspace_bytes(self, ref):
+                raise Stop
+        monkeypatch.setattr(ops.L, "lib", lambda: Lib())
+        monkeypatch.setitem(ops._zero_page, "cpu", type("Z", (), {"data_ptr": lambda self: 64})())
+        d = ops.GemmDesc()
+        with pytest.raises(Stop):
+            ops._run_gemm(d, "cpu", "test")
+        assert d.kernel_variant == X
+    finally:
+        ops.configure(keep)
+    assert ops.KERNEL_VARIANT == {"gemm": keep.gemm_variant, "attn": keep.attn_variant}

@@ -1,11 +1,15 @@
 """GPU parity of the individual denoise kernels (through the C ABI) against plain PyTorch fp32/fp64
 references of the same op evaluated on the SAME 2-byte-rounded inputs.  Tolerance: one output rounding of
 the activation dtype (bf16: 2^-8, f16: 2^-11 relative) plus accumulation-order noise."""
+import dataclasses
+
 import numpy as np
 import pytest
 from _margins import within
 import torch
 import torch.nn.functional as F
+
+from gaussctrl_amd.sd.ops import GC_GEMM_VAR_NO_LEAN_LN
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -165,7 +169,7 @@ def test_groupnorm_from_producer_partials(dt, kind, B, H, Cin, Cout):
         a = (_rand((B, H, H, Cin), dt, 1.0, 1).float() + 2.0).to(dt); bb = _rand((B, H, H, Cout), dt, 1.0, 2); cc = _rand((B, H, H, Cout), dt, 1.0, 3)
         out, parts = ops.concat_add(a, bb, cc, chan_parts=True)
         plain = ops.concat_add(a, bb, cc)
-    if parts is None and ops.KERNEL_VARIANT["gemm"]:
+    if parts is None and ops.OPTIONS.gemm_variant:
         pytest.skip("a forced kernel variant (tests/test_gemm_variants_gpu.py) without the statistics epilogue")
     assert parts is not None, "this shape must take the producer-statistics path"
     assert torch.equal(out, plain)                          # the statistics epilogue does not change what is stored
@@ -402,7 +406,7 @@ def test_statistics_buffers_nan_poisoned(kind, B, H, Cin, Cout, monkeypatch):
         y = ops.linear(x, wf, torch.zeros(Cout, device=DEV), ln=(rs, wf.float().sum(1).contiguous(), 1e-5))
         assert torch.isfinite(y.float()).all()
         return
-    if parts is None and ops.KERNEL_VARIANT["gemm"]:
+    if parts is None and ops.OPTIONS.gemm_variant:
         pytest.skip("forced kernel variant (tests/test_gemm_variants_gpu.py): the 4-wave kernel leaves no channel partials")
     assert parts is not None
     gamma = torch.randn(out.shape[-1], device=DEV); beta = torch.randn(out.shape[-1], device=DEV)
@@ -420,7 +424,7 @@ def test_statistics_buffers_nan_poisoned(kind, B, H, Cin, Cout, monkeypatch):
 
 
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("variant", [0, 0x800])
+@pytest.mark.parametrize("variant", [0, GC_GEMM_VAR_NO_LEAN_LN])
 @pytest.mark.parametrize("M,N,K,geglu", [(512, 960, 320, False), (24576, 960, 320, False), (300, 1280, 1280, False), (1024, 2560, 320, True),
                                          (384, 10240, 1280, True), (6144, 5120, 640, True), (1536, 10240, 1280, True), (1536, 1280, 1280, False),
                                          (6144, 640, 640, False)])
@@ -428,11 +432,11 @@ def test_linear_layernorm_folded(dt, M, N, K, geglu, variant, monkeypatch):
     """consumer side: y = LN(x) W^T + b computed as rstd (x W'^T - mean colsum) + b' from the row sums the PRODUCER of x left
     (here: an identity-free producer GEMM x = x0 W0^T + residual so that the slab layout is the real one); reference = torch layer_norm +
     matmul in fp64 on the same rounded x and the UNfolded weights.  variant 0: the LEAN fold of round 5 (k_gemm8<.., LNV = 1 | 2>, the
-    persistent k_gemm8p<.., 2> for the multi-round GEGLU shapes, the 64-row two-workgroups-per-CU tile for the K = N = C shapes); 0x800: the
+    persistent k_gemm8p<.., 2> for the multi-round GEGLU shapes, the 64-row two-workgroups-per-CU tile for the K = N = C shapes); GC_GEMM_VAR_NO_LEAN_LN: the
     round-2 everything-epilogue (FUSE), kept as the fallback of split-K / statistics-carrying problems."""
     from gaussctrl_amd.sd import ops
     from gaussctrl_amd.sd.weights import _fold_ln, geglu_permute
-    monkeypatch.setitem(ops.KERNEL_VARIANT, "gemm", ops.KERNEL_VARIANT["gemm"] | variant)
+    monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(ops.OPTIONS, gemm_variant=ops.OPTIONS.gemm_variant | variant))
     x0 = _rand((M, 256), dt, 1.0, 1); w0 = _rand((K, 256), dt, 256 ** -0.5 * 1.7, 5); b0 = torch.full((K,), 0.4, device=DEV)
     res = _rand((M, K), dt, 0.7, 9)
     rs = ops.RowStats()
@@ -463,7 +467,7 @@ def test_linear_layernorm_folded(dt, M, N, K, geglu, variant, monkeypatch):
 
 
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("variant", [0, 0x800])
+@pytest.mark.parametrize("variant", [0, GC_GEMM_VAR_NO_LEAN_LN])
 @pytest.mark.parametrize("B,L,C", [(6, 1024, 640), (6, 256, 1280), (2, 64, 1280)])
 def test_qkv_transposed_v_with_layernorm_folded(dt, B, L, C, variant, monkeypatch):
     """the fused Q | K | V^T projection (columns [0, 2C) -> qk, [2C, 3C) -> V^T [B, C, Lp]) as a LayerNorm-FOLDED consumer: norm1 of a C = 640 /
@@ -471,7 +475,7 @@ def test_qkv_transposed_v_with_layernorm_folded(dt, B, L, C, variant, monkeypatc
     the proj_in-like producer's lean epilogue"""
     from gaussctrl_amd.sd import ops
     from gaussctrl_amd.sd.weights import _fold_ln
-    monkeypatch.setitem(ops.KERNEL_VARIANT, "gemm", ops.KERNEL_VARIANT["gemm"] | variant)
+    monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(ops.OPTIONS, gemm_variant=ops.OPTIONS.gemm_variant | variant))
     x0 = _rand((B, L, C), dt, 1.0, 1); w0 = _rand((C, C), dt, C ** -0.5 * 1.5, 5); b0 = torch.full((C,), -0.2, device=DEV)
     rs = ops.RowStats()
     x = ops.linear(x0, w0, b0, row_stats=rs)
@@ -726,7 +730,7 @@ def test_groupnorm_apply_parts_fp8(dt, kind, B, H, Cin, Cout):
     else:
         a = (_rand((B, H, H, Cin), dt, 1.0, 1).float() + 1.0).to(dt); bb = _rand((B, H, H, Cout), dt, 1.0, 2)
         out, parts = ops.concat_add(a, bb, None, chan_parts=True)
-    if parts is None and ops.KERNEL_VARIANT["gemm"]:
+    if parts is None and ops.OPTIONS.gemm_variant:
         pytest.skip("a forced kernel variant without the statistics epilogue")
     assert parts is not None
     Co = out.shape[-1]
@@ -766,7 +770,7 @@ def test_conv3x3_fp8_k_sliced_with_partials(dt, B, H, Cin, Cout):
     plain = ops.conv3x3_fp8(x8.to(DEV), w8.to(DEV), wsc.to(DEV), dt, b.to(DEV), rowvec=rv, ld_rowvec=0, residual=res)
     assert torch.equal(out, plain)
     assert parts is not None, "every resnet convolution of the fp8 path leaves the partials of its output"
-    if B * H * H <= 128 * 12 and H == 16 and not ops.KERNEL_VARIANT["gemm"]:      # (a forced tile height, tests/test_gemm_variants_gpu.py, does not slice)
+    if B * H * H <= 128 * 12 and H == 16 and not ops.OPTIONS.gemm_variant:      # (a forced tile height, tests/test_gemm_variants_gpu.py, does not slice)
         assert parts.rows == 32 and parts.col_tile == 64, "a part-filled grid with a long K must take the k-sliced path"
     if parts is not None:
         G, cpg = 32, Cout // 32
@@ -844,7 +848,7 @@ def test_tile_order_does_not_change_results(dt, monkeypatch):
     for name, fn in cases():
         o = fn(); base[name] = (o[0] if isinstance(o, tuple) else o).clone()
     for pw in (0, 1, 3, 7):
-        monkeypatch.setitem(ops.KERNEL_VARIANT, "gemm", (pw + 1) << 16)
+        monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(ops.OPTIONS, gemm_variant=(pw + 1) << ops.GC_GEMM_VAR_PW_SHIFT))
         for name, fn in cases():
             o = fn(); o = o[0] if isinstance(o, tuple) else o
             assert torch.equal(o, base[name]), (name, pw)
@@ -853,7 +857,7 @@ def test_tile_order_does_not_change_results(dt, monkeypatch):
 @pytest.mark.parametrize("dt", DTS)
 def test_attention_head160_wide_form_matches_64_query_form(dt, monkeypatch):
     """k_attn_wide (head size 160, set-split: all 256 queries of a (frame, head) in one 8-wave workgroup, 32 queries per wave) runs the same body as
-    the 64-query form (kernel_variant bit 7): per set the same keys in the same tile order -> bit-identical partial outputs and result."""
+    the 64-query form (GC_ATTN_VAR_D160_Q64): per set the same keys in the same tile order -> bit-identical partial outputs and result."""
     from gaussctrl_amd.sd import ops
     f, L, heads, D = 5, 256, 8, 160
     B, C = 2 * f, heads * D
@@ -862,7 +866,7 @@ def test_attention_head160_wide_form_matches_64_query_form(dt, monkeypatch):
     vt = v.transpose(1, 2).contiguous()
     sets = [(-1, 0.6)] + [(r, 0.1) for r in range(4)]
     wide = ops.attention(q, k, vt, heads, sets, f, Lk=L)
-    monkeypatch.setitem(ops.KERNEL_VARIANT, "attn", 128)
+    monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(ops.OPTIONS, attn_variant=ops.GC_ATTN_VAR_D160_Q64))
     narrow = ops.attention(q, k, vt, heads, sets, f, Lk=L)
     assert torch.equal(wide, narrow)
 

@@ -142,8 +142,7 @@ def test_cfg_shared_prefix_equals_duplicated_computation(sd15, dt, monkeypatch):
     keep = ops.OPTIONS
 
     def run(share, invariant):
-        monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(keep, cfg_share=share))
-        monkeypatch.setattr(ops, "BATCH_INVARIANT", invariant)
+        monkeypatch.setattr(ops, "OPTIONS", dataclasses.replace(keep, cfg_share=share, batch_invariant=invariant))
         a = pipe.edit_chunk(to(lat), to(disp), to(cn), to(cp), steps=2)
         bank = pipe.build_ref_bank(to(lat[:4]), to(disp[:4]), to(cn), to(cp), steps=2)
         b = pipe.edit_chunk_cached(to(lat[4:]), to(disp[4:]), to(cn), to(cp), bank, steps=2)

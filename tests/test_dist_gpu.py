@@ -2,6 +2,7 @@
 GaussCtrlPipeline.render_reverse -> edit_images -> train_iteration (views sharded v % 2, reference K / V^T replicated OR computed by an
 owner rank and broadcast step by step, edited images all-gathered, Gaussian gradients all-reduced), compared with the single-rank run
 of the same scene.  (8-GPU RCCL runs are the driver's; this exercises every line of the N > 1 logic on the HIP kernels.)"""
+import dataclasses
 import os
 
 import numpy as np
@@ -88,7 +89,7 @@ def _worker(rank, world, port, owner, ret, gather=False):
 
 @pytest.mark.parametrize("owner,invariant", [(-1, False), (0, False), (0, True), ("allgather", False), ("allgather", True)])
 def test_two_ranks_one_gpu_match_single_rank(owner, invariant, monkeypatch):
-    """invariant: batch-invariant kernel planning (sd.ops.BATCH_INVARIANT; the spawned ranks read GC_BATCH_INVARIANT) -- the edited images
+    """invariant: batch-invariant kernel planning (sd.ops.OPTIONS.batch_invariant; the spawned ranks read GC_BATCH_INVARIANT) -- the edited images
     of the 2-rank run are then BIT-identical to the single-rank run, although the chunks hold other views.
     owner "allgather": the reference trajectory itself is sharded by sample (rank r runs both CFG halves of frames {r, r + 2}) and every
     cross-view attention layer all-gathers K / V^T (dist.RefShard) -- bit-identical to the single-rank bank in invariant mode too."""
@@ -96,7 +97,7 @@ def test_two_ranks_one_gpu_match_single_rank(owner, invariant, monkeypatch):
     owner = -1 if gather else owner
     from gaussctrl_amd.sd import ops as sdops
     monkeypatch.setenv("GC_BATCH_INVARIANT", "1" if invariant else "0")
-    monkeypatch.setattr(sdops, "BATCH_INVARIANT", invariant)
+    monkeypatch.setattr(sdops, "OPTIONS", dataclasses.replace(sdops.OPTIONS, batch_invariant=invariant))
     # poison the caching allocator first: a fresh process hands out zero pages, a long-running one recycled garbage -- a kernel that
     # reads memory nobody wrote would agree with the (fresh) spawned ranks only by luck of the zeros
     junk = [torch.full((n,), float("nan"), device="cuda:0") for n in (1 << 26, 1 << 24, 1 << 22, 1 << 20, 1 << 18)]
@@ -197,7 +198,7 @@ def test_ref_shard_world4_end_to_end(world, monkeypatch):
     here: its 8 ranks and this process would be 9 processes on one GPU, and the suite keeps at most 6 on a GPU at a time; its sharding
     layout is tests/test_dist_cpu.py::test_reference_trajectory_shards_allgather_layout[8]."""
     from gaussctrl_amd.sd import ops as sdops
-    monkeypatch.setattr(sdops, "BATCH_INVARIANT", True)
+    monkeypatch.setattr(sdops, "OPTIONS", dataclasses.replace(sdops.OPTIONS, batch_invariant=True))
     pipe, inputs = _tiny_pipe()
     ref_bank = pipe.build_ref_bank(*inputs, steps=3)
     g = torch.Generator().manual_seed(9)

@@ -341,7 +341,7 @@ def test_config4_f12_fp8_convs_and_linears(nets, cached):
 
 @pytest.mark.parametrize("dt,chunk", [(torch.float16, 3), (torch.bfloat16, 3), (torch.bfloat16, 8)])
 def test_batch_invariant_mode_bit_identical(nets, dt, chunk):
-    """sd.ops.BATCH_INVARIANT (gc_gemm_desc.plan_rows, GroupNorm planning bit, no set-split attention): a view's latents are BIT-identical
+    """sd.ops.OPTIONS.batch_invariant (gc_gemm_desc.plan_rows, GroupNorm planning bit, no set-split attention): a view's latents are BIT-identical
     whatever shares its chunk -- the property that makes an N-rank edit (other chunk compositions) equal to the single-GPU one.
     Full SD1.5 widths at 64 x 64 latents, cached reference bank, 3 DDIM steps: chunk {0,1,2} vs chunks {0} and {1,2}; and BASELINE
     configs[3]'s chunk_size 8 (CFG batch 16) vs two chunks of 4 (CFG batch 8) -- at B = 16 the D = 160 attention grid reaches 512 workgroups,
@@ -350,8 +350,8 @@ def test_batch_invariant_mode_bit_identical(nets, dt, chunk):
     from gaussctrl_amd.sd.pipeline import DenoisePipeline
     lat, disp, cn, cp = _inputs(4 + chunk, 64, 2)
     uw, cw = nets(dt)
-    keep = ops.BATCH_INVARIANT
-    ops.BATCH_INVARIANT = True
+    keep = ops.OPTIONS
+    ops.configure(batch_invariant=True)
     nst = 3 if chunk == 3 else 2
     cut = 1 if chunk == 3 else chunk // 2
     try:
@@ -365,11 +365,11 @@ def test_batch_invariant_mode_bit_identical(nets, dt, chunk):
         assert torch.equal(full[:cut], one), float((full[:cut] - one).abs().max())
         assert torch.equal(full[cut:], two), float((full[cut:] - two).abs().max())
         # and it is still the same computation: within the dtype's bar of the default planning
-        ops.BATCH_INVARIANT = False
+        ops.configure(batch_invariant=False)
         ref = pipe.edit_chunk_cached(to(lat[4:]), to(disp[4:]), to(cn), to(cp), bank, steps=nst)
         within("_rel(full, ref)", _rel(full, ref), BAR[dt])
     finally:
-        ops.BATCH_INVARIANT = keep
+        ops.configure(keep)
 
 
 def test_edit_f7_h64_fp8_convs(nets):
