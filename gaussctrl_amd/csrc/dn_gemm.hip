@@ -1,7 +1,9 @@
 // dn_gemm.hip -- host side of the bf16 / f16 / fp8 MFMA GEMM and implicit-GEMM 3x3 convolution of the SD1.5 UNet / ControlNet / VAE
-// blocks (gfx950): problem validation, kernel selection, launches.  The kernels live in dn_gemm_kernels.h and are instantiated in
-// three translation units that compile in parallel: dn_gemm_plain.hip (lean epilogue), dn_gemm_fuse.hip (fused-normalisation
-// epilogue), dn_gemm_fp8.hip (e4m3 operands on the block-scaled MFMA).  Reference call sites: see dn_gemm_kernels.h.
+// blocks (gfx950): problem validation, kernel selection, launches.  The GEMM is seven translation units that compile in parallel: this
+// one, and six that instantiate the kernels of dn_gemm_kernels.h -- dn_gemm_plain.hip (plain epilogue, split-K reduce kernels),
+// dn_gemm_fuse.hip (fused-normalisation epilogue), dn_gemm_lean.hip (lean epilogue), dn_gemm_cs.hip (lean epilogue + GroupNorm channel
+// partials), dn_gemm_ln.hip (lean LayerNorm fold), dn_gemm_fp8.hip (e4m3 operands on the block-scaled MFMA).  Reference call sites: see
+// dn_gemm_kernels.h.
 #include "dn_gemm_kernels.h"
 
 namespace {

@@ -29,16 +29,16 @@ void launch8q_cs(const GemmArgs &g, dim3 grid, hipStream_t s)
 template <class T>
 void dispatch8q(const GemmArgs &g, int mode, int ntw, int mt, dim3 grid, hipStream_t s)
 {
-    if (g.chan_parts && g.splits == 1) {      // (the launcher admits this for mode 2 without fused statistics only)
-        if (ntw == 5) launch8q_cs<T, 5, 2>(g, grid, s);
-        else if (mt == 3) launch8q_cs<T, 4, 3>(g, grid, s);
-        else launch8q_cs<T, 4, 2>(g, grid, s);
-        return;
-    }
-#define GC_Q(NTW_, MT_) do { if (mode == 2) launch8q<T, 2, NTW_, MT_>(g, grid, s); else launch8q<T, 3, NTW_, MT_>(g, grid, s); } while (0)
-    if (ntw == 5) GC_Q(5, 2);
-    else { if (mt == 3) GC_Q(4, 3); else GC_Q(4, 2); }
-#undef GC_Q
+    // the wave tiles that fit under 256 VGPRs, and no others instantiated: (5, 2) (4, 2) (4, 3)
+    if (ntw == 5 || mt != 3) mt = 2;
+    with_wave_tile(ntw, mt, [&](auto ntw_, auto mt_) {
+        constexpr int NTW = decltype(ntw_)::value, MT = decltype(mt_)::value;
+        if constexpr (MT == 2 || (NTW == 4 && MT == 3)) {
+            if (g.chan_parts && g.splits == 1) launch8q_cs<T, NTW, MT>(g, grid, s);      // (the launcher admits this for mode 2 without fused statistics only)
+            else if (mode == 2) launch8q<T, 2, NTW, MT>(g, grid, s);
+            else launch8q<T, 3, NTW, MT>(g, grid, s);
+        }
+    });
 }
 }  // namespace
 

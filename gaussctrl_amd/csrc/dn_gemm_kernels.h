@@ -1267,8 +1267,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
             const int64_t n = n_lane + nt * 16;
-            const bool okn = n < g.N && !(!LEAN && g.geglu && (nt & 1));
-            const int64_t on = (!LEAN && g.geglu) ? (n_base + wn * (16 * NTW) + nt * 16) / 2 + fc * 4 : n;
+            const bool okn = n < g.N && !(g.geglu && (nt & 1));
+            const int64_t on = g.geglu ? (n_base + wn * (16 * NTW) + nt * 16) / 2 + fc * 4 : n;
             rv[nt] = (g.rowvec && n < g.N) ? *reinterpret_cast<const float4 *>(g.rowvec + bidx * g.ld_rowvec + n) : make_float4(0.f, 0.f, 0.f, 0.f);
             rs[nt] = (g.residual && okn) ? *reinterpret_cast<const uint2 *>((const unsigned char *)g.residual + (m * g.ldr + on) * 2) : make_uint2(0u, 0u);
         }
@@ -1276,21 +1276,21 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         for (int nt = 0; nt < NTW; ++nt) {
             const int64_t n = n_lane + nt * 16;
             if (n >= g.N) continue;
-            if (!LEAN && g.geglu && (nt & 1)) continue;
+            if (g.geglu && (nt & 1)) continue;
             float v[4] = {acc[nt][mt][0] + bia[nt].x + rv[nt].x, acc[nt][mt][1] + bia[nt].y + rv[nt].y,
                           acc[nt][mt][2] + bia[nt].z + rv[nt].z, acc[nt][mt][3] + bia[nt].w + rv[nt].w};
             int64_t on = n;
-            if (!LEAN && g.geglu) {
+            if (g.geglu) {
                 constexpr int NP = NTW - 1;
                 const int np = nt + 1 < NTW ? nt + 1 : NP;
                 v[0] *= gelu_erf(acc[np][mt][0] + bia[np].x); v[1] *= gelu_erf(acc[np][mt][1] + bia[np].y);
                 v[2] *= gelu_erf(acc[np][mt][2] + bia[np].z); v[3] *= gelu_erf(acc[np][mt][3] + bia[np].w);
                 on = (n_base + wn * (16 * NTW) + nt * 16) / 2 + fc * 4;
             }
-            if (!LEAN && g.act == 1) {
+            if (g.act == 1) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = silu(v[r]);
-            } else if (!LEAN && g.act == 2) {
+            } else if (g.act == 2) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fminf(fmaxf(v[r] * 0.5f + 0.5f, 0.f), 1.f);
             }
@@ -1300,10 +1300,10 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
                 v[0] += T::to_f((unsigned short)(rs[nt].x & 0xffff)); v[1] += T::to_f((unsigned short)(rs[nt].x >> 16));
                 v[2] += T::to_f((unsigned short)(rs[nt].y & 0xffff)); v[3] += T::to_f((unsigned short)(rs[nt].y >> 16));
             }
-            const bool to_t = !LEAN && g.out_t && on >= g.t_col0;
+            const bool to_t = g.out_t && on >= g.t_col0;
             const uint2 pk = make_uint2(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]));
             if (g.out && !(to_t && g.t_col0 > 0)) {
-                if (!LEAN && g.out_f32)
+                if (g.out_f32)
                     *reinterpret_cast<float4 *>((float *)g.out + m * g.ldc + on) = make_float4(v[0], v[1], v[2], v[3]);
                 else
                     *reinterpret_cast<uint2 *>((unsigned char *)g.out + (m * g.ldc + on) * 2) = pk;
@@ -1795,7 +1795,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
         return;
     }
     if constexpr (CS) {
-        // ---- lean epilogue + channel partials (the CS epilogue of k_gemm8, same arithmetic and layout).  EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
+        // ---- lean epilogue + channel partials: a COPY of the CS epilogue of k_gemm8, same arithmetic and layout -- a fix to one is a fix to both.
+        // (Still a copy: as __forceinline__ functions shared by the kernels, this block, the k-slice store and the full epilogue compile to other
+        // code than the same text in the kernel body -- the optimiser simplifies a callee before it inlines it, where GemmArgs is a reference the
+        // stores may alias: +3 .. +420 instructions, other SGPR / scratch figures; with GemmArgs passed by value still +3 .. +24.)  EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
         // absent operands read the zero page), then the tile is computed and stored.  The generic epilogue loads bias / row-vector /
         // residual under per-lane branches inside the m loop: at every control-flow join hipcc falls back to s_waitcnt vmcnt(0), and on
         // gfx9 that counter also holds the STORES in flight -- MT x NTW serialised store round trips per wave (seen in the ISA).
@@ -2170,6 +2173,17 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue_cs(const GemmArgs g)
 
 inline bool fuse_of(const GemmArgs &g) { return g.row_stats || g.out_row_stats || g.out_group_stats; }
 
+// The wave tile of the 8-wave kernels as template arguments: f(integral_constant NTW, integral_constant MT) for the run-time ntw (5, else 4) and
+// mt (4, 3, else 2).  What a dispatcher launches outside this grid (MT = 1, the persistent kernel) it returns for before it comes here.
+template <class F>
+void with_wave_tile(int ntw, int mt, F &&f)
+{
+    const auto with_mt = [&](auto ntw_) {
+        if (mt == 4) f(ntw_, std::integral_constant<int, 4>{}); else if (mt == 3) f(ntw_, std::integral_constant<int, 3>{}); else f(ntw_, std::integral_constant<int, 2>{});
+    };
+    if (ntw == 5) with_mt(std::integral_constant<int, 5>{}); else with_mt(std::integral_constant<int, 4>{});
+}
+
 // ---- launch templates: instantiated with FUSE = false in dn_gemm_plain.hip and FUSE = true in dn_gemm_fuse.hip (one translation
 // unit each: the kernel templates are large and the two halves compile in parallel)
 template <class T, int MODE, int NTW, bool FUSE>
@@ -2216,12 +2230,7 @@ void dispatch8ln(const GemmArgs &g, int lnv, bool lean, int ntw, int mt, dim3 gr
 {
     if (lnv == 2 && g.persist > 0 && ntw == 4 && mt == 4) { launch8p<T, 4, 4, 2>(g, g.persist, s); return; }
     if (mt == 1 && ntw == 4) { dispatch8ln_m<T, 4, 1>(g, lnv, lean, grid, s); return; }
-    if (mt < 2) mt = 2;
-    if (ntw == 5) {
-        if (mt == 4) dispatch8ln_m<T, 5, 4>(g, lnv, lean, grid, s); else if (mt == 3) dispatch8ln_m<T, 5, 3>(g, lnv, lean, grid, s); else dispatch8ln_m<T, 5, 2>(g, lnv, lean, grid, s);
-    } else {
-        if (mt == 4) dispatch8ln_m<T, 4, 4>(g, lnv, lean, grid, s); else if (mt == 3) dispatch8ln_m<T, 4, 3>(g, lnv, lean, grid, s); else dispatch8ln_m<T, 4, 2>(g, lnv, lean, grid, s);
-    }
+    with_wave_tile(ntw, mt, [&](auto ntw_, auto mt_) { dispatch8ln_m<T, decltype(ntw_)::value, decltype(mt_)::value>(g, lnv, lean, grid, s); });
 }
 
 // lean epilogue (no GEGLU / activation / fp32 / transposed output): fast conv, upsample-fused conv, K % 64 == 0 linear
@@ -2241,12 +2250,7 @@ template <class T>
 void dispatch8lean(const GemmArgs &g, int mode, int ntw, int mt, dim3 grid, hipStream_t s)
 {
     if (mt == 1 && ntw == 4 && mode == 0) { launch8<T, 3, 4, 1, false, false, true>(g, grid, s); return; }
-    if (mt < 2) mt = 2;
-    if (ntw == 5) {
-        if (mt == 4) dispatch8lean_m<T, 5, 4>(g, mode, grid, s); else if (mt == 3) dispatch8lean_m<T, 5, 3>(g, mode, grid, s); else dispatch8lean_m<T, 5, 2>(g, mode, grid, s);
-    } else {
-        if (mt == 4) dispatch8lean_m<T, 4, 4>(g, mode, grid, s); else if (mt == 3) dispatch8lean_m<T, 4, 3>(g, mode, grid, s); else dispatch8lean_m<T, 4, 2>(g, mode, grid, s);
-    }
+    with_wave_tile(ntw, mt, [&](auto ntw_, auto mt_) { dispatch8lean_m<T, decltype(ntw_)::value, decltype(mt_)::value>(g, mode, grid, s); });
 }
 
 // channel-partial epilogue (CS): the modes whose output feeds a GroupNorm -- generic conv (conv_in), fast conv, K % 64 == 0 linear (proj_out)
@@ -2260,12 +2264,7 @@ void dispatch8cs_m(const GemmArgs &g, int mode, dim3 grid, hipStream_t s)
 template <class T>
 void dispatch8cs(const GemmArgs &g, int mode, int ntw, int mt, dim3 grid, hipStream_t s)
 {
-    if (mt < 2) mt = 2;
-    if (ntw == 5) {
-        if (mt == 4) dispatch8cs_m<T, 5, 4>(g, mode, grid, s); else if (mt == 3) dispatch8cs_m<T, 5, 3>(g, mode, grid, s); else dispatch8cs_m<T, 5, 2>(g, mode, grid, s);
-    } else {
-        if (mt == 4) dispatch8cs_m<T, 4, 4>(g, mode, grid, s); else if (mt == 3) dispatch8cs_m<T, 4, 3>(g, mode, grid, s); else dispatch8cs_m<T, 4, 2>(g, mode, grid, s);
-    }
+    with_wave_tile(ntw, mt, [&](auto ntw_, auto mt_) { dispatch8cs_m<T, decltype(ntw_)::value, decltype(mt_)::value>(g, mode, grid, s); });
 }
 
 template <class T, int NTW, int MT, bool FUSE>
@@ -2290,12 +2289,7 @@ void dispatch8(const GemmArgs &g, int mode, int ntw, int mt, dim3 grid, hipStrea
         if (mt == 1 && ntw == 4 && mode == 0 && g.K % 64 == 0) { launch8<T, 3, 4, 1, false>(g, grid, s); return; }
         if (g.persist > 0 && ntw == 4 && mt == 4 && mode == 0) { launch8p<T, 4, 4>(g, g.persist, s); return; }
     }
-    if (mt < 2) mt = 2;
-    if (ntw == 5) {
-        if (mt == 4) dispatch8m<T, 5, 4, FUSE>(g, mode, grid, s); else if (mt == 3) dispatch8m<T, 5, 3, FUSE>(g, mode, grid, s); else dispatch8m<T, 5, 2, FUSE>(g, mode, grid, s);
-    } else {
-        if (mt == 4) dispatch8m<T, 4, 4, FUSE>(g, mode, grid, s); else if (mt == 3) dispatch8m<T, 4, 3, FUSE>(g, mode, grid, s); else dispatch8m<T, 4, 2, FUSE>(g, mode, grid, s);
-    }
+    with_wave_tile(ntw, mt, [&](auto ntw_, auto mt_) { dispatch8m<T, decltype(ntw_)::value, decltype(mt_)::value, FUSE>(g, mode, grid, s); });
 }
 
 template <class T, bool FUSE>
