@@ -13,6 +13,8 @@
 // sweep (extra channel).  Backward replays the list back-to-front starting at the workgroup's
 // largest final_index (not at the end of the tile list), reduces the nine per-splat partials over
 // the 64 lanes with DPP row operations and issues one hardware float atomic per value per wave.
+#include <type_traits>
+
 #include "raster_tile.h"
 
 namespace {
@@ -131,6 +133,16 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_fwd(int H, int W, int tiles
 // of every row picks value c, two lane-swap steps add the four rows, and lanes 0..8 add their value into a per-batch LDS accumulator
 // (ONE ds_add_f32 instruction).  After a batch the staging lane of each splat flushes nine hardware float atomics -- once per
 // (tile, splat) instead of once per (block, splat), issued by 256 lanes at a time.
+//
+// HAS_DEPTH (gc_rasterize_bwd_depth_views): the forward's `extra` value is a fourth composited channel with background 0 -- E = sum e_i
+// alpha_i T_i -- that the rgb clamp does not touch, and the backward of the finalize epilogue (depth = E / alpha_px, 1000 where alpha_px = 0)
+// is folded into the pixel load like the clamp's: vE = v_depth / alpha_px, voa += -v_depth * depth / alpha_px; the sentinel carries no
+// gradient.  Per (pixel, splat): g_e = fac * vE, v_alpha += (e_i T - S3 ra) vE, S3 += e_i fac.  A tenth partial rides the same reduction
+// (lane column 9), the staged blue value becomes the forward's SplatC{b, e}.  <false> is the kernel without any of it.
+struct DepthIO { const float *extra, *depth, *v_depth; float *v_extra; };      // [C][N], [C][H][W], [C][H][W]; [C][N] zero on entry
+struct NoDepthIO {};
+
+template <bool HAS_DEPTH>
 __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles_x,
                                                          const int32_t *__restrict__ ids_sorted,
                                                          const int32_t *__restrict__ tile_bins,
@@ -141,8 +153,10 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                                                          const float *__restrict__ v_out, const float *__restrict__ v_out_alpha,
                                                          const float *__restrict__ pre_clamp,
                                                          float *__restrict__ v_xy, float *__restrict__ v_conic,
-                                                         float *__restrict__ v_colors, float *__restrict__ v_opacity, CV cv)
+                                                         float *__restrict__ v_colors, float *__restrict__ v_opacity, CV cv,
+                                                         std::conditional_t<HAS_DEPTH, DepthIO, NoDepthIO> dz)
 {
+    constexpr int NP = HAS_DEPTH ? 10 : 9;                              // partials per splat
     {
         const int64_t v = blockIdx.z, hw = (int64_t)H * W;
         ids_sorted += v * cv.m; tile_bins += v * 2 * cv.tiles; xys += v * 2 * cv.n; conics += v * 3 * cv.n; colors += v * 3 * cv.n;
@@ -151,11 +165,12 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
         if (v_out_alpha) v_out_alpha += v * hw;
         if (pre_clamp) pre_clamp += v * 3 * hw;
         v_xy += v * 2 * cv.n; v_conic += v * 3 * cv.n; v_colors += v * 3 * cv.n; v_opacity += v * cv.n;
+        if constexpr (HAS_DEPTH) { dz.extra += v * cv.n; dz.depth += v * hw; dz.v_depth += v * hw; dz.v_extra += v * cv.n; }
     }
     __shared__ SplatA sA[BLOCK];
     __shared__ SplatB sB[BLOCK];
-    __shared__ float sBlue[BLOCK];
-    __shared__ float sG[BLOCK * 9];
+    __shared__ std::conditional_t<HAS_DEPTH, SplatC, float> sBlue[BLOCK];
+    __shared__ float sG[BLOCK * NP];
     __shared__ unsigned char sMask[BLOCK];
     __shared__ int sMax[4];
     const int tile = blockIdx.y * tiles_x + blockIdx.x;
@@ -179,6 +194,15 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
         }
         if (v_out_alpha) voa = v_out_alpha[pix];
     }
+    float vE = 0.f, S3 = 0.f;
+    if constexpr (HAS_DEPTH) {
+        const float alpha_px = 1.f - T_final;                           // as gc_raster_finalize formed it
+        if (inside && alpha_px > 0.f) {
+            const float vd = dz.v_depth[pix];
+            vE = vd / alpha_px;
+            voa += -vd * dz.depth[pix] / alpha_px;
+        }
+    }
     const float bgdot = background[0] * vo0 + background[1] * vo1 + background[2] * vo2;
     float S0 = 0.f, S1 = 0.f, S2 = 0.f;
     // wave / workgroup maxima of final_index: nothing beyond them was composited
@@ -188,7 +212,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
     wmax = __builtin_amdgcn_readfirstlane(wmax);                       // wave-uniform: keeps the splat walk below in scalar registers
     if (lane == 0) sMax[wid] = wmax;
 #pragma unroll
-    for (int q = 0; q < 9; ++q) sG[q * BLOCK + tid] = 0.f;
+    for (int q = 0; q < NP; ++q) sG[q * BLOCK + tid] = 0.f;
     __syncthreads();
     const int kmax = __builtin_amdgcn_readfirstlane(max(max(sMax[0], sMax[1]), max(sMax[2], sMax[3])));
     if (kmax < start) return;
@@ -203,7 +227,8 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
             const float op = opacities[gid], c0 = conics[3 * gid], c1 = conics[3 * gid + 1], c2 = conics[3 * gid + 2];
             sA[tid] = {xy.x, xy.y, op, c0};
             sB[tid] = {c1, c2, colors[3 * gid], colors[3 * gid + 1]};
-            sBlue[tid] = colors[3 * gid + 2];
+            if constexpr (HAS_DEPTH) sBlue[tid] = {colors[3 * gid + 2], dz.extra[gid]};
+            else sBlue[tid] = colors[3 * gid + 2];
             mk = block_mask(xy.x, xy.y, op, c0, c1, c2, tx0, ty0);
         }
         sMask[tid] = (unsigned char)mk;
@@ -226,14 +251,21 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 const float alpha = fminf(ALPHA_CAP, araw);
                 const bool valid = (k <= bin_final) && !(sigma < 0.f || alpha < ALPHA_MIN);
                 if (!__any(valid)) continue;
-                float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_cxx = 0.f, g_cxy = 0.f, g_cyy = 0.f, g_x = 0.f, g_y = 0.f, g_o = 0.f;
+                float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_cxx = 0.f, g_cxy = 0.f, g_cyy = 0.f, g_x = 0.f, g_y = 0.f, g_o = 0.f, g_e = 0.f;
                 if (valid) {
                     const float ra = __builtin_amdgcn_rcpf(1.f - alpha);      // 1-ulp reciprocal: alpha <= 0.999, the IEEE division sequence is 10 instructions
                     T *= ra;
                     const float fac = alpha * T;
                     g_r = fac * vo0; g_g = fac * vo1; g_b = fac * vo2;
-                    const float cb = sBlue[t];
+                    float cb, ce = 0.f;
+                    if constexpr (HAS_DEPTH) { const SplatC cc = sBlue[t]; cb = cc.b; ce = cc.e; }
+                    else cb = sBlue[t];
                     float v_alpha = (bb.r * T - S0 * ra) * vo0 + (bb.g * T - S1 * ra) * vo1 + (cb * T - S2 * ra) * vo2;
+                    if constexpr (HAS_DEPTH) {
+                        g_e = fac * vE;
+                        v_alpha += (ce * T - S3 * ra) * vE;
+                        S3 += ce * fac;
+                    }
                     v_alpha += T_final * ra * voa;
                     v_alpha += -T_final * ra * bgdot;
                     S0 += bb.r * fac; S1 += bb.g * fac; S2 += cb * fac;
@@ -253,18 +285,19 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 float x = g_r;                                          // lane column c keeps value c
                 x = col == 1 ? g_g : x; x = col == 2 ? g_b : x; x = col == 3 ? g_cxx : x; x = col == 4 ? g_cxy : x;
                 x = col == 5 ? g_cyy : x; x = col == 6 ? g_x : x; x = col == 7 ? g_y : x; x = col == 8 ? g_o : x;
+                if constexpr (HAS_DEPTH) { g_e = row_sum(g_e); x = col == 9 ? g_e : x; }
                 x = xor_rows_sum(x);
-                if (lane < 9) __hip_atomic_fetch_add(&sG[lane * BLOCK + t], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane < NP) __hip_atomic_fetch_add(&sG[lane * BLOCK + t], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
         __syncthreads();
-        if (gid >= 0) {                                                 // flush: nine atomics per (tile, splat) that was touched at all
-            float v[9];
+        if (gid >= 0) {                                                 // flush: nine (ten) atomics per (tile, splat) that was touched at all
+            float v[NP];
 #pragma unroll
-            for (int q = 0; q < 9; ++q) { v[q] = sG[q * BLOCK + tid]; sG[q * BLOCK + tid] = 0.f; }
+            for (int q = 0; q < NP; ++q) { v[q] = sG[q * BLOCK + tid]; sG[q * BLOCK + tid] = 0.f; }
             bool any = false;
 #pragma unroll
-            for (int q = 0; q < 9; ++q) any |= v[q] != 0.f;
+            for (int q = 0; q < NP; ++q) any |= v[q] != 0.f;
             if (any) {
                 unsafeAtomicAdd(v_colors + 3 * gid, v[0]);
                 unsafeAtomicAdd(v_colors + 3 * gid + 1, v[1]);
@@ -275,6 +308,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 unsafeAtomicAdd(v_xy + 2 * gid, v[6]);
                 unsafeAtomicAdd(v_xy + 2 * gid + 1, v[7]);
                 unsafeAtomicAdd(v_opacity + gid, v[8]);
+                if constexpr (HAS_DEPTH) unsafeAtomicAdd(dz.v_extra + gid, v[9]);
             }
         }
         // the next staging pass overwrites sA / sB / sMask: every wave has left the loop (barrier above); sG slots are private to
@@ -334,16 +368,21 @@ static int rasterize_bwd_impl(const char *what, int C, int64_t N, int64_t M_cap,
                               const int32_t *tile_bins, const float *xys, const float *conics, const float *colors,
                               const float *opacities, const float *background, const float *final_Ts, const int32_t *final_index,
                               const float *v_out, const float *v_out_alpha, const float *pre_clamp, float *v_xy, float *v_conic,
-                              float *v_colors, float *v_opacity, void *stream)
+                              float *v_colors, float *v_opacity, void *stream, const DepthIO *dz = nullptr)
 {
     if (!(img_h > 0 && img_w > 0 && tiles_x == (img_w + TILE - 1) / TILE && tiles_y == (img_h + TILE - 1) / TILE)) {
         gc::set_error("%s: tile bounds do not match the image size", what); return GC_EINVAL;
     }
     CV cv; cv.n = N; cv.n_op = shared_opacities ? 0 : N; cv.m = M_cap; cv.tiles = tiles_x * tiles_y; cv.bg = shared_background ? 0 : 3;
     dim3 grid(tiles_x, tiles_y, C), block(BLOCK);
-    hipLaunchKernelGGL(k_rasterize_bwd, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins,
-                       xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic,
-                       v_colors, v_opacity, cv);
+    if (dz)
+        hipLaunchKernelGGL(k_rasterize_bwd<true>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins,
+                           xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic,
+                           v_colors, v_opacity, cv, *dz);
+    else
+        hipLaunchKernelGGL(k_rasterize_bwd<false>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins,
+                           xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic,
+                           v_colors, v_opacity, cv, NoDepthIO{});
     return gc::check_launch(what);
 }
 
@@ -382,6 +421,24 @@ int gc_rasterize_bwd_views(int C, int64_t N, int64_t M_cap, int shared_opacities
     return rasterize_bwd_impl("gc_rasterize_bwd_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
                               gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
                               pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream);
+}
+
+/* gc_rasterize_bwd_views with the depth channel differentiable (k_rasterize_bwd<true>): extra [C][N] = what the forward composited, depth
+ * [C][H][W] = the FINALIZED image (E / alpha, 1000 where alpha == 0), v_depth [C][H][W] its gradient; v_extra [C][N] ZERO on entry like the
+ * other four outputs.  C = 1 is the single-view case (M_cap is then not read). */
+int gc_rasterize_bwd_depth_views(int C, int64_t N, int64_t M_cap, int shared_opacities, int shared_background, int img_h, int img_w, int tiles_x,
+                                 int tiles_y, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys, const float *conics,
+                                 const float *colors, const float *opacities, const float *background, const float *final_Ts,
+                                 const int32_t *final_index, const float *v_out, const float *v_out_alpha, const float *pre_clamp, float *v_xy,
+                                 float *v_conic, float *v_colors, float *v_opacity, const float *extra, const float *depth, const float *v_depth,
+                                 float *v_extra, void *stream)
+{
+    GC_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && M_cap >= 0, "bad arguments");
+    GC_REQUIRE(extra && depth && v_depth && v_extra, "extra, depth, v_depth and v_extra are required (gc_rasterize_bwd_views is the form without depth)");
+    const DepthIO dz{extra, depth, v_depth, v_extra};
+    return rasterize_bwd_impl("gc_rasterize_bwd_depth_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
+                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
+                              pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream, &dz);
 }
 
 }  // extern "C"

@@ -450,7 +450,9 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int 
 // LDS and written with 16-byte-per-lane stores (a lane-strided 45-float store has the same 64-lines-per-instruction problem).
 // ACC: the six outputs are accumulated into (+=) instead of written -- gradient accumulation over the views of a batch without a
 // separate read-add-write pass per tensor (the caller owns zeroing / the first view runs with ACC = false).
-template <int K, bool ACC>
+// DEPTH (gc_project_sh_bwd_depth_views): v_depths [N] feeds project_one_bwd's depth argument (depth = row 2 of the view matrix applied to
+// the mean); without it the argument is the literal 0 it always was.
+template <int K, bool ACC, bool DEPTH = false>
 __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int n_use,
                                                         const float *__restrict__ means, const float *__restrict__ log_scales,
                                                         const float *__restrict__ quats, const float *__restrict__ op_logit,
@@ -460,7 +462,8 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int 
                                                         const float *__restrict__ v_rgbs, const float *__restrict__ v_opac,
                                                         float *__restrict__ v_means, float *__restrict__ v_ls,
                                                         float *__restrict__ v_quats, float *__restrict__ v_oplogit,
-                                                        float *__restrict__ v_dc, float *__restrict__ v_rest)
+                                                        float *__restrict__ v_dc, float *__restrict__ v_rest,
+                                                        const float *__restrict__ v_depths)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float svr[R > 0 ? 256 * R : 4];
@@ -487,7 +490,7 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int 
             float q0 = qr.x / qn, q1 = qr.y / qn, q2 = qr.z / qn, q3 = qr.w / qn;
             ProjGrad g;
             project_one_bwd(cam, p0, p1, p2, s0, s1, s2, q0, q1, q2, q3, conics[3 * i], conics[3 * i + 1], conics[3 * i + 2],
-                            v_xy[2 * i], v_xy[2 * i + 1], 0.f, v_conic[3 * i], v_conic[3 * i + 1], v_conic[3 * i + 2], g);
+                            v_xy[2 * i], v_xy[2 * i + 1], DEPTH ? v_depths[i] : 0.f, v_conic[3 * i], v_conic[3 * i + 1], v_conic[3 * i + 2], g);
             put(v_means + 3 * i, g.vm[0]); put(v_means + 3 * i + 1, g.vm[1]); put(v_means + 3 * i + 2, g.vm[2]);
             put(v_ls + 3 * i, g.vs[0] * s0); put(v_ls + 3 * i + 1, g.vs[1] * s1); put(v_ls + 3 * i + 2, g.vs[2] * s2);
             // outer normalisation q/|q| (gc_model.py:144)
@@ -623,7 +626,7 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatc
 // Backward over C views: the parameter record is read once, the per-view VJPs (same device functions as the single-view kernel) are summed
 // in registers IN VIEW ORDER -- ((g_0 + g_1) + g_2) ..., the order C accumulating single-view launches produce -- and the 59 gradient floats
 // are written (or, ACC, added to what is there) ONCE per batch: N * (56 + C * 64) bytes read + N * 236 written instead of C * N * 344.
-template <int K, bool ACC>
+template <int K, bool ACC, bool DEPTH = false>
 __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatch cb, int n_use,
                                                               const float *__restrict__ means, const float *__restrict__ log_scales,
                                                               const float *__restrict__ quats, const float *__restrict__ op_logit,
@@ -633,7 +636,8 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatc
                                                               const float *__restrict__ v_rgbs, const float *__restrict__ v_opac,
                                                               float *__restrict__ v_means, float *__restrict__ v_ls,
                                                               float *__restrict__ v_quats, float *__restrict__ v_oplogit,
-                                                              float *__restrict__ v_dc, float *__restrict__ v_rest)
+                                                              float *__restrict__ v_dc, float *__restrict__ v_rest,
+                                                              const float *__restrict__ v_depths /* [C][N], DEPTH only */)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float svr[R > 0 ? 256 * R : 4];
@@ -660,7 +664,7 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatc
             const Cam &cam = cb.cam[v];
             ProjGrad g;
             project_one_bwd(cam, p0, p1, p2, s0, s1, s2, q0, q1, q2, q3, conics[3 * o], conics[3 * o + 1], conics[3 * o + 2],
-                            v_xy[2 * o], v_xy[2 * o + 1], 0.f, v_conic[3 * o], v_conic[3 * o + 1], v_conic[3 * o + 2], g);
+                            v_xy[2 * o], v_xy[2 * o + 1], DEPTH ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1], v_conic[3 * o + 2], g);
             const float dq = q0 * g.vq[0] + q1 * g.vq[1] + q2 * g.vq[2] + q3 * g.vq[3];
             const float gq[4] = {(g.vq[0] - q0 * dq) / qn, (g.vq[1] - q1 * dq) / qn, (g.vq[2] - q2 * dq) / qn, (g.vq[3] - q3 * dq) / qn};
             const float gls[3] = {g.vs[0] * s0, g.vs[1] * s1, g.vs[2] * s2};
@@ -870,7 +874,7 @@ int gc_project_sh_fwd_boxes(int64_t N, const float *means, const float *log_scal
                                num_tiles_hit, rgbs, opac, tile_boxes, stream);
 }
 
-static int project_sh_bwd_impl(bool accumulate, int64_t N, const float *means, const float *log_scales, const float *quats,
+static int project_sh_bwd_impl(const char *what, bool accumulate, const float *v_depths, int64_t N, const float *means, const float *log_scales, const float *quats,
                       const float *opacity_logits, const float *rgbs,
                       int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
                       const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
@@ -882,14 +886,17 @@ static int project_sh_bwd_impl(bool accumulate, int64_t N, const float *means, c
     GC_REQUIRE(viewmat && projmat && cam_origin, "camera pointers are host pointers and must not be NULL");
     if (N == 0) return GC_OK;
     Cam cam = make_cam(viewmat, projmat, fx, fy, cx, cy, img_h, img_w, 0, 0, 0.f, 1.f, cam_origin);
+#define GC_BWD_L(KK, ACC, DEPTH) hipLaunchKernelGGL((k_project_sh_bwd<KK, ACC, DEPTH>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWD_ARGS)
 #define GC_BWD_K(KK) \
-    do { if (accumulate) hipLaunchKernelGGL((k_project_sh_bwd<KK, true>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWD_ARGS); \
-         else hipLaunchKernelGGL((k_project_sh_bwd<KK, false>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWD_ARGS); } while (0)
-#define GC_BWD_ARGS N, cam, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest
+    do { if (v_depths) { if (accumulate) GC_BWD_L(KK, true, true); else GC_BWD_L(KK, false, true); } \
+         else if (accumulate) GC_BWD_L(KK, true, false); \
+         else GC_BWD_L(KK, false, false); } while (0)
+#define GC_BWD_ARGS N, cam, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths
     switch (sh_degree) { case 0: GC_BWD_K(1); break; case 1: GC_BWD_K(4); break; case 2: GC_BWD_K(9); break; default: GC_BWD_K(16); break; }
 #undef GC_BWD_K
+#undef GC_BWD_L
 #undef GC_BWD_ARGS
-    return gc::check_launch("gc_project_sh_bwd");
+    return gc::check_launch(what);
 }
 
 int gc_project_sh_bwd(int64_t N, const float *means, const float *log_scales, const float *quats,
@@ -900,7 +907,7 @@ int gc_project_sh_bwd(int64_t N, const float *means, const float *log_scales, co
                       const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
                       float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
 {
-    return project_sh_bwd_impl(false, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    return project_sh_bwd_impl("gc_project_sh_bwd", false, nullptr, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
 }
 
 /* Same, but the six outputs are ACCUMULATED into (+=): gradient accumulation over the views of a batch inside the kernel. */
@@ -912,7 +919,7 @@ int gc_project_sh_bwd_accumulate(int64_t N, const float *means, const float *log
                       const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
                       float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
 {
-    return project_sh_bwd_impl(true, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    return project_sh_bwd_impl("gc_project_sh_bwd", true, nullptr, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
 }
 
 /* ---- C views per launch (round 5).  cams: HOST float array [C][GC_VIEW_CAM_FLOATS = 35] = viewmat[12] | projmat[16] | cam_origin[3] |
@@ -950,9 +957,8 @@ int gc_project_sh_fwd_views(int64_t N, int C, const float *means, const float *l
     return gc::check_launch("gc_project_sh_fwd_views");
 }
 
-/* Backward over C views: rgbs / radii / conics / v_xy / v_conic / v_rgbs / v_opac are [C][N][..]; the six leaf gradients are the SUM over
- * the views, written (accumulate = 0) or added to the buffers' contents (accumulate = 1) once per group of 8 views. */
-int gc_project_sh_bwd_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
+static int project_sh_bwd_views_impl(const char *what, const float *v_depths, int64_t N, int C, int accumulate, const float *means,
+                                     const float *log_scales, const float *quats,
                             const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
                             int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
                             const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
@@ -966,15 +972,51 @@ int gc_project_sh_bwd_views(int64_t N, int C, int accumulate, const float *means
         fill_cams(cb, cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, 0, 0, 0.f);
         const size_t o = (size_t)v0 * (size_t)N;
         const bool acc = accumulate || v0 > 0;
-#define GC_BWDV_ARGS N, cb, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs + 3 * o, radii + o, conics + 3 * o, v_xy + 2 * o, v_conic + 3 * o, v_rgbs + 3 * o, v_opac + o, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest
+#define GC_BWDV_ARGS N, cb, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs + 3 * o, radii + o, conics + 3 * o, v_xy + 2 * o, v_conic + 3 * o, v_rgbs + 3 * o, v_opac + o, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths ? v_depths + o : nullptr
+#define GC_BWDV_L(KK, ACC, DEPTH) hipLaunchKernelGGL((k_project_sh_bwd_views<KK, ACC, DEPTH>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWDV_ARGS)
 #define GC_BWDV_K(KK) \
-        do { if (acc) hipLaunchKernelGGL((k_project_sh_bwd_views<KK, true>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWDV_ARGS); \
-             else hipLaunchKernelGGL((k_project_sh_bwd_views<KK, false>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWDV_ARGS); } while (0)
+        do { if (v_depths) { if (acc) GC_BWDV_L(KK, true, true); else GC_BWDV_L(KK, false, true); } \
+             else if (acc) GC_BWDV_L(KK, true, false); \
+             else GC_BWDV_L(KK, false, false); } while (0)
         switch (sh_degree) { case 0: GC_BWDV_K(1); break; case 1: GC_BWDV_K(4); break; case 2: GC_BWDV_K(9); break; default: GC_BWDV_K(16); break; }
 #undef GC_BWDV_K
+#undef GC_BWDV_L
 #undef GC_BWDV_ARGS
     }
-    return gc::check_launch("gc_project_sh_bwd_views");
+    return gc::check_launch(what);
+}
+
+/* Backward over C views: rgbs / radii / conics / v_xy / v_conic / v_rgbs / v_opac are [C][N][..]; the six leaf gradients are the SUM over
+ * the views, written (accumulate = 0) or added to the buffers' contents (accumulate = 1) once per group of 8 views. */
+int gc_project_sh_bwd_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
+                            const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
+                            int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
+                            const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
+                            float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
+{
+    return project_sh_bwd_views_impl("gc_project_sh_bwd_views", nullptr, N, C, accumulate, means, log_scales, quats, opacity_logits, rgbs, sh_degree,
+                                     degrees_to_use, cams, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats,
+                                     v_opacity_logits, v_features_dc, v_features_rest, stream);
+}
+
+/* The same with a gradient on the projected depths: v_depths [C][N] (the v_extra of gc_rasterize_bwd_depth_views) enters each view's VJP as
+ * d depth / d mean = row 2 of that view's matrix; a culled Gaussian (radii == 0) contributes nothing.  C = 1 runs the single-view kernel. */
+int gc_project_sh_bwd_depth_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
+                                  const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
+                                  int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
+                                  const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
+                                  float *v_opacity_logits, float *v_features_dc, float *v_features_rest, const float *v_depths, void *stream)
+{
+    GC_REQUIRE(v_depths, "v_depths is required (gc_project_sh_bwd_views is the form without it)");
+    if (C == 1 && cams) {
+        const float *c = cams;
+        return project_sh_bwd_impl("gc_project_sh_bwd_depth_views", accumulate != 0, v_depths, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree,
+                                   degrees_to_use, c, c + 12, c + 28, c[31], c[32], c[33], c[34], img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+                                   v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    }
+    return project_sh_bwd_views_impl("gc_project_sh_bwd_depth_views", v_depths, N, C, accumulate, means, log_scales, quats, opacity_logits, rgbs,
+                                     sh_degree, degrees_to_use, cams, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means,
+                                     v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
 }
 
 int gc_raster_finalize(int64_t num_pixels, float *out_img, float *out_extra, const float *final_Ts, float *alpha,

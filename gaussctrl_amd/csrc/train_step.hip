@@ -178,6 +178,67 @@ __global__ __launch_bounds__(256) void k_adam(float *__restrict__ p, const float
     }
 }
 
+// Depth L1 (gc_depth_l1_fwd_bwd_views): mean |pred - target| over the pixels where both depths are real -- neither is the 1000 sentinel
+// gc_raster_finalize writes where alpha == 0, both are finite.  Two small streaming kernels; the valid count never leaves the device:
+// k_depth_l1_reduce leaves (sum, count) per workgroup, k_depth_l1_grad folds a view's partials (<= DL1_MAXB, one wave, fixed order:
+// the result does not depend on scheduling) and writes sign(pred - target) * grad_scale / max(count, 1).
+constexpr int DL1_MAXB = 64;            // workgroups per view in the reduce pass
+constexpr float DEPTH_SENTINEL = 1000.f;
+
+__device__ __forceinline__ bool depth_l1_valid(float p, float t)
+{
+    return p != DEPTH_SENTINEL && t != DEPTH_SENTINEL && fabsf(p) < INFINITY && fabsf(t) < INFINITY;     // (NaN compares false)
+}
+
+__global__ __launch_bounds__(256) void k_depth_l1_reduce(const float *__restrict__ pred, const float *__restrict__ target, int64_t hw,
+                                                         float *__restrict__ part_sum, uint32_t *__restrict__ part_cnt)
+{
+    __shared__ float rs[4];
+    __shared__ uint32_t rc[4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    pred += (size_t)b * hw; target += (size_t)b * hw;
+    float s = 0.f;
+    uint32_t c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < hw; i += (int64_t)gridDim.x * 256) {
+        const float p = pred[i], t = target[i];
+        if (depth_l1_valid(p, t)) { s += fabsf(p - t); c += 1; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { s += __shfl_xor(s, d, 64); c += __shfl_xor(c, d, 64); }
+    if ((tid & 63) == 0) { rs[tid >> 6] = s; rc[tid >> 6] = c; }
+    __syncthreads();
+    if (tid == 0) {
+        part_sum[b * DL1_MAXB + blockIdx.x] = (rs[0] + rs[1]) + (rs[2] + rs[3]);
+        part_cnt[b * DL1_MAXB + blockIdx.x] = (rc[0] + rc[1]) + (rc[2] + rc[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_depth_l1_grad(const float *__restrict__ pred, const float *__restrict__ target, int64_t hw, int nblk,
+                                                       const float *__restrict__ part_sum, const uint32_t *__restrict__ part_cnt,
+                                                       float grad_scale, float *__restrict__ loss_out, float *__restrict__ v_pred)
+{
+    __shared__ float s_inv;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    pred += (size_t)b * hw; target += (size_t)b * hw; v_pred += (size_t)b * hw;
+    if (tid < 64) {                                        // nblk <= DL1_MAXB = 64 partials: one wave
+        float s = tid < nblk ? part_sum[b * DL1_MAXB + tid] : 0.f;
+        uint32_t c = tid < nblk ? part_cnt[b * DL1_MAXB + tid] : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { s += __shfl_xor(s, d, 64); c += __shfl_xor(c, d, 64); }
+        if (tid == 0) {
+            s_inv = grad_scale / (float)(c > 0u ? c : 1u);
+            if (blockIdx.x == 0) { loss_out[2 * b] = s; loss_out[2 * b + 1] = (float)c; }
+        }
+    }
+    __syncthreads();
+    const float inv = s_inv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < hw; i += (int64_t)gridDim.x * 256) {
+        const float p = pred[i], t = target[i];
+        const float sgn = p > t ? 1.f : (p < t ? -1.f : 0.f);
+        v_pred[i] = depth_l1_valid(p, t) ? sgn * inv : 0.f;
+    }
+}
+
 Gauss make_window()
 {
     Gauss gw;
@@ -240,6 +301,32 @@ int gc_l1_ssim_fwd_bwd_views(int B, const float *pred, const float *target, int 
     if (workspace_bytes < gc_l1_ssim_views_workspace_bytes(B, H, W, C)) { gc::set_error("gc_l1_ssim_fwd_bwd_views: workspace too small"); return GC_ENOSPC; }
     return l1_ssim_impl("gc_l1_ssim_fwd_bwd_views", B, pred, target, H, W, C, lambda_, grad_scale, valid_window, loss_out, v_pred, workspace,
                         workspace_bytes, stream);
+}
+
+/* Depth L1 of B views: pred / target / v_pred [B][H][W].  A pixel is valid when neither value is the 1000 sentinel and both are finite.
+ * loss_out [B][2] = {sum |pred - target| over the valid pixels, their count} (the caller forms sum / max(count, 1): no host sync here);
+ * v_pred = grad_scale * sign(pred - target) / max(count, 1) on valid pixels (sign(0) = 0), 0 elsewhere. */
+size_t gc_depth_l1_views_workspace_bytes(int B, int H, int W)
+{
+    (void)H; (void)W;
+    return (size_t)(B > 0 ? B : 1) * DL1_MAXB * (sizeof(float) + sizeof(uint32_t));
+}
+
+int gc_depth_l1_fwd_bwd_views(int B, const float *pred, const float *target, int H, int W, float grad_scale, float *loss_out, float *v_pred,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    GC_REQUIRE(B >= 1 && B <= 65535 && H > 0 && W > 0, "bad arguments");
+    GC_REQUIRE(pred && target && loss_out && v_pred && workspace, "null argument");
+    if (workspace_bytes < gc_depth_l1_views_workspace_bytes(B, H, W)) { gc::set_error("gc_depth_l1_fwd_bwd_views: workspace too small"); return GC_ENOSPC; }
+    const int64_t hw = (int64_t)H * W;
+    const int nblk = (int)std::min<int64_t>(DL1_MAXB, (hw + 2047) / 2048);           // ~8 pixels per lane
+    float *part_sum = (float *)workspace;
+    uint32_t *part_cnt = (uint32_t *)(part_sum + (size_t)B * DL1_MAXB);
+    hipStream_t s = gc::S(stream);
+    hipLaunchKernelGGL(k_depth_l1_reduce, dim3(nblk, B), dim3(256), 0, s, pred, target, hw, part_sum, part_cnt);
+    hipLaunchKernelGGL(k_depth_l1_grad, dim3((unsigned)std::min<int64_t>(1024, (hw + 1023) / 1024), B), dim3(256), 0, s, pred, target, hw, nblk,
+                       part_sum, part_cnt, grad_scale, loss_out, v_pred);
+    return gc::check_launch("gc_depth_l1_fwd_bwd_views");
 }
 
 /* torch.optim.Adam step (betas, eps as given; step = 1-based iteration count) on one flat fp32 tensor. */

@@ -51,6 +51,9 @@ class GaussCtrlModelConfig(_ModelConfigBase):
     use_l1: bool = True
     patch_size: int = 32
     lpips_loss_mult: float = 1.0
+    # --- addition of this implementation (the name later splatfacto versions use)
+    output_depth_during_training: bool = False    # True: get_outputs in training mode also returns "depth" [H,W,1], differentiable
+                                                  # (ops.RenderAux.depth_grad); False: no depth while training, as the reference
 
 
 class GaussCtrlModel(_ModelBase):
@@ -141,11 +144,14 @@ class GaussCtrlModel(_ModelBase):
             # the fused backward writes the six leaf gradients straight into the caller's buffers (dist.FlatGrads: ONE flat allocation that
             # RCCL reduces in place) and autograd gets None for them: GaussCtrlPipeline.train_iteration, train_mode "throughput"
             aux.grad_into, aux.grad_accumulate = self.grad_into, False
-        rgb, alpha, depth = ops.render_view(*p, cam, background, not self.training, n, aux)
+        train_depth = bool(self.training and getattr(self.config, "output_depth_during_training", False))
+        aux.depth_grad = train_depth
+        want_depth = train_depth or not self.training
+        rgb, alpha, depth = ops.render_view(*p, cam, background, want_depth, n, aux)
         self.xys, self.radii = aux.xys, aux.radii
         if aux.M == 0:                                                          # :155-156
             return {"rgb": background.repeat(H, W, 1)}
-        depth_im = None if self.training else depth[..., None]
+        depth_im = depth[..., None] if want_depth else None
         return {"rgb": rgb, "depth": depth_im, "accumulation": alpha[..., None]}
 
     forward = get_outputs

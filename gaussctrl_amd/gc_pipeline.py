@@ -91,6 +91,10 @@ class GaussCtrlPipelineConfig(_PipelineConfigBase):
     fold_layernorms: bool = True       # LayerNorms of the C = 640 / 1280 transformer blocks folded into their producer / consumer GEMM epilogues
                                        # (weights.prepare(fold_ln=2): +2 % views/s, same latents to the storage type's rounding); ignored with
                                        # fp8 >= 2, whose linears take e4m3 activations from the LayerNorm kernel
+    depth_loss_mult: float = 0.0       # > 0: depth supervision of the optimisation that follows the edit -- the training render also returns a
+                                       # differentiable depth (model.output_depth_during_training for the call) and loss_dict gains "depth_loss" =
+                                       # depth_loss_mult * L1(depth, the view's pre-edit depth_image of render_reverse) over the pixels where both
+                                       # hold a surface; 0: the loss dict of the reference (rgb only)
     synthetic_weights: bool = False    # True: seeded random SD1.5-shaped weights + hashed prompt embeddings (bench / tests; there
                                        # are no checkpoints on the build machines).  False: checkpoints are REQUIRED -- no silent fallback.
 
@@ -389,9 +393,26 @@ class GaussCtrlPipeline(_PipelineBase):
     # ------------------------------------------------------------------------------------ :276-291
     def get_train_loss_dict(self, step: int):
         camera, batch = self.datamanager.next_train(step)
-        model_outputs = self._model(camera)
+        depth_mult = float(getattr(self.config, "depth_loss_mult", 0.0))
+        if depth_mult > 0:
+            ref_depth = self.datamanager.train_data[batch["image_idx"]].get("depth_image")
+            if ref_depth is None:
+                raise RuntimeError(f"depth_loss_mult > 0: view {batch['image_idx']} has no stored depth_image (render_reverse or "
+                                   "load_mid_results fills it before training)")
+            mcfg = self._model.config
+            keep = getattr(mcfg, "output_depth_during_training", False)
+            mcfg.output_depth_during_training = True
+            try:
+                model_outputs = self._model(camera)
+            finally:
+                mcfg.output_depth_during_training = keep
+        else:
+            model_outputs = self._model(camera)
         metrics_dict = self._model.get_metrics_dict(model_outputs, batch)
         loss_dict = self._model.get_loss_dict(model_outputs, batch, metrics_dict)
+        if depth_mult > 0 and model_outputs.get("depth") is not None:      # (a view that meets no Gaussian renders no depth: nothing to add)
+            from .train_ops import depth_l1_loss
+            loss_dict["depth_loss"] = depth_mult * depth_l1_loss(model_outputs["depth"][..., 0], ref_depth)
         return model_outputs, loss_dict, metrics_dict          # (world_size > 1: the gradient reduction happens after backward, train_iteration)
 
     def reduce_gradients(self):

@@ -353,6 +353,13 @@ class RenderAux:
     # render_views (round 6): True = the gather-free depth order (gc_raster_order_boxes_views + gc_raster_bin_sorted_views: the packed boxes ride
     # through the radix passes, culled Gaussians drop out in the first pass); False = the round-5 chain (same lists bit for bit; A/B and cross-checks)
     sorted_boxes = True
+    # Depth supervision: True (with want_depth and parameters that require grad) makes the depth image differentiable -- the backward then
+    # runs gc_rasterize_bwd_depth_views / gc_project_sh_bwd_depth_views.  False: depth is marked non-differentiable, as it always was.
+    depth_grad = False
+
+
+def _depth_grad_on(ctx, aux, want_depth):
+    return bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
 
 
 class _RenderView(torch.autograd.Function):
@@ -409,24 +416,43 @@ class _RenderView(torch.autograd.Function):
             aux.tile_boxes = boxes
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
             aux.xys_grad = None
-        ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
+        ctx.depth_grad = _depth_grad_on(ctx, aux, want_depth)
+        if ctx.depth_grad:
+            ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
+            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp, depths, dep)
+        else:
+            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
         ctx.meta = (cam, tb, N, sh_degree, int(sh_degree_to_use), V, P, O)
         ctx.aux = aux
-        ctx.mark_non_differentiable(*( [dep] if dep is not None else []))
+        if not ctx.depth_grad:
+            ctx.mark_non_differentiable(*( [dep] if dep is not None else []))
         if dep is None:
             dep = torch.empty(0, device=dev)
         return img, alpha, dep
 
     @staticmethod
     def backward(ctx, v_img, v_alpha, v_dep):
-        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors
+        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors[:17]
         cam, tb, N, sh_degree, n_use, V, P, O = ctx.meta
         H, W = cam["H"], cam["W"]
         dev = m.device
         vo = _c(v_img) if v_img is not None else torch.zeros(H, W, 3, device=dev)
         va = _c(v_alpha) if v_alpha is not None else None
-        # (clamp(max=1) backward, gc_model.py:188: applied by the kernel when it loads the pixel's gradient)
-        v_xy, v_conic, v_col, v_op = _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp)
+        v_ex = None
+        if ctx.depth_grad and v_dep is not None:          # depth channel: the C = 1 case of the batched entry points
+            depths, dep = ctx.saved_tensors[17:]
+            vd = _c(v_dep)
+            vbuf = torch.zeros(N * 10, device=dev)
+            v_xy = vbuf[:2 * N].view(N, 2); v_conic = vbuf[2 * N:5 * N].view(N, 3); v_col = vbuf[5 * N:8 * N].view(N, 3)
+            v_op = vbuf[8 * N:9 * N]; v_ex = vbuf[9 * N:]
+            L.check(L.lib().gc_rasterize_bwd_depth_views(
+                L.i32(1), L.i64(N), L.i64(ids_s.numel()), L.i32(1), L.i32(1), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+                L.ptr(v_ex), L.stream_ptr()), "gc_rasterize_bwd_depth_views")
+        else:
+            # (clamp(max=1) backward, gc_model.py:188: applied by the kernel when it loads the pixel's gradient)
+            v_xy, v_conic, v_col, v_op = _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp)
         if ctx.aux is not None:
             ctx.aux.xys_grad = v_xy
         into = ctx.aux.grad_into if ctx.aux is not None else None
@@ -441,6 +467,16 @@ class _RenderView(torch.autograd.Function):
             vop = torch.empty(N, device=dev); vdc = torch.empty(N, 3, device=dev)
             vrest = torch.empty(rest.shape, device=dev)
             fn = L.lib().gc_project_sh_bwd
+        if v_ex is not None:        # the compositing's v_extra is the projection's v_depths
+            acc = 1 if (into is not None and ctx.aux.grad_accumulate) else 0
+            L.check(L.lib().gc_project_sh_bwd_depth_views(
+                L.i64(N), L.i32(1), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
+                _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
+                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), L.stream_ptr()),
+                "gc_project_sh_bwd_depth_views")
+            if into is not None:
+                return (None,) * 11
+            return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
         L.check(fn(
             L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
             V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]), L.i32(H), L.i32(W),
@@ -454,7 +490,8 @@ class _RenderView(torch.autograd.Function):
 def render_view(means, log_scales, quats, opacities, features_dc, features_rest, cam: dict, background, want_depth: bool,
                 sh_degree_to_use: int = 3, aux: RenderAux | None = None):
     """Fused get_outputs core.  cam: dict(viewmat[12], fullproj[16], origin[3], fx, fy, cx, cy, H, W) of HOST floats.
-    Returns (rgb[H,W,3] clamped to <=1, alpha[H,W], depth[H,W] (normalised, 1000 where alpha==0) or empty)."""
+    Returns (rgb[H,W,3] clamped to <=1, alpha[H,W], depth[H,W] (normalised, 1000 where alpha==0) or empty).  depth carries no gradient
+    unless aux.depth_grad is set (RenderAux)."""
     return _RenderView.apply(means, log_scales, quats, opacities, features_dc, features_rest, cam, background, want_depth,
                              sh_degree_to_use, aux)
 
@@ -556,18 +593,23 @@ class _RenderViews(torch.autograd.Function):
             aux.M = (cnt, ovf)                          # per-view device counts / overflow flags ([C] each)
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, None
             aux.xys_grad = None
-        ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
+        ctx.depth_grad = _depth_grad_on(ctx, aux, want_depth)
+        if ctx.depth_grad:
+            ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
+            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp, depths, dep)
+        else:
+            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
         ctx.meta = (cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, int(sh_degree_to_use))
         ctx.aux = aux
-        if dep is not None:
-            ctx.mark_non_differentiable(dep)
-        else:
+        if dep is None:
             dep = torch.empty(0, device=dev)
+        elif not ctx.depth_grad:
+            ctx.mark_non_differentiable(dep)
         return img, alpha, dep
 
     @staticmethod
     def backward(ctx, v_img, v_alpha, v_dep):
-        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors
+        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors[:17]
         cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, n_use = ctx.meta
         H, W = cams[0]["H"], cams[0]["W"]
         dev = m.device
@@ -575,13 +617,24 @@ class _RenderViews(torch.autograd.Function):
         st = L.stream_ptr()
         vo = _c(v_img) if v_img is not None else torch.zeros(C, H, W, 3, device=dev)
         va = _c(v_alpha) if v_alpha is not None else None
-        vbuf = torch.zeros(C * N * 9, device=dev)                      # v_xy | v_conic | v_colors | v_opacity, each [C][N][..]
+        with_depth = ctx.depth_grad and v_dep is not None
+        vbuf = torch.zeros(C * N * (10 if with_depth else 9), device=dev)   # v_xy | v_conic | v_colors | v_opacity (| v_extra), each [C][N][..]
         v_xy = vbuf[:2 * C * N].view(C, N, 2); v_conic = vbuf[2 * C * N:5 * C * N].view(C, N, 3)
-        v_col = vbuf[5 * C * N:8 * C * N].view(C, N, 3); v_op = vbuf[8 * C * N:].view(C, N)
-        L.check(lib.gc_rasterize_bwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
-                                           L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg),
-                                           L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va), L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic),
-                                           L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
+        v_col = vbuf[5 * C * N:8 * C * N].view(C, N, 3); v_op = vbuf[8 * C * N:9 * C * N].view(C, N)
+        v_ex = vbuf[9 * C * N:].view(C, N) if with_depth else None
+        if with_depth:
+            depths, dep = ctx.saved_tensors[17:]
+            vd = _c(v_dep)
+            L.check(lib.gc_rasterize_bwd_depth_views(
+                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+                L.ptr(v_ex), st), "gc_rasterize_bwd_depth_views")
+        else:
+            L.check(lib.gc_rasterize_bwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
+                                               L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg),
+                                               L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va), L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic),
+                                               L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
         if ctx.aux is not None:
             ctx.aux.xys_grad = v_xy
         into = ctx.aux.grad_into if ctx.aux is not None else None
@@ -595,10 +648,16 @@ class _RenderViews(torch.autograd.Function):
         else:
             vm = torch.empty(N, 3, device=dev); vls = torch.empty(N, 3, device=dev); vq = torch.empty(N, 4, device=dev)
             vop = torch.empty(N, device=dev); vdc = torch.empty(N, 3, device=dev); vrest = torch.empty(rest.shape, device=dev)
-        L.check(lib.gc_project_sh_bwd_views(
-            L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-            L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-            L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
+        if with_depth:              # the compositing's v_extra is the projection's v_depths
+            L.check(lib.gc_project_sh_bwd_depth_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_depth_views")
+        else:
+            L.check(lib.gc_project_sh_bwd_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
         if into is not None:
             return (None,) * 11
         return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None

@@ -76,6 +76,42 @@ def l1_ssim_loss_views(pred, target, ssim_lambda: float = 0.2, valid_window: boo
     return _L1SSIMViews.apply(pred, target, float(ssim_lambda), bool(valid_window))
 
 
+class _DepthL1Views(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        if not pred.is_cuda:
+            raise L.GaussCtrlHipError("depth_l1_loss needs GPU tensors (HIP path only; no CPU fallback)")
+        if pred.dim() != 3 or pred.shape != target.shape:
+            raise ValueError("depth_l1_loss_views: pred and target must both be [B,H,W]")
+        lib = L.lib()
+        B, H, W = pred.shape
+        p = pred.detach().float().contiguous(); t = target.detach().to(p.device).float().contiguous()
+        nbytes = lib.gc_depth_l1_views_workspace_bytes(B, H, W)
+        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=p.device)
+        sums = torch.empty(B, 2, dtype=torch.float32, device=p.device)
+        v = torch.empty_like(p)
+        L.check(lib.gc_depth_l1_fwd_bwd_views(B, L.ptr(p), L.ptr(t), H, W, L.f32(1.0), L.ptr(sums), L.ptr(v), L.ptr(ws), C.c_size_t(nbytes),
+                                              L.stream_ptr()), "gc_depth_l1_fwd_bwd_views")
+        ctx.save_for_backward(v)
+        return sums[:, 0] / sums[:, 1].clamp(min=1.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        (v,) = ctx.saved_tensors
+        return v * g.reshape(-1, 1, 1), None
+
+
+def depth_l1_loss_views(pred, target):
+    """pred, target: [B,H,W] float32 depth images -> [B] losses: each view's mean |pred - target| over the pixels where both depths are
+    real (neither is the 1000 of an empty pixel, both finite); 0 for a view without such a pixel.  Differentiable w.r.t. pred."""
+    return _DepthL1Views.apply(pred, target)
+
+
+def depth_l1_loss(pred, target):
+    """depth_l1_loss_views for one [H,W] pair -> scalar loss tensor."""
+    return _DepthL1Views.apply(pred[None], target[None])[0]
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-15):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))

@@ -319,6 +319,40 @@ size_t gc_l1_ssim_views_workspace_bytes(int B, int H, int W, int C);
 int gc_l1_ssim_fwd_bwd_views(int B, const float *pred, const float *target, int H, int W, int C, float lambda_, float grad_scale,
                              int valid_window, float *loss_out, float *v_pred, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Depth supervision: the depth image of the fused render made differentiable, and an L1 loss on it.  Opt-in: nothing above calls these.
+ * gc_rasterize_bwd_depth_views = gc_rasterize_bwd_views + the depth channel.  extra [C][N]: the per-Gaussian value the forward composited
+ * (the projected depths); depth [C][H][W]: the FINALIZED image of gc_raster_finalize[_into] (E / alpha, 1000 where alpha == 0); v_depth
+ * [C][H][W]: its gradient; v_extra [C][N]: gradient w.r.t. extra, ZERO on entry like the other four outputs (the kernel adds into them).
+ * The backward of the finalize epilogue happens in the pixel load: where alpha = 1 - final_T > 0, vE = v_depth / alpha reaches the splats and
+ * -v_depth * depth / alpha joins v_out_alpha; a sentinel pixel passes no gradient.  The depth channel has background 0 and takes no part in
+ * the rgb clamp (pre_clamp stays [C][H][W][3]).  v_out_alpha and pre_clamp may be NULL; extra / depth / v_depth / v_extra may not.  C = 1 is
+ * the single-view case (N and M_cap are then not used as strides).  Limits: those of gc_rasterize_bwd_views (C <= 65535; float atomics:
+ * the summation order, hence the last bits, vary from run to run). */
+int gc_rasterize_bwd_depth_views(int C, int64_t N, int64_t M_cap, int shared_opacities, int shared_background, int img_h, int img_w,
+                                 int tiles_x, int tiles_y, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                                 const float *conics, const float *colors, const float *opacities, const float *background,
+                                 const float *final_Ts, const int32_t *final_index, const float *v_out, const float *v_out_alpha,
+                                 const float *pre_clamp, float *v_xy, float *v_conic, float *v_colors, float *v_opacity, const float *extra,
+                                 const float *depth, const float *v_depth, float *v_extra, void *stream);
+/* gc_project_sh_bwd_views + v_depths [C][N], the gradient w.r.t. the projected depths (the v_extra above): each view adds v_depths * (row 2
+ * of its view matrix) to v_means.  A culled Gaussian (radii == 0) contributes nothing, whatever v_depths holds there; views sum in view
+ * order; accumulate as in gc_project_sh_bwd_views.  v_depths must not be NULL.  C = 1 runs the single-view kernel of gc_project_sh_bwd. */
+int gc_project_sh_bwd_depth_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
+                                  const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
+                                  int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
+                                  const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
+                                  float *v_opacity_logits, float *v_features_dc, float *v_features_rest, const float *v_depths,
+                                  void *stream);
+/* L1 between two depth images over the pixels where BOTH are real: pred / target / v_pred float32 [B][H][W]; a pixel is valid when
+ * pred != 1000 && target != 1000 (the sentinel of gc_raster_finalize) and both are finite.  loss_out: device float [B][2] = {sum |pred -
+ * target| over the valid pixels, their count}; the loss of a view is sum / max(count, 1) (formed by the caller: no host read-back here).
+ * v_pred = grad_scale * sign(pred - target) / max(count, 1) on valid pixels (sign(0) = 0), 0 elsewhere.  Deterministic (fixed reduction
+ * order).  Limits: 1 <= B <= 65535; H * W < 2^32 (the count is an exact integer on the device and rounded once to float in loss_out);
+ * workspace >= gc_depth_l1_views_workspace_bytes(B, H, W), 4-byte aligned. */
+size_t gc_depth_l1_views_workspace_bytes(int B, int H, int W);
+int gc_depth_l1_fwd_bwd_views(int B, const float *pred, const float *target, int H, int W, float grad_scale, float *loss_out, float *v_pred,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 
 /* ===================================================================================== */
 /* Part B -- ControlNet + UNet denoise step (replaces the diffusers / cuBLAS / cuDNN calls behind  */
