@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GC_HIP_LIB") or os.path.join(_HERE, "libgaussctrl_hip.so")   # GC_HIP_LIB: kernel-experiment builds only
 
-# every symbol include/gaussctrl_hip.h declares (tests/test_abi.py checks the header against this list)
+# every symbol the headers under include/ declare (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
     "gc_last_error_string", "gc_abi_version",
     "gc_project_gaussians_fwd", "gc_project_gaussians_bwd", "gc_sh_fwd", "gc_sh_bwd",
@@ -31,6 +31,8 @@ SYMBOLS = [
     "gc_raster_order_boxes_views_workspace_bytes", "gc_raster_order_boxes_views", "gc_raster_bin_sorted_views",
     # depth supervision: differentiable depth of the fused render + depth L1
     "gc_rasterize_bwd_depth_views", "gc_project_sh_bwd_depth_views", "gc_depth_l1_views_workspace_bytes", "gc_depth_l1_fwd_bwd_views",
+    # refinement (densification) on the device: include/gaussctrl_refine.h
+    "gc_refine_accumulate_views", "gc_refine_plan_workspace_bytes", "gc_refine_plan", "gc_refine_apply", "gc_refine_reset_opacity",
     "gc_dn_gemm", "gc_dn_gemm_workspace_bytes", "gc_dn_gemm_row_stat_slots", "gc_dn_gemm_chan_parts_layout", "gc_dn_gemm_selection", "gc_dn_groupnorm_apply_parts", "gc_dn_groupnorm_apply_parts_fp8", "gc_dn_groupnorm_coef_parts", "gc_dn_concat_parts_layout", "gc_dn_concat_add_parts", "gc_dn_attention", "gc_dn_groupnorm", "gc_dn_groupnorm_workspace_bytes", "gc_dn_groupnorm_apply", "gc_dn_groupnorm_apply_fp8", "gc_dn_group_stats", "gc_dn_layernorm", "gc_dn_layernorm_fp8", "gc_dn_concat_add", "gc_dn_axpby",
     "gc_dn_cast_f32", "gc_dn_softmax_rows", "gc_dn_attention_workspace_bytes", "gc_dn_attention_selection", "gc_dn_transformer_tail", "gc_dn_transformer_tail_layout", "gc_dn_transformer_head", "gc_dn_groupnorm_coef", "gc_dn_cfg_ddim_step", "gc_dn_depth_to_disparity", "gc_dn_mask_composite",
 ]

@@ -38,6 +38,14 @@ else:
         reset_alpha_every: int = 30
         stop_split_at: int = 15000
         continue_cull_post_densification: bool = True
+        # the rest of splatfacto's refinement schedule (gaussctrl_amd/refine.py reads them; splatfacto's defaults)
+        warmup_length: int = 500
+        densify_grad_thresh: float = 0.0002
+        densify_size_thresh: float = 0.01
+        n_split_samples: int = 2
+        cull_screen_size: float = 0.15
+        split_screen_size: float = 0.05
+        stop_screen_size_at: int = 4000
 
         def setup(self, **kw):
             return self._target(self, **kw)
@@ -54,6 +62,9 @@ class GaussCtrlModelConfig(_ModelConfigBase):
     # --- addition of this implementation (the name later splatfacto versions use)
     output_depth_during_training: bool = False    # True: get_outputs in training mode also returns "depth" [H,W,1], differentiable
                                                   # (ops.RenderAux.depth_grad); False: no depth while training, as the reference
+    refine_on_device: bool = False                # True (stand-alone model): get_training_callbacks returns [StepCallback, RefineCallback] --
+                                                  # splatfacto's whole refinement (statistics, split / duplicate, cull, opacity reset) on the
+                                                  # HIP kernels of csrc/train_refine.hip; False: the callbacks as before (CullCallback)
 
 
 class GaussCtrlModel(_ModelBase):
@@ -105,10 +116,16 @@ class GaussCtrlModel(_ModelBase):
     def get_training_callbacks(self, training_callback_attributes):
         """SplatfactoModel's callbacks (step bookkeeping, after_train, refinement_after) under nerfstudio; stand-alone: the
         part of refinement_after that still acts after step 30000 (> stop_split_at = 15000): opacity / scale culling every
-        `refine_every` steps [recall nerfstudio 1.0.0 splatfacto.py; SURVEY.md 3.5]."""
+        `refine_every` steps [recall nerfstudio 1.0.0 splatfacto.py; SURVEY.md 3.5].  With config.refine_on_device the stand-alone model
+        runs all of splatfacto's refinement on the device instead (gc_trainer.RefineCallback, which also covers that cull); under nerfstudio
+        the inherited callbacks stay whatever the switch says."""
         if HAVE_NERFSTUDIO:
             return super().get_training_callbacks(training_callback_attributes)
-        from .gc_trainer import CullCallback, StepCallback
+        from .gc_trainer import CullCallback, RefineCallback, StepCallback
+        if getattr(self.config, "refine_on_device", False):
+            dm = getattr(getattr(training_callback_attributes, "pipeline", None), "datamanager", None)
+            n_train = len(getattr(dm, "train_data", None) or ())
+            return [StepCallback(self), RefineCallback(self, training_callback_attributes.optimizers, n_train)]
         return [StepCallback(self), CullCallback(self, training_callback_attributes.optimizers)]
 
     # ------------------------------------------------------------------------------------ gc_model.py:57-206

@@ -221,3 +221,29 @@ class CullCallback(_Callback):
                         if k in st:
                             st[k] = st[k][keep].contiguous()
                     opt.state[p] = st
+
+
+class RefineCallback(_Callback):
+    """SplatfactoModel.after_train + refinement_after on the device (gaussctrl_amd/refine.py, csrc/train_refine.hip): the screen-space gradient
+    statistics after every training iteration before stop_split_at, and at every refinement step split / duplicate / cull / opacity reset --
+    or, after stop_split_at, the cull CullCallback does, through the same kernels.  Opt-in: GaussCtrlModelConfig.refine_on_device."""
+    where = ("after_train_iteration",)
+
+    def __init__(self, model, optimizers: dict, num_train_data: int = 0):
+        from .refine import RefineState
+        self.model, self.optimizers, self.num_train_data = model, optimizers, int(num_train_data)
+        self.state = RefineState()
+        self.n_culled = 0
+        self.n_added = 0
+
+    def run(self, step, samples=None):
+        c = self.model.config
+        if step < c.stop_split_at:
+            self.state.accumulate(self.model)
+        if step % c.refine_every != 0:
+            return
+        self.state.refine(self.model, self.optimizers, step, self.num_train_data, samples)
+        last = self.state.last
+        if last:
+            self.n_culled += last["n_in"] - last["n_survivors"]          # originals that left (culled ones and split sources)
+            self.n_added += last["n_out"] - last["n_survivors"]
