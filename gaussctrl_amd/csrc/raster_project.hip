@@ -9,6 +9,7 @@
 // arithmetic is written as explicit IEEE binary32 operations in a fixed order so that the integer
 // outputs (radii, tile boxes, num_tiles_hit -> sort keys) are bit-identical to the CPU oracle.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -329,14 +330,76 @@ __global__ __launch_bounds__(256) void k_sh_bwd(int64_t N, int K, int n, const f
         }
 }
 
-// ---------------------------------------------------------------- kernels: fused product path
+// ---------------------------------------------------------------- fused product path: the shared per-view pieces
 // One pass over the 59-float record (236 B/Gaussian read, 48 B written).  Mirrors the reference
 // op-by-op: exp(scales), q/|q| (gc_model.py:144), project, viewdirs (gc_model.py:163-164),
 // SH, clamp(+0.5,min 0) (:167) -- or sigmoid(features_dc) when config.sh_degree == 0 (:169, n_use = -1) -- and sigmoid(opacity) (:181).
 //
+// The single-view kernels (k_project_sh_fwd / _bwd) and the C-views-per-launch kernels (k_project_sh_fwd_views / _bwd_views) are built from the
+// pieces of this section: view c of a batch is bit-identical to the single-view kernel on camera c because both run the SAME code (compiled with
+// -ffp-contract=off, so inlining cannot change a bit).  A kernel owns only its memory schedule: loads, barrier, and where the view sums live.
+__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + __expf(-x)); }
+
+// The camera-independent part of a Gaussian.  load_record only ISSUES the loads (a kernel may put other traffic before their first use).
+struct Record {
+    float p[3];      // mean
+    float s[3];      // log-scale as loaded; exp(.) after activate
+    float q[4], qn;  // quaternion as loaded; q/|q| after activate (the outer normalisation, gc_model.py:144), with |q| in qn
+    float op;        // opacity logit as loaded; sigmoid(.) after activate
+    float d[3];      // features_dc (DC only: the backward does not need it)
+};
+
+template <bool DC>
+__device__ __forceinline__ void load_record(Record &r, int64_t i, const float *means, const float *log_scales, const float *quats,
+        const float *op_logit, const float *f_dc)
+{
+    r.p[0] = means[3 * i]; r.p[1] = means[3 * i + 1]; r.p[2] = means[3 * i + 2];
+    r.s[0] = log_scales[3 * i]; r.s[1] = log_scales[3 * i + 1]; r.s[2] = log_scales[3 * i + 2];
+    const float4 q = *reinterpret_cast<const float4 *>(quats + 4 * i);
+    r.q[0] = q.x; r.q[1] = q.y; r.q[2] = q.z; r.q[3] = q.w; r.qn = 0.f;
+    r.op = op_logit[i];
+    r.d[0] = DC ? f_dc[3 * i] : 0.f; r.d[1] = DC ? f_dc[3 * i + 1] : 0.f; r.d[2] = DC ? f_dc[3 * i + 2] : 0.f;
+}
+
+__device__ __forceinline__ void activate(Record &r)
+{
+    r.s[0] = expf(r.s[0]); r.s[1] = expf(r.s[1]); r.s[2] = expf(r.s[2]);
+    r.qn = sqrtf(((r.q[0] * r.q[0] + r.q[1] * r.q[1]) + r.q[2] * r.q[2]) + r.q[3] * r.q[3]);
+    r.q[0] = r.q[0] / r.qn; r.q[1] = r.q[1] / r.qn; r.q[2] = r.q[2] / r.qn; r.q[3] = r.q[3] / r.qn;
+    r.op = sigmoidf(r.op);
+}
+
 // HBM access: one lane per Gaussian, but the 45-float features_rest record (180 of the 236 bytes) is NOT read lane-by-lane --
 // a 180-byte lane stride makes every load instruction touch 64 different cache lines (rocprofv3 FETCH_SIZE of the round-1 kernel:
 // 3.6x the algorithmic bytes).  The workgroup's 256 records are one contiguous 46 KB block: it is streamed with 16-byte-per-lane
+// loads into LDS, and each lane then reads ITS record from LDS at a 45-dword stride (odd: bank-conflict free).  The 46 KB of LDS
+// allow 3 workgroups per CU.  The caller places the barrier.
+template <int R>
+__device__ __forceinline__ void stage_rest_in(float *srest, const float *f_rest, int64_t N, int64_t i0, int tid)
+{
+    const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;        // floats of this workgroup's block
+    const float *src = f_rest + i0 * R;                              // 256 * R * 4 bytes per block: 16-byte aligned
+    for (int64_t j = tid; j < cnt / 4; j += 256) reinterpret_cast<float4 *>(srest)[j] = reinterpret_cast<const float4 *>(src)[j];
+    for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) srest[j] = src[j];
+}
+
+// The way back: the features_rest gradient rows the lanes left in LDS are written with 16-byte-per-lane stores (a lane-strided 45-float
+// store has the same 64-lines-per-instruction problem), or, ACC, added to what is there.  Barrier included.
+template <int R, bool ACC>
+__device__ __forceinline__ void flush_rest_out(const float *svr, float *v_rest, int64_t N, int64_t i0, int tid)
+{
+    if (R == 0) return;
+    __syncthreads();
+    const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;
+    float *dst = v_rest + i0 * R;
+    for (int64_t j = tid; j < cnt / 4; j += 256) {
+        float4 v = reinterpret_cast<const float4 *>(svr)[j];
+        if (ACC) { const float4 o = reinterpret_cast<const float4 *>(dst)[j]; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+        reinterpret_cast<float4 *>(dst)[j] = v;
+    }
+    for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) dst[j] = ACC ? dst[j] + svr[j] : svr[j];
+}
+
 // Tight tile box of the fused path (round 3).  gsplat bins a Gaussian into every tile of the box around a CIRCLE of 3 sqrt(lambda_max);
 // a pixel can only pass the compositing test alpha = opacity * exp(-sigma) >= 1/255 inside the ellipse sigma <= tau = ln(255 opacity),
 // whose axis-aligned bounding box has half extents sqrt(2 tau cyy / det), sqrt(2 tau cxx / det) (conic = inverse covariance).  For
@@ -368,110 +431,173 @@ __device__ __forceinline__ uint32_t tight_tile_box(const Cam &cam, const Proj &o
     return (uint32_t)minx | ((uint32_t)maxx << 8) | ((uint32_t)miny << 16) | ((uint32_t)maxy << 24);
 }
 
-// loads into LDS, and each lane then reads ITS record from LDS at a 45-dword stride (odd: bank-conflict free).
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + __expf(-x)); }
-
-template <int K>
-__global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int n_use,
-                                                        const float *__restrict__ means, const float *__restrict__ log_scales,
-                                                        const float *__restrict__ quats, const float *__restrict__ op_logit,
-                                                        const float *__restrict__ f_dc, const float *__restrict__ f_rest,
-                                                        float *__restrict__ xys, float *__restrict__ depths,
-                                                        int32_t *__restrict__ radii, float *__restrict__ conics,
-                                                        int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs,
-                                                        float *__restrict__ opac, uint32_t *__restrict__ tile_box)
+// Projects Gaussian `id` for one camera and stores the view's projection state at element index o (o = id for a single view, view * N + id
+// in a batch).  tile_box (optional): the tight box, and the tiles_hit it implies -- nth and the box the emission walks shrink together.
+// depth_pairs (optional): the depth-order sort's input pair.  Returns project_one's verdict.
+__device__ __forceinline__ bool store_view(const Cam &cam, const Record &r, int64_t o, int64_t id, float *xys, float *depths, int32_t *radii,
+        float *conics, int32_t *tiles_hit, uint32_t *tile_box, uint2 *depth_pairs)
 {
-    constexpr int R = (K - 1) * 3;                         // floats of features_rest per Gaussian
-    __shared__ __attribute__((aligned(16))) float srest[R > 0 ? 256 * R : 4];
-    const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * 256;
-    const int64_t i = i0 + tid;
-    // the lane's own record is requested BEFORE the cooperative staging of the SH block, so that the two HBM round trips overlap
-    // (3 workgroups per CU -- the 46 KB of LDS -- leave little else to hide them behind)
-    const int64_t ic = i < N ? i : N - 1;
-    float p0 = means[3 * ic], p1 = means[3 * ic + 1], p2 = means[3 * ic + 2];
-    const float l0 = log_scales[3 * ic], l1 = log_scales[3 * ic + 1], l2 = log_scales[3 * ic + 2];
-    float4 q = *reinterpret_cast<const float4 *>(quats + 4 * ic);
-    const float opl = op_logit[ic];
-    const float d0 = f_dc[3 * ic], d1 = f_dc[3 * ic + 1], d2 = f_dc[3 * ic + 2];
-    if (R > 0 && n_use > 0) {
-        const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;        // floats of this workgroup's block
-        const float *src = f_rest + i0 * R;                              // 256 * R * 4 bytes per block: 16-byte aligned
-        for (int64_t j = tid; j < cnt / 4; j += 256) reinterpret_cast<float4 *>(srest)[j] = reinterpret_cast<const float4 *>(src)[j];
-        for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) srest[j] = src[j];
+    Proj pr;
+    const bool ok = project_one(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], pr);
+    xys[2 * o] = pr.xy[0]; xys[2 * o + 1] = pr.xy[1];
+    if (tile_box) {
+        uint32_t box = 0;
+        if (ok) box = tight_tile_box(cam, pr, r.op);
+        tile_box[o] = box;
+        pr.tiles_hit = (int)(((box >> 8) & 255u) - (box & 255u)) * (int)((box >> 24) - ((box >> 16) & 255u));
     }
-    Proj o;
-    bool ok = false;
-    if (i < N) {
-        float s0 = expf(l0), s1 = expf(l1), s2 = expf(l2);
-        float qn = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-        q.x = q.x / qn; q.y = q.y / qn; q.z = q.z / qn; q.w = q.w / qn;
-        ok = project_one(cam, p0, p1, p2, s0, s1, s2, q.x, q.y, q.z, q.w, o);
-        xys[2 * i] = o.xy[0]; xys[2 * i + 1] = o.xy[1];
-        const float op = sigmoidf(opl);
-        if (tile_box) {      // tight tile box (see tight_tile_box): nth and the box the emission walks shrink together
-            uint32_t box = 0;
-            if (ok) box = tight_tile_box(cam, o, op);
-            tile_box[i] = box;
-            o.tiles_hit = (int)(((box >> 8) & 255u) - (box & 255u)) * (int)((box >> 24) - ((box >> 16) & 255u));
-        }
-        depths[i] = o.depth; radii[i] = o.radius; tiles_hit[i] = o.tiles_hit;
-        conics[3 * i] = o.conic[0]; conics[3 * i + 1] = o.conic[1]; conics[3 * i + 2] = o.conic[2];
-        opac[i] = op;
-    }
-    if (R > 0 && n_use > 0) __syncthreads();
-    if (i >= N) return;
+    depths[o] = pr.depth; radii[o] = pr.radius; tiles_hit[o] = pr.tiles_hit;
+    conics[3 * o] = pr.conic[0]; conics[3 * o + 1] = pr.conic[1]; conics[3 * o + 2] = pr.conic[2];
+    if (depth_pairs) depth_pairs[o] = make_uint2(pr.radius > 0 ? __float_as_uint(pr.depth) : 0xFFFFFFFFu, (uint32_t)id);
+    return ok;
+}
+
+// Unit vector from the camera origin to the mean (gc_model.py:163-164) -> SH basis up to degree n_use.
+__device__ __forceinline__ void view_basis(const Cam &cam, const Record &r, int n_use, float *B)
+{
+    float dx = r.p[0] - cam.ox, dy = r.p[1] - cam.oy, dz = r.p[2] - cam.oz;
+    float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
+    dx = dx / dn; dy = dy / dn; dz = dz / dn;
+    sh_basis(n_use, dx, dy, dz, B);
+}
+
+// Colour of the Gaussian for one camera; rest = the lane's features_rest row in LDS (read only when n_use > 0).  0 when !ok.
+template <int K>
+__device__ __forceinline__ float3 shade(const Cam &cam, const Record &r, const float *rest, int n_use, bool ok)
+{
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     if (ok) {
         if (n_use < 0) {          // config.sh_degree == 0: rgbs = sigmoid(features_dc)   (gc_model.py:169)
-            c0 = sigmoidf(d0); c1 = sigmoidf(d1); c2 = sigmoidf(d2);
+            c0 = sigmoidf(r.d[0]); c1 = sigmoidf(r.d[1]); c2 = sigmoidf(r.d[2]);
         } else {
-            float dx = p0 - cam.ox, dy = p1 - cam.oy, dz = p2 - cam.oz;
-            float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-            dx = dx / dn; dy = dy / dn; dz = dz / dn;
             float B[16];
-            sh_basis(n_use, dx, dy, dz, B);
-            c0 = B[0] * d0; c1 = B[0] * d1; c2 = B[0] * d2;
-            const float *r = srest + tid * R;
+            view_basis(cam, r, n_use, B);
+            c0 = B[0] * r.d[0]; c1 = B[0] * r.d[1]; c2 = B[0] * r.d[2];
             int Ku = (n_use + 1) * (n_use + 1);
 #pragma unroll
             for (int k = 1; k < K; ++k)
                 if (k < Ku) {
-                    c0 += B[k] * r[3 * (k - 1)]; c1 += B[k] * r[3 * (k - 1) + 1]; c2 += B[k] * r[3 * (k - 1) + 2];
+                    c0 += B[k] * rest[3 * (k - 1)]; c1 += B[k] * rest[3 * (k - 1) + 1]; c2 += B[k] * rest[3 * (k - 1) + 2];
                 }
             c0 = fmaxf(c0 + 0.5f, 0.f); c1 = fmaxf(c1 + 0.5f, 0.f); c2 = fmaxf(c2 + 0.5f, 0.f);
         }
     }
-    rgbs[3 * i] = c0; rgbs[3 * i + 1] = c1; rgbs[3 * i + 2] = c2;
+    return make_float3(c0, c1, c2);
 }
 
-// Backward of the above.  The colour path needs only the FORWARD colours (rgbs): the clamp(min = 0) mask is rgbs > 0 and the
-// sigmoid mode's derivative is s (1 - s), so the 192-byte SH record is not re-read; the 180-byte features_rest gradient is staged in
-// LDS and written with 16-byte-per-lane stores (a lane-strided 45-float store has the same 64-lines-per-instruction problem).
-// ACC: the six outputs are accumulated into (+=) instead of written -- gradient accumulation over the views of a batch without a
-// separate read-add-write pass per tensor (the caller owns zeroing / the first view runs with ACC = false).
-// DEPTH (gc_project_sh_bwd_depth_views): v_depths [N] feeds project_one_bwd's depth argument (depth = row 2 of the view matrix applied to
-// the mean); without it the argument is the literal 0 it always was.
+// Leaf-gradient stores: written, or (ACC) added to what is there; put4 is one 16-byte access.
+template <bool ACC> __device__ __forceinline__ void put(float *p, float v) { *p = ACC ? *p + v : v; }
+template <bool ACC>
+__device__ __forceinline__ void put4(float *p, const float *v)
+{
+    float4 v4 = make_float4(v[0], v[1], v[2], v[3]);
+    if (ACC) { const float4 o = *reinterpret_cast<const float4 *>(p); v4.x += o.x; v4.y += o.y; v4.z += o.z; v4.w += o.w; }
+    *reinterpret_cast<float4 *>(p) = v4;
+}
+
+// Gradient of one view to the leaves of one Gaussian the view did not cull (radii > 0), all per-view inputs at element index o; in two parts
+// so that a kernel may store the first before it computes the second.  GeomGrad: the VJP of store_view, to means / log-scales / quaternion /
+// opacity logit.  DEPTH (gc_project_sh_bwd_depth_views): v_depths feeds project_one_bwd's depth argument (depth = row 2 of the view matrix
+// applied to the mean); without it the argument is the literal 0 it always was.
+struct GeomGrad { float vm[3], gls[3], gq[4], gop; };
+
+template <bool DEPTH>
+__device__ __forceinline__ void geom_vjp(const Cam &cam, const Record &r, int64_t o, const float *conics, const float *v_xy, const float *v_conic,
+                                         const float *v_opac, const float *v_depths, GeomGrad &g)
+{
+    ProjGrad pg;
+    project_one_bwd(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], conics[3 * o], conics[3 * o + 1],
+                    conics[3 * o + 2], v_xy[2 * o], v_xy[2 * o + 1], DEPTH ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1],
+                    v_conic[3 * o + 2], pg);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.vm[k] = pg.vm[k]; g.gls[k] = pg.vs[k] * r.s[k]; }
+    // outer normalisation q/|q| (gc_model.py:144)
+    const float dq = r.q[0] * pg.vq[0] + r.q[1] * pg.vq[1] + r.q[2] * pg.vq[2] + r.q[3] * pg.vq[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g.gq[k] = (pg.vq[k] - r.q[k] * dq) / r.qn;
+    g.gop = v_opac[o] * r.op * (1.f - r.op);
+}
+
+// ColourGrad: the VJP of shade.  It needs only the FORWARD colours (rgbs): the clamp(min = 0) mask is rgbs > 0 and the sigmoid mode's
+// derivative is s (1 - s), so the 192-byte SH record is not re-read.  gdc goes to features_dc; the features_rest row is B[k] * v[.] for
+// 1 <= k < Ku and 0 beyond (rest_row).
+struct ColourGrad { float gdc[3], v[3], B[16]; int Ku; };
+
+__device__ __forceinline__ void colour_vjp(const Cam &cam, const Record &r, int64_t o, int n_use, const float *rgbs, const float *v_rgbs,
+                                           ColourGrad &g)
+{
+    const float c[3] = {rgbs[3 * o], rgbs[3 * o + 1], rgbs[3 * o + 2]};
+    if (n_use < 0) {        // d sigmoid(features_dc)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { g.gdc[k] = v_rgbs[3 * o + k] * c[k] * (1.f - c[k]); g.v[k] = 0.f; }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) g.B[k] = 0.f;
+        g.Ku = 0;
+    } else {
+        view_basis(cam, r, n_use, g.B);
+        g.Ku = (n_use + 1) * (n_use + 1);
+        // clamp(SH + 0.5, min 0) (gc_model.py:167): the gradient passes where the forward colour is positive
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { g.v[k] = c[k] > 0.f ? v_rgbs[3 * o + k] : 0.f; g.gdc[k] = g.B[0] * g.v[k]; }
+    }
+}
+
+// The view's features_rest gradient row into the lane's LDS row: assigned, or (ADD) added to the running sum.
+template <int K, bool ADD>
+__device__ __forceinline__ void rest_row(float *vr, const ColourGrad &g)
+{
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        const float b = k < g.Ku ? g.B[k] : 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vr[3 * (k - 1) + c] = ADD ? vr[3 * (k - 1) + c] + b * g.v[c] : b * g.v[c];
+    }
+}
+
+// ---------------------------------------------------------------- kernels: fused product path, one camera
+template <int K>
+__global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int n_use, const float *__restrict__ means,
+        const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ f_dc,
+        const float *__restrict__ f_rest, float *__restrict__ xys, float *__restrict__ depths, int32_t *__restrict__ radii,
+        float *__restrict__ conics, int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs, float *__restrict__ opac,
+        uint32_t *__restrict__ tile_box)
+{
+    constexpr int R = (K - 1) * 3;                         // floats of features_rest per Gaussian
+    __shared__ __attribute__((aligned(16))) float srest[R > 0 ? 256 * R : 4];
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
+    // the lane's own record is requested BEFORE the cooperative staging of the SH block, so that the two HBM round trips overlap
+    // (3 workgroups per CU -- the 46 KB of LDS -- leave little else to hide them behind), and projected before the barrier
+    Record r;
+    load_record<true>(r, i < N ? i : N - 1, means, log_scales, quats, op_logit, f_dc);
+    if (R > 0 && n_use > 0) stage_rest_in<R>(srest, f_rest, N, i0, tid);
+    bool ok = false;
+    if (i < N) {
+        activate(r);
+        ok = store_view(cam, r, i, i, xys, depths, radii, conics, tiles_hit, tile_box, nullptr);
+        opac[i] = r.op;
+    }
+    if (R > 0 && n_use > 0) __syncthreads();
+    if (i >= N) return;
+    const float3 c = shade<K>(cam, r, srest + tid * R, n_use, ok);
+    rgbs[3 * i] = c.x; rgbs[3 * i + 1] = c.y; rgbs[3 * i + 2] = c.z;
+}
+
+// Backward of the above.  ACC: the six outputs are accumulated into (+=) instead of written -- gradient accumulation over the views of a
+// batch without a separate read-add-write pass per tensor (the caller owns zeroing / the first view runs with ACC = false).
 template <int K, bool ACC, bool DEPTH = false>
-__global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int n_use,
-                                                        const float *__restrict__ means, const float *__restrict__ log_scales,
-                                                        const float *__restrict__ quats, const float *__restrict__ op_logit,
-                                                        const float *__restrict__ rgbs,
-                                                        const int32_t *__restrict__ radii, const float *__restrict__ conics,
-                                                        const float *__restrict__ v_xy, const float *__restrict__ v_conic,
-                                                        const float *__restrict__ v_rgbs, const float *__restrict__ v_opac,
-                                                        float *__restrict__ v_means, float *__restrict__ v_ls,
-                                                        float *__restrict__ v_quats, float *__restrict__ v_oplogit,
-                                                        float *__restrict__ v_dc, float *__restrict__ v_rest,
-                                                        const float *__restrict__ v_depths)
+__global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int n_use, const float *__restrict__ means,
+        const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ rgbs,
+        const int32_t *__restrict__ radii, const float *__restrict__ conics, const float *__restrict__ v_xy, const float *__restrict__ v_conic,
+        const float *__restrict__ v_rgbs, const float *__restrict__ v_opac, float *__restrict__ v_means, float *__restrict__ v_ls,
+        float *__restrict__ v_quats, float *__restrict__ v_oplogit, float *__restrict__ v_dc, float *__restrict__ v_rest,
+        const float *__restrict__ v_depths)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float svr[R > 0 ? 256 * R : 4];
     const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * 256;
-    const int64_t i = i0 + tid;
+    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
     float *vr = svr + tid * R;
-    auto put = [](float *p, float v) __attribute__((always_inline)) { *p = ACC ? *p + v : v; };
     if (i < N) {
         if (radii[i] <= 0) {
             if (!ACC) {
@@ -483,167 +609,78 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int 
 #pragma unroll
             for (int k = 0; k < R; ++k) vr[k] = 0.f;
         } else {
-            float p0 = means[3 * i], p1 = means[3 * i + 1], p2 = means[3 * i + 2];
-            float s0 = expf(log_scales[3 * i]), s1 = expf(log_scales[3 * i + 1]), s2 = expf(log_scales[3 * i + 2]);
-            float4 qr = *reinterpret_cast<const float4 *>(quats + 4 * i);
-            float qn = sqrtf(((qr.x * qr.x + qr.y * qr.y) + qr.z * qr.z) + qr.w * qr.w);
-            float q0 = qr.x / qn, q1 = qr.y / qn, q2 = qr.z / qn, q3 = qr.w / qn;
-            ProjGrad g;
-            project_one_bwd(cam, p0, p1, p2, s0, s1, s2, q0, q1, q2, q3, conics[3 * i], conics[3 * i + 1], conics[3 * i + 2],
-                            v_xy[2 * i], v_xy[2 * i + 1], DEPTH ? v_depths[i] : 0.f, v_conic[3 * i], v_conic[3 * i + 1], v_conic[3 * i + 2], g);
-            put(v_means + 3 * i, g.vm[0]); put(v_means + 3 * i + 1, g.vm[1]); put(v_means + 3 * i + 2, g.vm[2]);
-            put(v_ls + 3 * i, g.vs[0] * s0); put(v_ls + 3 * i + 1, g.vs[1] * s1); put(v_ls + 3 * i + 2, g.vs[2] * s2);
-            // outer normalisation q/|q| (gc_model.py:144)
-            float dq = q0 * g.vq[0] + q1 * g.vq[1] + q2 * g.vq[2] + q3 * g.vq[3];
-            float4 vq4 = make_float4((g.vq[0] - q0 * dq) / qn, (g.vq[1] - q1 * dq) / qn, (g.vq[2] - q2 * dq) / qn, (g.vq[3] - q3 * dq) / qn);
-            if (ACC) { const float4 o = *reinterpret_cast<const float4 *>(v_quats + 4 * i); vq4.x += o.x; vq4.y += o.y; vq4.z += o.z; vq4.w += o.w; }
-            *reinterpret_cast<float4 *>(v_quats + 4 * i) = vq4;
-            float op = sigmoidf(op_logit[i]);
-            put(v_oplogit + i, v_opac[i] * op * (1.f - op));
-            const float r0 = rgbs[3 * i], r1 = rgbs[3 * i + 1], r2 = rgbs[3 * i + 2];
-            if (n_use < 0) {        // d sigmoid(features_dc)
-                put(v_dc + 3 * i, v_rgbs[3 * i] * r0 * (1.f - r0)); put(v_dc + 3 * i + 1, v_rgbs[3 * i + 1] * r1 * (1.f - r1));
-                put(v_dc + 3 * i + 2, v_rgbs[3 * i + 2] * r2 * (1.f - r2));
+            Record r;
+            load_record<false>(r, i, means, log_scales, quats, op_logit, nullptr);
+            activate(r);
+            GeomGrad g;
+            geom_vjp<DEPTH>(cam, r, i, conics, v_xy, v_conic, v_opac, v_depths, g);
 #pragma unroll
-                for (int k = 0; k < R; ++k) vr[k] = 0.f;
-            } else {
-                float dx = p0 - cam.ox, dy = p1 - cam.oy, dz = p2 - cam.oz;
-                float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-                dx = dx / dn; dy = dy / dn; dz = dz / dn;
-                float B[16];
-                sh_basis(n_use, dx, dy, dz, B);
-                int Ku = (n_use + 1) * (n_use + 1);
-                // clamp(SH + 0.5, min 0) (gc_model.py:167): the gradient passes where the forward colour is positive
-                float v0 = r0 > 0.f ? v_rgbs[3 * i] : 0.f;
-                float v1 = r1 > 0.f ? v_rgbs[3 * i + 1] : 0.f;
-                float v2 = r2 > 0.f ? v_rgbs[3 * i + 2] : 0.f;
-                put(v_dc + 3 * i, B[0] * v0); put(v_dc + 3 * i + 1, B[0] * v1); put(v_dc + 3 * i + 2, B[0] * v2);
+            for (int k = 0; k < 3; ++k) { put<ACC>(v_means + 3 * i + k, g.vm[k]); put<ACC>(v_ls + 3 * i + k, g.gls[k]); }
+            put4<ACC>(v_quats + 4 * i, g.gq);
+            put<ACC>(v_oplogit + i, g.gop);
+            ColourGrad c;
+            colour_vjp(cam, r, i, n_use, rgbs, v_rgbs, c);
 #pragma unroll
-                for (int k = 1; k < K; ++k) {
-                    float b = k < Ku ? B[k] : 0.f;
-                    vr[3 * (k - 1)] = b * v0; vr[3 * (k - 1) + 1] = b * v1; vr[3 * (k - 1) + 2] = b * v2;
-                }
-            }
+            for (int k = 0; k < 3; ++k) put<ACC>(v_dc + 3 * i + k, c.gdc[k]);
+            rest_row<K, false>(vr, c);
         }
     }
-    if (R > 0) {
-        __syncthreads();
-        const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;
-        float *dst = v_rest + i0 * R;
-        for (int64_t j = tid; j < cnt / 4; j += 256) {
-            float4 v = reinterpret_cast<const float4 *>(svr)[j];
-            if (ACC) { const float4 o = reinterpret_cast<const float4 *>(dst)[j]; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-            reinterpret_cast<float4 *>(dst)[j] = v;
-        }
-        for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) dst[j] = ACC ? dst[j] + svr[j] : svr[j];
-    }
+    flush_rest_out<R, ACC>(svr, v_rest, N, i0, tid);
 }
 
 // ---------------------------------------------------------------- kernels: C views per launch (round 5)
 // The 236-byte parameter record of a Gaussian does not depend on the camera: a launch over C views reads it ONCE (the SH block staged
 // through LDS once) and projects / shades it for every view of the batch, instead of C launches that each stream the whole record again --
-// 236 + C * 60 bytes per Gaussian instead of C * 296.  Same device functions, same operation order as the single-view kernel: every output
+// 236 + C * 60 bytes per Gaussian instead of C * 296.  Per view it runs store_view and shade, the code of the single-view kernel: every output
 // of view c is bit-identical to what gc_project_sh_fwd[_boxes] writes for that camera.  Per-view outputs are [C][N][..]; `opac` (sigmoid of
 // the opacity logit, camera independent) is written once, [N]; depth_pairs (optional) are the depth-order sort's input pairs.
 constexpr int MAXV = 8;
 struct CamBatch { Cam cam[MAXV]; int C; };
 
 template <int K>
-__global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatch cb, int n_use,
-                                                              const float *__restrict__ means, const float *__restrict__ log_scales,
-                                                              const float *__restrict__ quats, const float *__restrict__ op_logit,
-                                                              const float *__restrict__ f_dc, const float *__restrict__ f_rest,
-                                                              float *__restrict__ xys, float *__restrict__ depths,
-                                                              int32_t *__restrict__ radii, float *__restrict__ conics,
-                                                              int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs,
-                                                              float *__restrict__ opac, uint32_t *__restrict__ tile_box,
-                                                              uint2 *__restrict__ depth_pairs)
+__global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatch cb, int n_use, const float *__restrict__ means,
+        const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ f_dc,
+        const float *__restrict__ f_rest, float *__restrict__ xys, float *__restrict__ depths, int32_t *__restrict__ radii,
+        float *__restrict__ conics, int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs, float *__restrict__ opac,
+        uint32_t *__restrict__ tile_box, uint2 *__restrict__ depth_pairs)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float srest[R > 0 ? 256 * R : 4];
     const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * 256;
-    const int64_t i = i0 + tid;
-    const int64_t ic = i < N ? i : N - 1;
-    const float p0 = means[3 * ic], p1 = means[3 * ic + 1], p2 = means[3 * ic + 2];
-    const float l0 = log_scales[3 * ic], l1 = log_scales[3 * ic + 1], l2 = log_scales[3 * ic + 2];
-    float4 q = *reinterpret_cast<const float4 *>(quats + 4 * ic);
-    const float opl = op_logit[ic];
-    const float d0 = f_dc[3 * ic], d1 = f_dc[3 * ic + 1], d2 = f_dc[3 * ic + 2];
-    if (R > 0 && n_use > 0) {
-        const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;
-        const float *src = f_rest + i0 * R;
-        for (int64_t j = tid; j < cnt / 4; j += 256) reinterpret_cast<float4 *>(srest)[j] = reinterpret_cast<const float4 *>(src)[j];
-        for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) srest[j] = src[j];
+    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
+    Record r;
+    load_record<true>(r, i < N ? i : N - 1, means, log_scales, quats, op_logit, f_dc);
+    if (R > 0 && n_use > 0) {      // staged once for all views: the barrier stands before the view loop
+        stage_rest_in<R>(srest, f_rest, N, i0, tid);
         __syncthreads();
     }
     if (i >= N) return;
-    const float s0 = expf(l0), s1 = expf(l1), s2 = expf(l2);
-    const float qn = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-    q.x = q.x / qn; q.y = q.y / qn; q.z = q.z / qn; q.w = q.w / qn;
-    const float op = sigmoidf(opl);
-    opac[i] = op;
-    const float *r = srest + tid * R;
+    activate(r);
+    opac[i] = r.op;
     for (int v = 0; v < cb.C; ++v) {
         const Cam &cam = cb.cam[v];
         const int64_t o = (int64_t)v * N + i;
-        Proj pr;
-        const bool ok = project_one(cam, p0, p1, p2, s0, s1, s2, q.x, q.y, q.z, q.w, pr);
-        xys[2 * o] = pr.xy[0]; xys[2 * o + 1] = pr.xy[1];
-        if (tile_box) {
-            uint32_t box = 0;
-            if (ok) box = tight_tile_box(cam, pr, op);
-            tile_box[o] = box;
-            pr.tiles_hit = (int)(((box >> 8) & 255u) - (box & 255u)) * (int)((box >> 24) - ((box >> 16) & 255u));
-        }
-        depths[o] = pr.depth; radii[o] = pr.radius; tiles_hit[o] = pr.tiles_hit;
-        conics[3 * o] = pr.conic[0]; conics[3 * o + 1] = pr.conic[1]; conics[3 * o + 2] = pr.conic[2];
-        if (depth_pairs) depth_pairs[o] = make_uint2(pr.radius > 0 ? __float_as_uint(pr.depth) : 0xFFFFFFFFu, (uint32_t)i);
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-        if (ok) {
-            if (n_use < 0) {
-                c0 = sigmoidf(d0); c1 = sigmoidf(d1); c2 = sigmoidf(d2);
-            } else {
-                float dx = p0 - cam.ox, dy = p1 - cam.oy, dz = p2 - cam.oz;
-                float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-                dx = dx / dn; dy = dy / dn; dz = dz / dn;
-                float B[16];
-                sh_basis(n_use, dx, dy, dz, B);
-                c0 = B[0] * d0; c1 = B[0] * d1; c2 = B[0] * d2;
-                int Ku = (n_use + 1) * (n_use + 1);
-#pragma unroll
-                for (int k = 1; k < K; ++k)
-                    if (k < Ku) {
-                        c0 += B[k] * r[3 * (k - 1)]; c1 += B[k] * r[3 * (k - 1) + 1]; c2 += B[k] * r[3 * (k - 1) + 2];
-                    }
-                c0 = fmaxf(c0 + 0.5f, 0.f); c1 = fmaxf(c1 + 0.5f, 0.f); c2 = fmaxf(c2 + 0.5f, 0.f);
-            }
-        }
-        rgbs[3 * o] = c0; rgbs[3 * o + 1] = c1; rgbs[3 * o + 2] = c2;
+        const bool ok = store_view(cam, r, o, i, xys, depths, radii, conics, tiles_hit, tile_box, depth_pairs);
+        const float3 c = shade<K>(cam, r, srest + tid * R, n_use, ok);
+        rgbs[3 * o] = c.x; rgbs[3 * o + 1] = c.y; rgbs[3 * o + 2] = c.z;
     }
 }
 
-// Backward over C views: the parameter record is read once, the per-view VJPs (same device functions as the single-view kernel) are summed
+// Backward over C views: the parameter record is read once, the per-view VJPs (geom_vjp + colour_vjp, the code of the single-view kernel) are summed
 // in registers IN VIEW ORDER -- ((g_0 + g_1) + g_2) ..., the order C accumulating single-view launches produce -- and the 59 gradient floats
 // are written (or, ACC, added to what is there) ONCE per batch: N * (56 + C * 64) bytes read + N * 236 written instead of C * N * 344.
 template <int K, bool ACC, bool DEPTH = false>
-__global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatch cb, int n_use,
-                                                              const float *__restrict__ means, const float *__restrict__ log_scales,
-                                                              const float *__restrict__ quats, const float *__restrict__ op_logit,
-                                                              const float *__restrict__ rgbs,
-                                                              const int32_t *__restrict__ radii, const float *__restrict__ conics,
-                                                              const float *__restrict__ v_xy, const float *__restrict__ v_conic,
-                                                              const float *__restrict__ v_rgbs, const float *__restrict__ v_opac,
-                                                              float *__restrict__ v_means, float *__restrict__ v_ls,
-                                                              float *__restrict__ v_quats, float *__restrict__ v_oplogit,
-                                                              float *__restrict__ v_dc, float *__restrict__ v_rest,
-                                                              const float *__restrict__ v_depths /* [C][N], DEPTH only */)
+__global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatch cb, int n_use, const float *__restrict__ means,
+        const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ rgbs,
+        const int32_t *__restrict__ radii, const float *__restrict__ conics, const float *__restrict__ v_xy, const float *__restrict__ v_conic,
+        const float *__restrict__ v_rgbs, const float *__restrict__ v_opac, float *__restrict__ v_means, float *__restrict__ v_ls,
+        float *__restrict__ v_quats, float *__restrict__ v_oplogit, float *__restrict__ v_dc, float *__restrict__ v_rest,
+        const float *__restrict__ v_depths /* [C][N], DEPTH only */)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float svr[R > 0 ? 256 * R : 4];
     const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * 256;
-    const int64_t i = i0 + tid;
+    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
     float *vr = svr + tid * R;
     if (i < N) {
         float am[3] = {0.f, 0.f, 0.f}, as[3] = {0.f, 0.f, 0.f}, aq[4] = {0.f, 0.f, 0.f, 0.f}, aop = 0.f, adc[3] = {0.f, 0.f, 0.f};
@@ -652,95 +689,41 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatc
 #pragma unroll
         for (int k = 0; k < R; ++k) vr[k] = 0.f;
         bool first = true;          // the first contributing view ASSIGNS (0 + g would turn a -0 into +0: keep the single-view bits)
-        const float p0 = means[3 * i], p1 = means[3 * i + 1], p2 = means[3 * i + 2];
-        const float s0 = expf(log_scales[3 * i]), s1 = expf(log_scales[3 * i + 1]), s2 = expf(log_scales[3 * i + 2]);
-        const float4 qr = *reinterpret_cast<const float4 *>(quats + 4 * i);
-        const float qn = sqrtf(((qr.x * qr.x + qr.y * qr.y) + qr.z * qr.z) + qr.w * qr.w);
-        const float q0 = qr.x / qn, q1 = qr.y / qn, q2 = qr.z / qn, q3 = qr.w / qn;
-        const float op = sigmoidf(op_logit[i]);
+        Record r;
+        load_record<false>(r, i, means, log_scales, quats, op_logit, nullptr);
+        activate(r);
         for (int v = 0; v < cb.C; ++v) {
             const int64_t o = (int64_t)v * N + i;
             if (radii[o] <= 0) continue;
-            const Cam &cam = cb.cam[v];
-            ProjGrad g;
-            project_one_bwd(cam, p0, p1, p2, s0, s1, s2, q0, q1, q2, q3, conics[3 * o], conics[3 * o + 1], conics[3 * o + 2],
-                            v_xy[2 * o], v_xy[2 * o + 1], DEPTH ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1], v_conic[3 * o + 2], g);
-            const float dq = q0 * g.vq[0] + q1 * g.vq[1] + q2 * g.vq[2] + q3 * g.vq[3];
-            const float gq[4] = {(g.vq[0] - q0 * dq) / qn, (g.vq[1] - q1 * dq) / qn, (g.vq[2] - q2 * dq) / qn, (g.vq[3] - q3 * dq) / qn};
-            const float gls[3] = {g.vs[0] * s0, g.vs[1] * s1, g.vs[2] * s2};
-            const float gop = v_opac[o] * op * (1.f - op);
-            const float r0 = rgbs[3 * o], r1 = rgbs[3 * o + 1], r2 = rgbs[3 * o + 2];
-            float gdc[3], v0 = 0.f, v1 = 0.f, v2 = 0.f;
-            float B[16];
-            int Ku = 0;
-            if (n_use < 0) {
-                gdc[0] = v_rgbs[3 * o] * r0 * (1.f - r0); gdc[1] = v_rgbs[3 * o + 1] * r1 * (1.f - r1); gdc[2] = v_rgbs[3 * o + 2] * r2 * (1.f - r2);
-#pragma unroll
-                for (int k = 0; k < 16; ++k) B[k] = 0.f;
-            } else {
-                float dx = p0 - cam.ox, dy = p1 - cam.oy, dz = p2 - cam.oz;
-                float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-                dx = dx / dn; dy = dy / dn; dz = dz / dn;
-                sh_basis(n_use, dx, dy, dz, B);
-                Ku = (n_use + 1) * (n_use + 1);
-                v0 = r0 > 0.f ? v_rgbs[3 * o] : 0.f;
-                v1 = r1 > 0.f ? v_rgbs[3 * o + 1] : 0.f;
-                v2 = r2 > 0.f ? v_rgbs[3 * o + 2] : 0.f;
-                gdc[0] = B[0] * v0; gdc[1] = B[0] * v1; gdc[2] = B[0] * v2;
-            }
+            GeomGrad g;
+            geom_vjp<DEPTH>(cb.cam[v], r, o, conics, v_xy, v_conic, v_opac, v_depths, g);
+            ColourGrad c;
+            colour_vjp(cb.cam[v], r, o, n_use, rgbs, v_rgbs, c);
             if (first) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { am[k] = g.vm[k]; as[k] = gls[k]; adc[k] = gdc[k]; }
+                for (int k = 0; k < 3; ++k) { am[k] = g.vm[k]; as[k] = g.gls[k]; adc[k] = c.gdc[k]; }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) aq[k] = gq[k];
-                aop = gop;
-#pragma unroll
-                for (int k = 1; k < K; ++k) {
-                    const float b = k < Ku ? B[k] : 0.f;
-                    vr[3 * (k - 1)] = b * v0; vr[3 * (k - 1) + 1] = b * v1; vr[3 * (k - 1) + 2] = b * v2;
-                }
+                for (int k = 0; k < 4; ++k) aq[k] = g.gq[k];
+                aop = g.gop;
+                rest_row<K, false>(vr, c);
                 first = false;
             } else {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { am[k] = am[k] + g.vm[k]; as[k] = as[k] + gls[k]; adc[k] = adc[k] + gdc[k]; }
+                for (int k = 0; k < 3; ++k) { am[k] = am[k] + g.vm[k]; as[k] = as[k] + g.gls[k]; adc[k] = adc[k] + c.gdc[k]; }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) aq[k] = aq[k] + gq[k];
-                aop = aop + gop;
-#pragma unroll
-                for (int k = 1; k < K; ++k) {
-                    const float b = k < Ku ? B[k] : 0.f;
-                    vr[3 * (k - 1)] = vr[3 * (k - 1)] + b * v0; vr[3 * (k - 1) + 1] = vr[3 * (k - 1) + 1] + b * v1;
-                    vr[3 * (k - 1) + 2] = vr[3 * (k - 1) + 2] + b * v2;
-                }
+                for (int k = 0; k < 4; ++k) aq[k] = aq[k] + g.gq[k];
+                aop = aop + g.gop;
+                rest_row<K, true>(vr, c);
             }
         }
-        if (ACC) {
-            if (!first) {
+        if (!ACC || !first) {       // (ACC and no view contributed: nothing to add)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { v_means[3 * i + k] += am[k]; v_ls[3 * i + k] += as[k]; v_dc[3 * i + k] += adc[k]; }
-                float4 o4 = *reinterpret_cast<const float4 *>(v_quats + 4 * i);
-                o4.x += aq[0]; o4.y += aq[1]; o4.z += aq[2]; o4.w += aq[3];
-                *reinterpret_cast<float4 *>(v_quats + 4 * i) = o4;
-                v_oplogit[i] += aop;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { v_means[3 * i + k] = am[k]; v_ls[3 * i + k] = as[k]; v_dc[3 * i + k] = adc[k]; }
-            *reinterpret_cast<float4 *>(v_quats + 4 * i) = make_float4(aq[0], aq[1], aq[2], aq[3]);
-            v_oplogit[i] = aop;
+            for (int k = 0; k < 3; ++k) { put<ACC>(v_means + 3 * i + k, am[k]); put<ACC>(v_ls + 3 * i + k, as[k]); put<ACC>(v_dc + 3 * i + k, adc[k]); }
+            put4<ACC>(v_quats + 4 * i, aq);
+            put<ACC>(v_oplogit + i, aop);
         }
     }
-    if (R > 0) {
-        __syncthreads();
-        const int64_t cnt = ((N - i0 < 256 ? N - i0 : 256)) * R;
-        float *dst = v_rest + i0 * R;
-        for (int64_t j = tid; j < cnt / 4; j += 256) {
-            float4 v = reinterpret_cast<const float4 *>(svr)[j];
-            if (ACC) { const float4 o = reinterpret_cast<const float4 *>(dst)[j]; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-            reinterpret_cast<float4 *>(dst)[j] = v;
-        }
-        for (int64_t j = (cnt / 4) * 4 + tid; j < cnt; j += 256) dst[j] = ACC ? dst[j] + svr[j] : svr[j];
-    }
+    flush_rest_out<R, ACC>(svr, v_rest, N, i0, tid);
 }
 
 // img_out == img_raw: in place.  Otherwise the un-clamped image stays where the compositing wrote it (the backward needs it for the
@@ -767,6 +750,121 @@ Cam make_cam(const float *viewmat, const float *projmat, float fx, float fy, flo
     c.clip = clip; c.glob = glob;
     c.ox = origin ? origin[0] : 0.f; c.oy = origin ? origin[1] : 0.f; c.oz = origin ? origin[2] : 0.f;
     return c;
+}
+
+
+// ---------------------------------------------------------------- host side of the fused product path
+// What the entry points of one direction share, in the order of their C parameter lists; the extern "C" wrappers fill one and name themselves.
+struct FwdArgs {
+    int64_t N;
+    const float *means, *log_scales, *quats, *opacity_logits, *features_dc, *features_rest;
+    int sh_degree, degrees_to_use, img_h, img_w, tiles_x, tiles_y;
+    float clip_thresh, *xys, *depths;
+    int32_t *radii; float *conics; int32_t *num_tiles_hit;
+    float *rgbs, *opac;
+    uint32_t *tile_boxes;                                                 // NULL: gsplat's boxes
+    void *stream;
+};
+
+struct BwdArgs {
+    int64_t N;
+    const float *means, *log_scales, *quats, *opacity_logits, *rgbs;      // rgbs ... v_opac: per view, [C][N][..] for the batched entries
+    int sh_degree, degrees_to_use, img_h, img_w;
+    const int32_t *radii;
+    const float *conics, *v_xy, *v_conic, *v_rgbs, *v_opac;
+    float *v_means, *v_log_scales, *v_quats, *v_opacity_logits, *v_features_dc, *v_features_rest;
+    const float *v_depths;                                                // NULL: the entries without a depth gradient
+    void *stream;
+};
+
+struct CamArgs { const float *viewmat, *projmat, *origin; float fx, fy, cx, cy; };      // one camera, HOST pointers
+
+// one view of a `cams` array: viewmat[12] | projmat[16] | cam_origin[3] | fx fy cx cy (GC_VIEW_CAM_FLOATS = 35)
+CamArgs packed_cam(const float *c) { return CamArgs{c, c + 12, c + 28, c[31], c[32], c[33], c[34]}; }
+
+Cam make_cam(const CamArgs &c, int H, int W, int tx, int ty, float clip) { return make_cam(c.viewmat, c.projmat, c.fx, c.fy, c.cx, c.cy, H, W, tx, ty, clip, 1.f, c.origin); }
+
+CamBatch make_cams(const float *cams, int v0, int nv, int img_h, int img_w, int tx, int ty, float clip)
+{
+    CamBatch cb;
+    cb.C = nv;
+    for (int v = 0; v < nv; ++v) cb.cam[v] = make_cam(packed_cam(cams + (size_t)(v0 + v) * 35), img_h, img_w, tx, ty, clip);
+    return cb;
+}
+
+// The template instantiation for a run-time choice: f is called with a std::integral_constant.
+template <class F>
+void for_sh_degree(int sh_degree, F f)       // f(K): K = (sh_degree + 1)^2 SH bases
+{
+    switch (sh_degree) {
+    case 0: f(std::integral_constant<int, 1>{}); break;
+    case 1: f(std::integral_constant<int, 4>{}); break;
+    case 2: f(std::integral_constant<int, 9>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
+template <class F>
+void for_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
+// Launches for one camera (Cam) or one group of views (CamBatch); o = element offset of the group's first view in the per-view arrays.
+template <int K> constexpr auto project_sh_fwd_kernel(const Cam &) { return k_project_sh_fwd<K>; }
+template <int K> constexpr auto project_sh_fwd_kernel(const CamBatch &) { return k_project_sh_fwd_views<K>; }
+template <int K, bool ACC, bool DEPTH> constexpr auto project_sh_bwd_kernel(const Cam &) { return k_project_sh_bwd<K, ACC, DEPTH>; }
+template <int K, bool ACC, bool DEPTH> constexpr auto project_sh_bwd_kernel(const CamBatch &) { return k_project_sh_bwd_views<K, ACC, DEPTH>; }
+
+
+template <class CamT, class... Pairs>       // Pairs: the batched kernel's trailing depth_pairs
+void launch_project_sh_fwd(const FwdArgs &a, const CamT &cam, size_t o, Pairs... pairs)
+{
+    for_sh_degree(a.sh_degree, [&](auto K) {
+        hipLaunchKernelGGL(project_sh_fwd_kernel<decltype(K)::value>(cam), dim3(gc::cdiv(a.N, 256)), dim3(256), 0, gc::S(a.stream), a.N, cam,
+                           a.degrees_to_use, a.means, a.log_scales, a.quats, a.opacity_logits, a.features_dc, a.features_rest, a.xys + 2 * o,
+                           a.depths + o, a.radii + o, a.conics + 3 * o, a.num_tiles_hit + o, a.rgbs + 3 * o, a.opac,
+                           a.tile_boxes ? a.tile_boxes + o : nullptr, pairs...);
+    });
+}
+
+template <class CamT>
+void launch_project_sh_bwd(const BwdArgs &a, const CamT &cam, bool acc, size_t o)
+{
+    for_sh_degree(a.sh_degree, [&](auto K) { for_flag(acc, [&](auto ACC) { for_flag(a.v_depths != nullptr, [&](auto DEPTH) {
+        hipLaunchKernelGGL((project_sh_bwd_kernel<decltype(K)::value, decltype(ACC)::value, decltype(DEPTH)::value>(cam)),
+                           dim3(gc::cdiv(a.N, 256)), dim3(256), 0, gc::S(a.stream), a.N, cam, a.degrees_to_use, a.means, a.log_scales,
+                           a.quats, a.opacity_logits, a.rgbs + 3 * o, a.radii + o, a.conics + 3 * o, a.v_xy + 2 * o, a.v_conic + 3 * o,
+                           a.v_rgbs + 3 * o, a.v_opac + o, a.v_means, a.v_log_scales, a.v_quats, a.v_opacity_logits, a.v_features_dc,
+                           a.v_features_rest, a.v_depths ? a.v_depths + o : nullptr);
+    }); }); });
+}
+
+int project_sh_fwd_impl(const char *what, const FwdArgs &a, const CamArgs &c)
+{
+    GC_REQUIRE(a.sh_degree >= 0 && a.sh_degree <= 3 && a.degrees_to_use >= -1 && a.degrees_to_use <= a.sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
+    GC_REQUIRE(c.viewmat && c.projmat && c.origin, "camera pointers are host pointers and must not be NULL");
+    if (a.N == 0) return GC_OK;
+    launch_project_sh_fwd(a, make_cam(c, a.img_h, a.img_w, a.tiles_x, a.tiles_y, a.clip_thresh), 0);
+    return gc::check_launch(what);
+}
+
+int project_sh_bwd_impl(const char *what, bool accumulate, const BwdArgs &a, const CamArgs &c)
+{
+    GC_REQUIRE(a.sh_degree >= 0 && a.sh_degree <= 3 && a.degrees_to_use >= -1 && a.degrees_to_use <= a.sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
+    GC_REQUIRE(c.viewmat && c.projmat && c.origin, "camera pointers are host pointers and must not be NULL");
+    if (a.N == 0) return GC_OK;
+    launch_project_sh_bwd(a, make_cam(c, a.img_h, a.img_w, 0, 0, 0.f), accumulate, 0);
+    return gc::check_launch(what);
+}
+
+// Views are processed in groups of 8 (one launch per group: the cameras travel as kernel arguments); a later group adds to the first one's sums.
+int project_sh_bwd_views_impl(const char *what, int C, int accumulate, const BwdArgs &a, const float *cams)
+{
+    GC_REQUIRE(a.sh_degree >= 0 && a.sh_degree <= 3 && a.degrees_to_use >= -1 && a.degrees_to_use <= a.sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
+    GC_REQUIRE(cams && C >= 1, "cams is a host pointer and must not be NULL");
+    if (a.N == 0) return GC_OK;
+    for (int v0 = 0; v0 < C; v0 += MAXV)
+        launch_project_sh_bwd(a, make_cams(cams, v0, C - v0 < MAXV ? C - v0 : MAXV, a.img_h, a.img_w, 0, 0, 0.f), accumulate || v0 > 0,
+                              (size_t)v0 * (size_t)a.N);
+    return gc::check_launch(what);
 }
 
 }  // namespace
@@ -823,200 +921,98 @@ int gc_sh_bwd(int64_t N, int degree, int degrees_to_use, const float *viewdirs, 
     return gc::check_launch("gc_sh_bwd");
 }
 
-#define GC_SH_DISPATCH(KERNEL, ...)                                                                               \
-    switch (sh_degree) {                                                                                          \
-    case 0: hipLaunchKernelGGL(KERNEL<1>, dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), __VA_ARGS__); break; \
-    case 1: hipLaunchKernelGGL(KERNEL<4>, dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL(KERNEL<9>, dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<16>, dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), __VA_ARGS__); break; \
-    }
-
-static int project_sh_fwd_impl(const char *what, int64_t N, const float *means, const float *log_scales, const float *quats,
-                      const float *opacity_logits, const float *features_dc, const float *features_rest,
-                      int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                      const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                      int tiles_x, int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii,
-                      float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, uint32_t *tile_boxes, void *stream)
+int gc_project_sh_fwd(int64_t N, const float *means, const float *log_scales, const float *quats, const float *opacity_logits,
+        const float *features_dc, const float *features_rest, int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
+        const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w, int tiles_x, int tiles_y, float clip_thresh,
+        float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, void *stream)
 {
-    GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
-    GC_REQUIRE(viewmat && projmat && cam_origin, "camera pointers are host pointers and must not be NULL");
-    if (N == 0) return GC_OK;
-    Cam cam = make_cam(viewmat, projmat, fx, fy, cx, cy, img_h, img_w, tiles_x, tiles_y, clip_thresh, 1.f, cam_origin);
-    GC_SH_DISPATCH(k_project_sh_fwd, N, cam, degrees_to_use, means, log_scales, quats, opacity_logits, features_dc,
-                   features_rest, xys, depths, radii, conics, num_tiles_hit, rgbs, opac, tile_boxes)
-    return gc::check_launch(what);
-}
-
-int gc_project_sh_fwd(int64_t N, const float *means, const float *log_scales, const float *quats,
-                      const float *opacity_logits, const float *features_dc, const float *features_rest,
-                      int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                      const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                      int tiles_x, int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii,
-                      float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, void *stream)
-{
-    return project_sh_fwd_impl("gc_project_sh_fwd", N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use,
-                               viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, tiles_x, tiles_y, clip_thresh, xys, depths, radii, conics,
-                               num_tiles_hit, rgbs, opac, nullptr, stream);
+    const FwdArgs a{N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use, img_h, img_w, tiles_x,
+                    tiles_y, clip_thresh, xys, depths, radii, conics, num_tiles_hit, rgbs, opac, nullptr, stream};
+    return project_sh_fwd_impl("gc_project_sh_fwd", a, CamArgs{viewmat, projmat, cam_origin, fx, fy, cx, cy});
 }
 
 /* The same with TIGHT tile boxes: tile_boxes[N] (packed, see tight_tile_box) and num_tiles_hit count only the tiles of the bounding box
  * of the alpha >= 1/255 ellipse inside gsplat's box; feed both to gc_raster_depth_order / gc_raster_bin_tiles_boxes. */
-int gc_project_sh_fwd_boxes(int64_t N, const float *means, const float *log_scales, const float *quats,
-                            const float *opacity_logits, const float *features_dc, const float *features_rest,
-                            int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                            const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                            int tiles_x, int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii,
-                            float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, uint32_t *tile_boxes, void *stream)
+int gc_project_sh_fwd_boxes(int64_t N, const float *means, const float *log_scales, const float *quats, const float *opacity_logits,
+        const float *features_dc, const float *features_rest, int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
+        const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w, int tiles_x, int tiles_y, float clip_thresh,
+        float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, uint32_t *tile_boxes,
+        void *stream)
 {
     GC_REQUIRE(tile_boxes && tiles_x <= 255 && tiles_y <= 255, "tile_boxes required; packed boxes hold at most 255 x 255 tiles (use gc_project_sh_fwd beyond)");
-    return project_sh_fwd_impl("gc_project_sh_fwd_boxes", N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use,
-                               viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, tiles_x, tiles_y, clip_thresh, xys, depths, radii, conics,
-                               num_tiles_hit, rgbs, opac, tile_boxes, stream);
+    const FwdArgs a{N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use, img_h, img_w, tiles_x,
+                    tiles_y, clip_thresh, xys, depths, radii, conics, num_tiles_hit, rgbs, opac, tile_boxes, stream};
+    return project_sh_fwd_impl("gc_project_sh_fwd_boxes", a, CamArgs{viewmat, projmat, cam_origin, fx, fy, cx, cy});
 }
 
-static int project_sh_bwd_impl(const char *what, bool accumulate, const float *v_depths, int64_t N, const float *means, const float *log_scales, const float *quats,
-                      const float *opacity_logits, const float *rgbs,
-                      int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                      const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                      const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                      const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                      float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
+int gc_project_sh_bwd(int64_t N, const float *means, const float *log_scales, const float *quats, const float *opacity_logits, const float *rgbs,
+        int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat, const float *cam_origin, float fx, float fy, float cx,
+        float cy, int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic, const float *v_rgbs,
+        const float *v_opac, float *v_means, float *v_log_scales, float *v_quats, float *v_opacity_logits, float *v_features_dc,
+        float *v_features_rest, void *stream)
 {
-    GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
-    GC_REQUIRE(viewmat && projmat && cam_origin, "camera pointers are host pointers and must not be NULL");
-    if (N == 0) return GC_OK;
-    Cam cam = make_cam(viewmat, projmat, fx, fy, cx, cy, img_h, img_w, 0, 0, 0.f, 1.f, cam_origin);
-#define GC_BWD_L(KK, ACC, DEPTH) hipLaunchKernelGGL((k_project_sh_bwd<KK, ACC, DEPTH>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWD_ARGS)
-#define GC_BWD_K(KK) \
-    do { if (v_depths) { if (accumulate) GC_BWD_L(KK, true, true); else GC_BWD_L(KK, false, true); } \
-         else if (accumulate) GC_BWD_L(KK, true, false); \
-         else GC_BWD_L(KK, false, false); } while (0)
-#define GC_BWD_ARGS N, cam, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths
-    switch (sh_degree) { case 0: GC_BWD_K(1); break; case 1: GC_BWD_K(4); break; case 2: GC_BWD_K(9); break; default: GC_BWD_K(16); break; }
-#undef GC_BWD_K
-#undef GC_BWD_L
-#undef GC_BWD_ARGS
-    return gc::check_launch(what);
-}
-
-int gc_project_sh_bwd(int64_t N, const float *means, const float *log_scales, const float *quats,
-                      const float *opacity_logits, const float *rgbs,
-                      int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                      const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                      const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                      const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                      float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
-{
-    return project_sh_bwd_impl("gc_project_sh_bwd", false, nullptr, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    const BwdArgs a{N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+                    v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, nullptr, stream};
+    return project_sh_bwd_impl("gc_project_sh_bwd", false, a, CamArgs{viewmat, projmat, cam_origin, fx, fy, cx, cy});
 }
 
 /* Same, but the six outputs are ACCUMULATED into (+=): gradient accumulation over the views of a batch inside the kernel. */
-int gc_project_sh_bwd_accumulate(int64_t N, const float *means, const float *log_scales, const float *quats,
-                      const float *opacity_logits, const float *rgbs,
-                      int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat,
-                      const float *cam_origin, float fx, float fy, float cx, float cy, int img_h, int img_w,
-                      const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                      const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                      float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
+int gc_project_sh_bwd_accumulate(int64_t N, const float *means, const float *log_scales, const float *quats, const float *opacity_logits,
+        const float *rgbs, int sh_degree, int degrees_to_use, const float *viewmat, const float *projmat, const float *cam_origin, float fx, float fy,
+        float cx, float cy, int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
+        const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats, float *v_opacity_logits, float *v_features_dc,
+        float *v_features_rest, void *stream)
 {
-    return project_sh_bwd_impl("gc_project_sh_bwd", true, nullptr, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, viewmat, projmat, cam_origin, fx, fy, cx, cy, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    const BwdArgs a{N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+                    v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, nullptr, stream};
+    return project_sh_bwd_impl("gc_project_sh_bwd_accumulate", true, a, CamArgs{viewmat, projmat, cam_origin, fx, fy, cx, cy});
 }
 
 /* ---- C views per launch (round 5).  cams: HOST float array [C][GC_VIEW_CAM_FLOATS = 35] = viewmat[12] | projmat[16] | cam_origin[3] |
  * fx fy cx cy per view; all views share H, W and the tile grid.  Views are processed in groups of 8 (one launch per group: the cameras
  * travel as kernel arguments); outputs are [C][N][..] except opac [N].  tile_boxes / depth_pairs optional (NULL). */
-static int fill_cams(CamBatch &cb, const float *cams, int v0, int nv, int img_h, int img_w, int tx, int ty, float clip)
-{
-    cb.C = nv;
-    for (int v = 0; v < nv; ++v) {
-        const float *c = cams + (size_t)(v0 + v) * 35;
-        cb.cam[v] = make_cam(c, c + 12, c[31], c[32], c[33], c[34], img_h, img_w, tx, ty, clip, 1.f, c + 28);
-    }
-    return 0;
-}
-
-int gc_project_sh_fwd_views(int64_t N, int C, const float *means, const float *log_scales, const float *quats,
-                            const float *opacity_logits, const float *features_dc, const float *features_rest,
-                            int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w,
-                            int tiles_x, int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii,
-                            float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac, uint32_t *tile_boxes,
-                            uint32_t *depth_pairs, void *stream)
+int gc_project_sh_fwd_views(int64_t N, int C, const float *means, const float *log_scales, const float *quats, const float *opacity_logits,
+        const float *features_dc, const float *features_rest, int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w, int tiles_x,
+        int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac,
+        uint32_t *tile_boxes, uint32_t *depth_pairs, void *stream)
 {
     GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
     GC_REQUIRE(cams && C >= 1, "cams is a host pointer and must not be NULL");
     GC_REQUIRE(!tile_boxes || (tiles_x <= 255 && tiles_y <= 255), "packed boxes hold at most 255 x 255 tiles");
     if (N == 0) return GC_OK;
-    for (int v0 = 0; v0 < C; v0 += MAXV) {
-        CamBatch cb;
-        fill_cams(cb, cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, tiles_x, tiles_y, clip_thresh);
-        const size_t o = (size_t)v0 * (size_t)N;
-        GC_SH_DISPATCH(k_project_sh_fwd_views, N, cb, degrees_to_use, means, log_scales, quats, opacity_logits, features_dc, features_rest,
-                       xys + 2 * o, depths + o, radii + o, conics + 3 * o, num_tiles_hit + o, rgbs + 3 * o, opac,
-                       tile_boxes ? tile_boxes + o : nullptr, depth_pairs ? (uint2 *)depth_pairs + o : nullptr)
-    }
+    const FwdArgs a{N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use, img_h, img_w, tiles_x,
+                    tiles_y, clip_thresh, xys, depths, radii, conics, num_tiles_hit, rgbs, opac, tile_boxes, stream};
+    for (int v0 = 0; v0 < C; v0 += MAXV)
+        launch_project_sh_fwd(a, make_cams(cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, tiles_x, tiles_y, clip_thresh),
+                              (size_t)v0 * (size_t)N, depth_pairs ? (uint2 *)depth_pairs + (size_t)v0 * (size_t)N : nullptr);
     return gc::check_launch("gc_project_sh_fwd_views");
-}
-
-static int project_sh_bwd_views_impl(const char *what, const float *v_depths, int64_t N, int C, int accumulate, const float *means,
-                                     const float *log_scales, const float *quats,
-                            const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
-                            int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                            const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                            float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
-{
-    GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
-    GC_REQUIRE(cams && C >= 1, "cams is a host pointer and must not be NULL");
-    if (N == 0) return GC_OK;
-    for (int v0 = 0; v0 < C; v0 += MAXV) {
-        CamBatch cb;
-        fill_cams(cb, cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, 0, 0, 0.f);
-        const size_t o = (size_t)v0 * (size_t)N;
-        const bool acc = accumulate || v0 > 0;
-#define GC_BWDV_ARGS N, cb, degrees_to_use, means, log_scales, quats, opacity_logits, rgbs + 3 * o, radii + o, conics + 3 * o, v_xy + 2 * o, v_conic + 3 * o, v_rgbs + 3 * o, v_opac + o, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths ? v_depths + o : nullptr
-#define GC_BWDV_L(KK, ACC, DEPTH) hipLaunchKernelGGL((k_project_sh_bwd_views<KK, ACC, DEPTH>), dim3(gc::cdiv(N, 256)), dim3(256), 0, gc::S(stream), GC_BWDV_ARGS)
-#define GC_BWDV_K(KK) \
-        do { if (v_depths) { if (acc) GC_BWDV_L(KK, true, true); else GC_BWDV_L(KK, false, true); } \
-             else if (acc) GC_BWDV_L(KK, true, false); \
-             else GC_BWDV_L(KK, false, false); } while (0)
-        switch (sh_degree) { case 0: GC_BWDV_K(1); break; case 1: GC_BWDV_K(4); break; case 2: GC_BWDV_K(9); break; default: GC_BWDV_K(16); break; }
-#undef GC_BWDV_K
-#undef GC_BWDV_L
-#undef GC_BWDV_ARGS
-    }
-    return gc::check_launch(what);
 }
 
 /* Backward over C views: rgbs / radii / conics / v_xy / v_conic / v_rgbs / v_opac are [C][N][..]; the six leaf gradients are the SUM over
  * the views, written (accumulate = 0) or added to the buffers' contents (accumulate = 1) once per group of 8 views. */
 int gc_project_sh_bwd_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
-                            const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
-                            int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                            const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                            float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
+        const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w,
+        const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic, const float *v_rgbs, const float *v_opac, float *v_means,
+        float *v_log_scales, float *v_quats, float *v_opacity_logits, float *v_features_dc, float *v_features_rest, void *stream)
 {
-    return project_sh_bwd_views_impl("gc_project_sh_bwd_views", nullptr, N, C, accumulate, means, log_scales, quats, opacity_logits, rgbs, sh_degree,
-                                     degrees_to_use, cams, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means, v_log_scales, v_quats,
-                                     v_opacity_logits, v_features_dc, v_features_rest, stream);
+    const BwdArgs a{N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+                    v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, nullptr, stream};
+    return project_sh_bwd_views_impl("gc_project_sh_bwd_views", C, accumulate, a, cams);
 }
 
 /* The same with a gradient on the projected depths: v_depths [C][N] (the v_extra of gc_rasterize_bwd_depth_views) enters each view's VJP as
  * d depth / d mean = row 2 of that view's matrix; a culled Gaussian (radii == 0) contributes nothing.  C = 1 runs the single-view kernel. */
 int gc_project_sh_bwd_depth_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
-                                  const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams,
-                                  int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic,
-                                  const float *v_rgbs, const float *v_opac, float *v_means, float *v_log_scales, float *v_quats,
-                                  float *v_opacity_logits, float *v_features_dc, float *v_features_rest, const float *v_depths, void *stream)
+        const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w,
+        const int32_t *radii, const float *conics, const float *v_xy, const float *v_conic, const float *v_rgbs, const float *v_opac, float *v_means,
+        float *v_log_scales, float *v_quats, float *v_opacity_logits, float *v_features_dc, float *v_features_rest, const float *v_depths,
+        void *stream)
 {
     GC_REQUIRE(v_depths, "v_depths is required (gc_project_sh_bwd_views is the form without it)");
-    if (C == 1 && cams) {
-        const float *c = cams;
-        return project_sh_bwd_impl("gc_project_sh_bwd_depth_views", accumulate != 0, v_depths, N, means, log_scales, quats, opacity_logits, rgbs, sh_degree,
-                                   degrees_to_use, c, c + 12, c + 28, c[31], c[32], c[33], c[34], img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
-                                   v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
-    }
-    return project_sh_bwd_views_impl("gc_project_sh_bwd_depth_views", v_depths, N, C, accumulate, means, log_scales, quats, opacity_logits, rgbs,
-                                     sh_degree, degrees_to_use, cams, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs, v_opac, v_means,
-                                     v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, stream);
+    const BwdArgs a{N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+                    v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths, stream};
+    if (C == 1 && cams) return project_sh_bwd_impl("gc_project_sh_bwd_depth_views", accumulate != 0, a, packed_cam(cams));
+    return project_sh_bwd_views_impl("gc_project_sh_bwd_depth_views", C, accumulate, a, cams);
 }
 
 int gc_raster_finalize(int64_t num_pixels, float *out_img, float *out_extra, const float *final_Ts, float *alpha,

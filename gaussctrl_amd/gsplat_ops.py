@@ -157,36 +157,28 @@ def bin_and_sort_gaussians(N, xys, depths, radii, num_tiles_hit, tile_bounds, wa
         # sync-free: buffers sized for the caller's capacity, count and overflow flag stay on the device.
         # Returns M = (count tensor, overflow tensor) instead of a host int.
         M = int(m_cap)
-        ids_s = torch.empty(M, dtype=torch.int32, device=dev)
-        keys_s = torch.empty(M, dtype=torch.int64, device=dev) if want_keys else None
         ovf = torch.empty(1, dtype=torch.int32, device=dev)
-        bb = int(lib.gc_raster_bin_workspace_bytes(L.i64(M)))
-        bws = torch.empty(bb, dtype=torch.uint8, device=dev)
-        if tile_boxes is not None:
-            L.check(lib.gc_raster_bin_tiles_boxes(L.i64(N), L.i64(M), L.ptr(cnt), L.ptr(ovf), L.ptr(order), L.ptr(cum), L.ptr(tile_boxes),
-                                                  L.ptr(depths), L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s), L.ptr(bins),
-                                                  L.ptr(keys_s), L.ptr(bws), L.C.c_size_t(bb), st), "gc_raster_bin_tiles_boxes")
-        else:
-            L.check(lib.gc_raster_bin_tiles_dev(L.i64(N), L.i64(M), L.ptr(cnt), L.ptr(ovf), L.ptr(order), L.ptr(cum), L.ptr(xys),
-                                                L.ptr(depths), L.ptr(radii), L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s),
-                                                L.ptr(bins), L.ptr(keys_s), L.ptr(bws), L.C.c_size_t(bb), st), "gc_raster_bin_tiles_dev")
-        return (cnt, ovf), keys_s, ids_s, bins, cum
-    m_host = L.C.c_int32(0)
-    L.check(lib.gc_raster_read_count(L.ptr(cnt), L.C.byref(m_host), st), "gc_raster_read_count")
-    M = int(m_host.value)
+        dev_cnt, ret_M = (L.ptr(cnt), L.ptr(ovf)), (cnt, ovf)
+    else:
+        m_host = L.C.c_int32(0)
+        L.check(lib.gc_raster_read_count(L.ptr(cnt), L.C.byref(m_host), st), "gc_raster_read_count")
+        M = int(m_host.value)
+        dev_cnt, ret_M = (None, None), M
     ids_s = torch.empty(M, dtype=torch.int32, device=dev)
     keys_s = torch.empty(M, dtype=torch.int64, device=dev) if want_keys else None
     bb = int(lib.gc_raster_bin_workspace_bytes(L.i64(M)))
     bws = torch.empty(bb, dtype=torch.uint8, device=dev)
+    out = (L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(keys_s), L.ptr(bws), L.C.c_size_t(bb), st)
     if tile_boxes is not None:
-        L.check(lib.gc_raster_bin_tiles_boxes(L.i64(N), L.i64(M), None, None, L.ptr(order), L.ptr(cum), L.ptr(tile_boxes), L.ptr(depths),
-                                              L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(keys_s),
-                                              L.ptr(bws), L.C.c_size_t(bb), st), "gc_raster_bin_tiles_boxes")
+        L.check(lib.gc_raster_bin_tiles_boxes(L.i64(N), L.i64(M), *dev_cnt, L.ptr(order), L.ptr(cum), L.ptr(tile_boxes), L.ptr(depths), *out),
+                "gc_raster_bin_tiles_boxes")
+    elif m_cap is not None:
+        L.check(lib.gc_raster_bin_tiles_dev(L.i64(N), L.i64(M), *dev_cnt, L.ptr(order), L.ptr(cum), L.ptr(xys), L.ptr(depths), L.ptr(radii), *out),
+                "gc_raster_bin_tiles_dev")
     else:
-        L.check(lib.gc_raster_bin_tiles(L.i64(N), L.i64(M), L.ptr(order), L.ptr(cum), L.ptr(xys), L.ptr(depths), L.ptr(radii),
-                                        L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(keys_s),
-                                        L.ptr(bws), L.C.c_size_t(bb), st), "gc_raster_bin_tiles")
-    return M, keys_s, ids_s, bins, cum
+        L.check(lib.gc_raster_bin_tiles(L.i64(N), L.i64(M), L.ptr(order), L.ptr(cum), L.ptr(xys), L.ptr(depths), L.ptr(radii), *out),
+                "gc_raster_bin_tiles")
+    return ret_M, keys_s, ids_s, bins, cum
 
 
 def bin_and_sort_gaussians_keys64(N, xys, depths, radii, num_tiles_hit, tile_bounds):
@@ -358,8 +350,46 @@ class RenderAux:
     depth_grad = False
 
 
-def _depth_grad_on(ctx, aux, want_depth):
-    return bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
+def _finalize(ctx, npix, img, dep, fT):
+    """alpha = 1 - T, depth / alpha, clamp(max=1).  Differentiable: the raw image stays for the clamp's backward (pre_clamp), no copy pass.
+    Returns (img, alpha, pre_clamp | None)."""
+    alpha = torch.empty_like(fT)
+    if any(ctx.needs_input_grad[:6]):
+        pre_clamp, img = img, torch.empty_like(img)
+        L.check(L.lib().gc_raster_finalize_into(L.i64(npix), L.ptr(pre_clamp), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), L.stream_ptr()),
+                "gc_raster_finalize_into")
+        return img, alpha, pre_clamp
+    L.check(L.lib().gc_raster_finalize(L.i64(npix), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), L.stream_ptr()), "gc_raster_finalize")
+    return img, alpha, None
+
+
+def _save_and_mark(ctx, aux, want_depth, saved, depths, dep):
+    """save_for_backward, with the two depth tensors when the depth image is differentiable (RenderAux.depth_grad); otherwise depth is
+    marked non-differentiable.  Returns the depth output (empty when there is none)."""
+    ctx.depth_grad = bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
+    if ctx.depth_grad:
+        ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
+        ctx.save_for_backward(*saved, depths, dep)
+    else:
+        ctx.save_for_backward(*saved)
+        if dep is not None:
+            ctx.mark_non_differentiable(dep)
+    return dep if dep is not None else torch.empty(0, device=saved[0].device)
+
+
+def _leaf_grad_buffers(aux, m, ls, q, dc, rest):
+    """The six leaf-gradient tensors the projection backward fills: RenderAux.grad_into's (validated) or fresh ones.
+    Returns (vm, vls, vq, vop, vdc, vrest), into (the caller's dict or None), acc (add to the buffers' contents)."""
+    N, dev = m.shape[0], m.device
+    into = aux.grad_into if aux is not None else None
+    if into is None:
+        return tuple(torch.empty(s, device=dev) for s in (m.shape, ls.shape, q.shape, (N,), dc.shape, rest.shape)), None, False
+    bufs = tuple(into[k] for k in ("means", "scales", "quats", "opacities", "features_dc", "features_rest"))
+    vm, vls, vq, vop, vdc, vrest = bufs
+    for t, ref in ((vm, m), (vls, ls), (vq, q), (vdc, dc), (vrest, rest)):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == ref.shape and t.device == dev
+    assert vop.is_contiguous() and vop.dtype == torch.float32 and vop.numel() == N and vop.device == dev
+    return bufs, into, bool(aux.grad_accumulate)
 
 
 class _RenderView(torch.autograd.Function):
@@ -402,32 +432,16 @@ class _RenderView(torch.autograd.Function):
         bg = _c(background)
         extra = depths if want_depth else None
         img, dep, fT, fi = _rasterize_fwd(H, W, tb, ids_s, bins, xys, conics, rgbs, opac, extra, bg)
-        alpha = torch.empty(H, W, device=dev)
-        if any(ctx.needs_input_grad[:6]):        # differentiable: the raw image stays for the clamp's backward, no copy pass
-            pre_clamp, img = img, torch.empty_like(img)
-            L.check(lib.gc_raster_finalize_into(L.i64(H * W), L.ptr(pre_clamp), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), st),
-                    "gc_raster_finalize_into")
-        else:
-            pre_clamp = None
-            L.check(lib.gc_raster_finalize(L.i64(H * W), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), st),
-                    "gc_raster_finalize")
+        img, alpha, pre_clamp = _finalize(ctx, H * W, img, dep, fT)
         if aux is not None:
             aux.xys, aux.radii, aux.num_tiles_hit, aux.M, aux.depths = xys, radii, nth, M, depths
             aux.tile_boxes = boxes
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
             aux.xys_grad = None
-        ctx.depth_grad = _depth_grad_on(ctx, aux, want_depth)
-        if ctx.depth_grad:
-            ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
-            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp, depths, dep)
-        else:
-            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
         ctx.meta = (cam, tb, N, sh_degree, int(sh_degree_to_use), V, P, O)
         ctx.aux = aux
-        if not ctx.depth_grad:
-            ctx.mark_non_differentiable(*( [dep] if dep is not None else []))
-        if dep is None:
-            dep = torch.empty(0, device=dev)
+        dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
+                             depths, dep)
         return img, alpha, dep
 
     @staticmethod
@@ -455,33 +469,20 @@ class _RenderView(torch.autograd.Function):
             v_xy, v_conic, v_col, v_op = _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp)
         if ctx.aux is not None:
             ctx.aux.xys_grad = v_xy
-        into = ctx.aux.grad_into if ctx.aux is not None else None
-        if into is not None:
-            vm, vls, vq, vop, vdc, vrest = (into[k] for k in ("means", "scales", "quats", "opacities", "features_dc", "features_rest"))
-            for t, ref in ((vm, m), (vls, ls), (vq, q), (vdc, dc), (vrest, rest)):
-                assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == ref.shape and t.device == dev
-            assert vop.is_contiguous() and vop.dtype == torch.float32 and vop.numel() == N and vop.device == dev
-            fn = L.lib().gc_project_sh_bwd_accumulate if ctx.aux.grad_accumulate else L.lib().gc_project_sh_bwd
-        else:
-            vm = torch.empty(N, 3, device=dev); vls = torch.empty(N, 3, device=dev); vq = torch.empty(N, 4, device=dev)
-            vop = torch.empty(N, device=dev); vdc = torch.empty(N, 3, device=dev)
-            vrest = torch.empty(rest.shape, device=dev)
-            fn = L.lib().gc_project_sh_bwd
+        (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
         if v_ex is not None:        # the compositing's v_extra is the projection's v_depths
-            acc = 1 if (into is not None and ctx.aux.grad_accumulate) else 0
             L.check(L.lib().gc_project_sh_bwd_depth_views(
-                L.i64(N), L.i32(1), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
+                L.i64(N), L.i32(1), L.i32(int(acc)), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
                 _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
                 L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), L.stream_ptr()),
                 "gc_project_sh_bwd_depth_views")
-            if into is not None:
-                return (None,) * 11
-            return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
-        L.check(fn(
-            L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
-            V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]), L.i32(H), L.i32(W),
-            L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-            L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.stream_ptr()), "gc_project_sh_bwd")
+        else:
+            fn = L.lib().gc_project_sh_bwd_accumulate if acc else L.lib().gc_project_sh_bwd
+            L.check(fn(
+                L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
+                V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]), L.i32(H), L.i32(W),
+                L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.stream_ptr()), "gc_project_sh_bwd_accumulate" if acc else "gc_project_sh_bwd")
         if into is not None:
             return (None,) * 11
         return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
@@ -580,31 +581,16 @@ class _RenderViews(torch.autograd.Function):
                                            L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac),
                                            L.ptr(depths if want_depth else None), L.ptr(bg), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(fi), st),
                 "gc_rasterize_fwd_views")
-        alpha = torch.empty(C, H, W, **f32)
-        if any(ctx.needs_input_grad[:6]):
-            pre_clamp, img = img, torch.empty_like(img)
-            L.check(lib.gc_raster_finalize_into(L.i64(C * H * W), L.ptr(pre_clamp), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), st),
-                    "gc_raster_finalize_into")
-        else:
-            pre_clamp = None
-            L.check(lib.gc_raster_finalize(L.i64(C * H * W), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), st), "gc_raster_finalize")
+        img, alpha, pre_clamp = _finalize(ctx, C * H * W, img, dep, fT)
         if aux is not None:
             aux.xys, aux.radii, aux.num_tiles_hit, aux.depths, aux.tile_boxes = xys, radii, nth, depths, boxes
             aux.M = (cnt, ovf)                          # per-view device counts / overflow flags ([C] each)
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, None
             aux.xys_grad = None
-        ctx.depth_grad = _depth_grad_on(ctx, aux, want_depth)
-        if ctx.depth_grad:
-            ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
-            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp, depths, dep)
-        else:
-            ctx.save_for_backward(m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp)
         ctx.meta = (cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, int(sh_degree_to_use))
         ctx.aux = aux
-        if dep is None:
-            dep = torch.empty(0, device=dev)
-        elif not ctx.depth_grad:
-            ctx.mark_non_differentiable(dep)
+        dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
+                             depths, dep)
         return img, alpha, dep
 
     @staticmethod
@@ -637,17 +623,8 @@ class _RenderViews(torch.autograd.Function):
                                                L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
         if ctx.aux is not None:
             ctx.aux.xys_grad = v_xy
-        into = ctx.aux.grad_into if ctx.aux is not None else None
-        acc = 0
-        if into is not None:
-            vm, vls, vq, vop, vdc, vrest = (into[k] for k in ("means", "scales", "quats", "opacities", "features_dc", "features_rest"))
-            for t, ref in ((vm, m), (vls, ls), (vq, q), (vdc, dc), (vrest, rest)):
-                assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == ref.shape and t.device == dev
-            assert vop.is_contiguous() and vop.dtype == torch.float32 and vop.numel() == N and vop.device == dev
-            acc = 1 if ctx.aux.grad_accumulate else 0
-        else:
-            vm = torch.empty(N, 3, device=dev); vls = torch.empty(N, 3, device=dev); vq = torch.empty(N, 4, device=dev)
-            vop = torch.empty(N, device=dev); vdc = torch.empty(N, 3, device=dev); vrest = torch.empty(rest.shape, device=dev)
+        (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
+        acc = int(acc)
         if with_depth:              # the compositing's v_extra is the projection's v_depths
             L.check(lib.gc_project_sh_bwd_depth_views(
                 L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,

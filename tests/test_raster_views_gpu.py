@@ -405,3 +405,94 @@ def test_sorted_boxes_chain_all_culled_and_capacity():
         ops.render_views(tp["means"], tp["scales"], tp["quats"], tp["opacities"], tp["features_dc"], tp["features_rest"], cams, _t(BG), False, 3, a2)
     ovf = a2.M[1].cpu().numpy(); cnt = a2.M[0].cpu().numpy()
     assert np.array_equal(ovf, (cnt > mmax // 2).astype(np.int32)) and ovf.max() == 1
+
+
+# ---------------------------------------------------------------------------------------- every instantiation of the shared projection pieces
+def _project_views(lib, L, ops, tp, cams, deg, n_use, W, H):
+    """gc_project_sh_fwd_views on the test scene: the per-view state [C][N][..] the projection backward takes"""
+    N, C = tp["means"].shape[0], len(cams)
+    f32 = dict(device=DEV, dtype=torch.float32); i32 = dict(device=DEV, dtype=torch.int32)
+    o = dict(xys=torch.empty(C, N, 2, **f32), depths=torch.empty(C, N, **f32), radii=torch.empty(C, N, **i32), conics=torch.empty(C, N, 3, **f32),
+             nth=torch.empty(C, N, **i32), rgbs=torch.empty(C, N, 3, **f32), opac=torch.empty(N, **f32), boxes=torch.empty(C, N, **i32))
+    tx, ty = (W + 15) // 16, (H + 15) // 16
+    L.check(lib.gc_project_sh_fwd_views(
+        L.i64(N), L.i32(C), L.ptr(tp["means"]), L.ptr(tp["scales"]), L.ptr(tp["quats"]), L.ptr(tp["opacities"]), L.ptr(tp["features_dc"]),
+        L.ptr(tp["features_rest"]), L.i32(deg), L.i32(n_use), ops._cams_host(cams), L.i32(H), L.i32(W), L.i32(tx), L.i32(ty), L.f32(0.01),
+        L.ptr(o["xys"]), L.ptr(o["depths"]), L.ptr(o["radii"]), L.ptr(o["conics"]), L.ptr(o["nth"]), L.ptr(o["rgbs"]), L.ptr(o["opac"]),
+        L.ptr(o["boxes"]), None, L.stream_ptr()), "gc_project_sh_fwd_views")
+    return o
+
+
+@pytest.mark.parametrize("deg", [0, 1, 2, 3])
+def test_every_sh_width_and_colour_mode_single_view_vs_views(deg):
+    """The bit-identity tests above run sh_degree = 3, sh_degree_to_use = 3 only.  Here every features_rest width K - 1 in {0, 3, 8, 15} and every
+    sh_degree_to_use from -1 (sigmoid colour mode) to the degree -- every instantiation of the four fused projection kernels -- at N = 299: one
+    full workgroup and one of 43 records (43 * 45 and 43 * 9 are 3 mod 4: the scalar tails of the 16-byte staging loops run), C = 3 cameras on a
+    33 x 17 image, the cloud larger than the camera orbit so that part of it lies behind a camera.
+      * forward: render_views == render_view per camera, exactly, for rgb / alpha / depth and the five projection tensors of RenderAux;
+      * backward, fixed incoming gradients (no atomics in these kernels, C <= 8: no tolerance): gc_project_sh_bwd_views == gc_project_sh_bwd then
+        gc_project_sh_bwd_accumulate per camera; gc_project_sh_bwd_depth_views over C = 3 == three calls of itself with C = 1 (the single-view
+        kernel), for accumulate = 0 and 1.  Written buffers start NaN-filled.  With accumulate = 1 they start at zero: x + ((g0 + g1) + g2) and
+        ((x + g0) + g1) + g2 associate differently for any other x, so only there is equality of the bits defined."""
+    from gaussctrl_amd import _lib as L, gsplat_ops as ops
+    lib = L.lib()
+    N, W, H, C = 299, 33, 17, 3
+    P = syn.make_gaussians(N, seed=5, sh_degree=deg, scale_mean=0.3)
+    P["means"][:, :] *= 3.0
+    cams, _ = _cams(C, W, H, 40.0, seed=9)
+    tz = np.stack([P["means"] @ np.asarray(list(c["viewmat"])[:12], np.float32).reshape(3, 4)[2, :3] + list(c["viewmat"])[11] for c in cams])
+    assert (tz <= 0.01).any(axis=1).any() and (tz > 0.01).any(axis=1).all(), "part of the cloud must lie behind a camera"
+    tp = {k: _t(v) for k, v in P.items()}
+    tp["opacities"] = tp["opacities"].reshape(-1).contiguous()
+    leaves = (tp["means"], tp["scales"], tp["quats"], tp["opacities"], tp["features_dc"], tp["features_rest"])
+    bgs = torch.rand(C, 3, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
+    g = torch.Generator(device=DEV).manual_seed(3)
+    v_xy = torch.randn(C, N, 2, device=DEV, generator=g); v_con = torch.randn(C, N, 3, device=DEV, generator=g)
+    v_col = torch.randn(C, N, 3, device=DEV, generator=g); v_op = torch.randn(C, N, device=DEV, generator=g)
+    v_dep = torch.randn(C, N, device=DEV, generator=g)
+    fresh = lambda fill: [torch.full_like(t, fill) for t in leaves]
+    names = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
+    st = L.stream_ptr()
+    for n_use in range(-1, deg + 1):
+        # ---- forward
+        aux = ops.RenderAux()
+        with torch.no_grad():
+            rgb, alpha, depth = ops.render_views(*leaves, cams, bgs, True, n_use, aux)
+        assert int(aux.M[1].max()) == 0 and bool((aux.radii > 0).any(dim=1).all())
+        for c, cam in enumerate(cams):
+            a1 = ops.RenderAux()
+            with torch.no_grad():
+                r1, al1, d1 = ops.render_view(*leaves, cam, bgs[c], True, n_use, a1)
+            assert torch.equal(rgb[c], r1) and torch.equal(alpha[c], al1) and torch.equal(depth[c], d1), (n_use, c)
+            for name in ("xys", "radii", "num_tiles_hit", "depths", "tile_boxes"):
+                assert torch.equal(getattr(aux, name)[c], getattr(a1, name)), (n_use, c, name)
+        # ---- backward
+        o = _project_views(lib, L, ops, tp, cams, deg, n_use, W, H)
+        assert torch.equal(o["radii"], aux.radii)
+        common = lambda c: (L.ptr(o["radii"][c]), L.ptr(o["conics"][c]), L.ptr(v_xy[c]), L.ptr(v_con[c]), L.ptr(v_col[c]), L.ptr(v_op[c]))
+        views = fresh(float("nan"))
+        L.check(lib.gc_project_sh_bwd_views(L.i64(N), L.i32(C), L.i32(0), *[L.ptr(t) for t in leaves[:4]], L.ptr(o["rgbs"]), L.i32(deg),
+                                            L.i32(n_use), ops._cams_host(cams), L.i32(H), L.i32(W), L.ptr(o["radii"]), L.ptr(o["conics"]),
+                                            L.ptr(v_xy), L.ptr(v_con), L.ptr(v_col), L.ptr(v_op), *[L.ptr(t) for t in views], st), "bwd views")
+        single = fresh(float("nan"))
+        for c, cam in enumerate(cams):
+            fn = lib.gc_project_sh_bwd_accumulate if c > 0 else lib.gc_project_sh_bwd
+            L.check(fn(L.i64(N), *[L.ptr(t) for t in leaves[:4]], L.ptr(o["rgbs"][c]), L.i32(deg), L.i32(n_use), L.host_floats(cam["viewmat"]),
+                       L.host_floats(cam["fullproj"]), L.host_floats(cam["origin"]), L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]),
+                       L.f32(cam["cy"]), L.i32(H), L.i32(W), *common(c), *[L.ptr(t) for t in single], st), "bwd single")
+        for a, b, name in zip(single, views, names):
+            assert torch.isfinite(b).all() and torch.equal(a, b), (n_use, name)
+        for accumulate in (0, 1):
+            start = 0.0 if accumulate else float("nan")
+            views, single = fresh(start), fresh(start)
+            L.check(lib.gc_project_sh_bwd_depth_views(
+                L.i64(N), L.i32(C), L.i32(accumulate), *[L.ptr(t) for t in leaves[:4]], L.ptr(o["rgbs"]), L.i32(deg), L.i32(n_use),
+                ops._cams_host(cams), L.i32(H), L.i32(W), L.ptr(o["radii"]), L.ptr(o["conics"]), L.ptr(v_xy), L.ptr(v_con), L.ptr(v_col),
+                L.ptr(v_op), *[L.ptr(t) for t in views], L.ptr(v_dep), st), "bwd depth views")
+            for c, cam in enumerate(cams):
+                L.check(lib.gc_project_sh_bwd_depth_views(
+                    L.i64(N), L.i32(1), L.i32(1 if (accumulate or c > 0) else 0), *[L.ptr(t) for t in leaves[:4]], L.ptr(o["rgbs"][c]),
+                    L.i32(deg), L.i32(n_use), ops._cams_host([cam]), L.i32(H), L.i32(W), *common(c), *[L.ptr(t) for t in single],
+                    L.ptr(v_dep[c]), st), "bwd depth single")
+            for a, b, name in zip(single, views, names):
+                assert torch.isfinite(b).all() and torch.equal(a, b), (n_use, accumulate, name)
