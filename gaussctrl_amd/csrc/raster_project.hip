@@ -9,6 +9,7 @@
 // arithmetic is written as explicit IEEE binary32 operations in a fixed order so that the integer
 // outputs (radii, tile boxes, num_tiles_hit -> sort keys) are bit-identical to the CPU oracle.
 #include "common.h"
+#include "../../include/gaussctrl_antialias.h"
 #include <type_traits>
 
 namespace {
@@ -72,15 +73,22 @@ struct Proj {
     float conic[3];
     int radius;
     int tiles_hit;
+    float comp;        // AA only: opacity compensation rho (0 when culled)
 };
 
 // SURVEY.md Appendix A.1; op order mirrors oracle/raster_ref.c::project_one exactly.
+// AA (rasterize_mode "antialiased" of later splatfacto / gsplat versions, the Mip-Splatting opacity compensation): also
+// o.comp = rho = sqrt(max(0, det(cov2d) / det(cov2d + 0.3 I))), formed from the un-blurred a0, d0 themselves ((a - 0.3)(d - 0.3) would cancel
+// for the sub-pixel splats the mode exists for); 0 for a culled Gaussian.  Every other output is the classic one bit for bit: a0 + 0.3f is
+// the same IEEE operation whether a0 has a name or not (-ffp-contract=off).
+template <bool AA = false>
 __device__ __forceinline__ bool project_one(const Cam &cam, float p0, float p1, float p2, float s0, float s1,
                                             float s2, float qw, float qx, float qy, float qz, Proj &o)
 {
     const float *V = cam.V, *P = cam.P;
     o.radius = 0; o.tiles_hit = 0; o.depth = 0.f; o.xy[0] = o.xy[1] = 0.f;
     o.conic[0] = o.conic[1] = o.conic[2] = 0.f;
+    if (AA) o.comp = 0.f;
 #pragma unroll
     for (int k = 0; k < 6; ++k) o.cov3d[k] = 0.f;
     float tx = ((V[0] * p0 + V[1] * p1) + V[2] * p2) + V[3];
@@ -107,11 +115,13 @@ __device__ __forceinline__ bool project_one(const Cam &cam, float p0, float p1, 
     float u10 = (t10 * c[0] + t11 * c[1]) + t12 * c[2];
     float u11 = (t10 * c[1] + t11 * c[3]) + t12 * c[4];
     float u12 = (t10 * c[2] + t11 * c[4]) + t12 * c[5];
-    float a = ((u00 * t00 + u01 * t01) + u02 * t02) + 0.3f;
+    float a0 = (u00 * t00 + u01 * t01) + u02 * t02, a = a0 + 0.3f;
     float b = (u00 * t10 + u01 * t11) + u02 * t12;
-    float d = ((u10 * t10 + u11 * t11) + u12 * t12) + 0.3f;
+    float d0 = (u10 * t10 + u11 * t11) + u12 * t12, d = d0 + 0.3f;
     float det = a * d - b * b;
     if (det == 0.f) return false;
+    float rho = 0.f;
+    if (AA) rho = sqrtf(fmaxf(0.f, (a0 * d0 - b * b) / det));      // (fmaxf drops a NaN: inf / inf of an overflowing covariance gives 0)
     float inv_det = 1.f / det;
     // written before the tile-box cull, like gsplat / the oracle (unobservable for culled splats)
     o.conic[0] = d * inv_det; o.conic[1] = -b * inv_det; o.conic[2] = a * inv_det;
@@ -132,18 +142,30 @@ __device__ __forceinline__ bool project_one(const Cam &cam, float p0, float p1, 
     if (area <= 0) return false;
     o.tiles_hit = area; o.depth = tz; o.radius = (int)radius;
     o.xy[0] = px; o.xy[1] = py;
+    if (AA) o.comp = rho;
     return true;
 }
 
 struct ProjGrad {
     float vm[3], vs[3], vq[4];
+    float rho;         // AA only: the compensation of this view, recomputed
 };
 
 // True VJP of project_one w.r.t. (mean, scale, raw quat); mirrors oracle orc_project_gaussians_bwd.
+// AA: v_rho, the cotangent of the compensation (v_opac * sigmoid(logit)), joins the cotangent of the blurred covariance [[a, b], [b, d]].
+// rho is RECOMPUTED here instead of read back from the forward's `compensation` array: T and Sigma are in registers anyway, the 21
+// multiply-adds are project_one's own (same operations in the same order under -ffp-contract=off, so the same bits), it saves the 4-byte
+// load per Gaussian and view, and it gives the un-blurred a0, d0, from which the derivative has no cancelling term.  With h = 0.3,
+// rho^2 = det0 / det and det - det0 = h (a0 + d0 + h):
+//     d rho^2 / da = h (d d0 + b^2) / det^2,   d rho^2 / dd = h (a a0 + b^2) / det^2,   d rho^2 / db = -2 b h (a0 + d0 + h) / det^2
+// (the forms (s X00 - h detX), (s X11 - h detX), 2 s X01 with s = 1 - rho^2 of the conic X, multiplied out), d rho = d rho^2 / (2 rho).
+// b stands for BOTH off-diagonal entries, so each of them takes half of d/db -- the convention of G01 = 0.5 g1 below.  rho == 0 (or a zero
+// cotangent, which is all a splat below 1/255 can receive) contributes nothing, and nothing is divided by it.
+template <bool AA = false>
 __device__ __forceinline__ void project_one_bwd(const Cam &cam, float p0, float p1, float p2, float s0, float s1,
                                                 float s2, float qw, float qx, float qy, float qz,
                                                 float X00, float X01, float X11, float vx, float vy, float vz,
-                                                float g0, float g1, float g2, ProjGrad &o)
+                                                float g0, float g1, float g2, ProjGrad &o, float v_rho = 0.f)
 {
     const float *V = cam.V, *P = cam.P;
     float hx = ((P[0] * p0 + P[1] * p1) + P[2] * p2) + P[3];
@@ -177,6 +199,27 @@ __device__ __forceinline__ void project_one_bwd(const Cam &cam, float p0, float 
     quat_to_rotmat(qw, qx, qy, qz, rot);
     scale_rot_to_cov3d(s0, s1, s2, cam.glob, rot.R, c3, M);
     float S[9] = {c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
+    if (AA) {
+        float u00 = (T[0] * c3[0] + T[1] * c3[1]) + T[2] * c3[2];
+        float u01 = (T[0] * c3[1] + T[1] * c3[3]) + T[2] * c3[4];
+        float u02 = (T[0] * c3[2] + T[1] * c3[4]) + T[2] * c3[5];
+        float u10 = (T[3] * c3[0] + T[4] * c3[1]) + T[5] * c3[2];
+        float u11 = (T[3] * c3[1] + T[4] * c3[3]) + T[5] * c3[4];
+        float u12 = (T[3] * c3[2] + T[4] * c3[4]) + T[5] * c3[5];
+        float a0 = (u00 * T[0] + u01 * T[1]) + u02 * T[2];
+        float b = (u00 * T[3] + u01 * T[4]) + u02 * T[5];
+        float d0 = (u10 * T[3] + u11 * T[4]) + u12 * T[5];
+        float a = a0 + 0.3f, d = d0 + 0.3f;
+        float det = a * d - b * b;
+        float rho = sqrtf(fmaxf(0.f, (a0 * d0 - b * b) / det));      // det != 0: the forward kept this Gaussian
+        o.rho = rho;
+        if (rho > 0.f && v_rho != 0.f) {
+            float k = (0.5f * v_rho / rho) * (0.3f / (det * det));
+            C00 += k * (d * d0 + b * b);
+            C11 += k * (a * a0 + b * b);
+            C01 -= k * (b * ((a0 + d0) + 0.3f));
+        }
+    }
     float GT[6];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { GT[k] = C00 * T[k] + C01 * T[3 + k]; GT[3 + k] = C01 * T[k] + C11 * T[3 + k]; }
@@ -434,15 +477,20 @@ __device__ __forceinline__ uint32_t tight_tile_box(const Cam &cam, const Proj &o
 // Projects Gaussian `id` for one camera and stores the view's projection state at element index o (o = id for a single view, view * N + id
 // in a batch).  tile_box (optional): the tight box, and the tiles_hit it implies -- nth and the box the emission walks shrink together.
 // depth_pairs (optional): the depth-order sort's input pair.  Returns project_one's verdict.
+// AA: the view's effective opacity sigmoid(logit) * rho goes to opac[o] and rho to compensation[o] (both per view), and the tight box is the
+// effective opacity's -- smaller, by the same argument: no dropped tile holds a pixel that passes alpha >= 1/255.
+template <bool AA = false>
 __device__ __forceinline__ bool store_view(const Cam &cam, const Record &r, int64_t o, int64_t id, float *xys, float *depths, int32_t *radii,
-        float *conics, int32_t *tiles_hit, uint32_t *tile_box, uint2 *depth_pairs)
+        float *conics, int32_t *tiles_hit, uint32_t *tile_box, uint2 *depth_pairs, float *opac = nullptr, float *compensation = nullptr)
 {
     Proj pr;
-    const bool ok = project_one(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], pr);
+    const bool ok = project_one<AA>(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], pr);
     xys[2 * o] = pr.xy[0]; xys[2 * o + 1] = pr.xy[1];
+    const float op_v = AA ? r.op * pr.comp : r.op;
+    if (AA) { opac[o] = op_v; compensation[o] = pr.comp; }
     if (tile_box) {
         uint32_t box = 0;
-        if (ok) box = tight_tile_box(cam, pr, r.op);
+        if (ok) box = tight_tile_box(cam, pr, op_v);
         tile_box[o] = box;
         pr.tiles_hit = (int)(((box >> 8) & 255u) - (box & 255u)) * (int)((box >> 24) - ((box >> 16) & 255u));
     }
@@ -501,21 +549,21 @@ __device__ __forceinline__ void put4(float *p, const float *v)
 // applied to the mean); without it the argument is the literal 0 it always was.
 struct GeomGrad { float vm[3], gls[3], gq[4], gop; };
 
-template <bool DEPTH>
+template <bool DEPTH, bool AA = false>
 __device__ __forceinline__ void geom_vjp(const Cam &cam, const Record &r, int64_t o, const float *conics, const float *v_xy, const float *v_conic,
                                          const float *v_opac, const float *v_depths, GeomGrad &g)
 {
     ProjGrad pg;
-    project_one_bwd(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], conics[3 * o], conics[3 * o + 1],
-                    conics[3 * o + 2], v_xy[2 * o], v_xy[2 * o + 1], DEPTH ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1],
-                    v_conic[3 * o + 2], pg);
+    project_one_bwd<AA>(cam, r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3], conics[3 * o], conics[3 * o + 1],
+                        conics[3 * o + 2], v_xy[2 * o], v_xy[2 * o + 1], DEPTH ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1],
+                        v_conic[3 * o + 2], pg, AA ? v_opac[o] * r.op : 0.f);      // AA: v_opac is of the view's sigmoid(logit) * rho
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g.vm[k] = pg.vm[k]; g.gls[k] = pg.vs[k] * r.s[k]; }
     // outer normalisation q/|q| (gc_model.py:144)
     const float dq = r.q[0] * pg.vq[0] + r.q[1] * pg.vq[1] + r.q[2] * pg.vq[2] + r.q[3] * pg.vq[3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) g.gq[k] = (pg.vq[k] - r.q[k] * dq) / r.qn;
-    g.gop = v_opac[o] * r.op * (1.f - r.op);
+    g.gop = AA ? (v_opac[o] * pg.rho) * r.op * (1.f - r.op) : v_opac[o] * r.op * (1.f - r.op);
 }
 
 // ColourGrad: the VJP of shade.  It needs only the FORWARD colours (rgbs): the clamp(min = 0) mask is rgbs > 0 and the sigmoid mode's
@@ -555,12 +603,13 @@ __device__ __forceinline__ void rest_row(float *vr, const ColourGrad &g)
 }
 
 // ---------------------------------------------------------------- kernels: fused product path, one camera
-template <int K>
+// AA: opac is the view's effective opacity and compensation its rho (store_view); the AA = false instantiation never touches `compensation`.
+template <int K, bool AA = false>
 __global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int n_use, const float *__restrict__ means,
         const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ f_dc,
         const float *__restrict__ f_rest, float *__restrict__ xys, float *__restrict__ depths, int32_t *__restrict__ radii,
         float *__restrict__ conics, int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs, float *__restrict__ opac,
-        uint32_t *__restrict__ tile_box)
+        uint32_t *__restrict__ tile_box, float *__restrict__ compensation)
 {
     constexpr int R = (K - 1) * 3;                         // floats of features_rest per Gaussian
     __shared__ __attribute__((aligned(16))) float srest[R > 0 ? 256 * R : 4];
@@ -574,8 +623,8 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int 
     bool ok = false;
     if (i < N) {
         activate(r);
-        ok = store_view(cam, r, i, i, xys, depths, radii, conics, tiles_hit, tile_box, nullptr);
-        opac[i] = r.op;
+        ok = store_view<AA>(cam, r, i, i, xys, depths, radii, conics, tiles_hit, tile_box, nullptr, opac, compensation);
+        if (!AA) opac[i] = r.op;
     }
     if (R > 0 && n_use > 0) __syncthreads();
     if (i >= N) return;
@@ -585,7 +634,8 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(int64_t N, Cam cam, int 
 
 // Backward of the above.  ACC: the six outputs are accumulated into (+=) instead of written -- gradient accumulation over the views of a
 // batch without a separate read-add-write pass per tensor (the caller owns zeroing / the first view runs with ACC = false).
-template <int K, bool ACC, bool DEPTH = false>
+// AA: v_opac is the cotangent of the view's effective opacity (geom_vjp / project_one_bwd).
+template <int K, bool ACC, bool DEPTH = false, bool AA = false>
 __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int n_use, const float *__restrict__ means,
         const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ rgbs,
         const int32_t *__restrict__ radii, const float *__restrict__ conics, const float *__restrict__ v_xy, const float *__restrict__ v_conic,
@@ -613,7 +663,7 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int 
             load_record<false>(r, i, means, log_scales, quats, op_logit, nullptr);
             activate(r);
             GeomGrad g;
-            geom_vjp<DEPTH>(cam, r, i, conics, v_xy, v_conic, v_opac, v_depths, g);
+            geom_vjp<DEPTH, AA>(cam, r, i, conics, v_xy, v_conic, v_opac, v_depths, g);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { put<ACC>(v_means + 3 * i + k, g.vm[k]); put<ACC>(v_ls + 3 * i + k, g.gls[k]); }
             put4<ACC>(v_quats + 4 * i, g.gq);
@@ -634,15 +684,16 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd(int64_t N, Cam cam, int 
 // 236 + C * 60 bytes per Gaussian instead of C * 296.  Per view it runs store_view and shade, the code of the single-view kernel: every output
 // of view c is bit-identical to what gc_project_sh_fwd[_boxes] writes for that camera.  Per-view outputs are [C][N][..]; `opac` (sigmoid of
 // the opacity logit, camera independent) is written once, [N]; depth_pairs (optional) are the depth-order sort's input pairs.
+// AA: opac and compensation are per view, [C][N] (what the compositing kernels take with shared_opacities = 0).
 constexpr int MAXV = 8;
 struct CamBatch { Cam cam[MAXV]; int C; };
 
-template <int K>
+template <int K, bool AA = false>
 __global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatch cb, int n_use, const float *__restrict__ means,
         const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ f_dc,
         const float *__restrict__ f_rest, float *__restrict__ xys, float *__restrict__ depths, int32_t *__restrict__ radii,
         float *__restrict__ conics, int32_t *__restrict__ tiles_hit, float *__restrict__ rgbs, float *__restrict__ opac,
-        uint32_t *__restrict__ tile_box, uint2 *__restrict__ depth_pairs)
+        uint32_t *__restrict__ tile_box, uint2 *__restrict__ depth_pairs, float *__restrict__ compensation)
 {
     constexpr int R = (K - 1) * 3;
     __shared__ __attribute__((aligned(16))) float srest[R > 0 ? 256 * R : 4];
@@ -656,11 +707,11 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatc
     }
     if (i >= N) return;
     activate(r);
-    opac[i] = r.op;
+    if (!AA) opac[i] = r.op;
     for (int v = 0; v < cb.C; ++v) {
         const Cam &cam = cb.cam[v];
         const int64_t o = (int64_t)v * N + i;
-        const bool ok = store_view(cam, r, o, i, xys, depths, radii, conics, tiles_hit, tile_box, depth_pairs);
+        const bool ok = store_view<AA>(cam, r, o, i, xys, depths, radii, conics, tiles_hit, tile_box, depth_pairs, opac, compensation);
         const float3 c = shade<K>(cam, r, srest + tid * R, n_use, ok);
         rgbs[3 * o] = c.x; rgbs[3 * o + 1] = c.y; rgbs[3 * o + 2] = c.z;
     }
@@ -669,7 +720,7 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd_views(int64_t N, CamBatc
 // Backward over C views: the parameter record is read once, the per-view VJPs (geom_vjp + colour_vjp, the code of the single-view kernel) are summed
 // in registers IN VIEW ORDER -- ((g_0 + g_1) + g_2) ..., the order C accumulating single-view launches produce -- and the 59 gradient floats
 // are written (or, ACC, added to what is there) ONCE per batch: N * (56 + C * 64) bytes read + N * 236 written instead of C * N * 344.
-template <int K, bool ACC, bool DEPTH = false>
+template <int K, bool ACC, bool DEPTH = false, bool AA = false>
 __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatch cb, int n_use, const float *__restrict__ means,
         const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit, const float *__restrict__ rgbs,
         const int32_t *__restrict__ radii, const float *__restrict__ conics, const float *__restrict__ v_xy, const float *__restrict__ v_conic,
@@ -696,7 +747,7 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatc
             const int64_t o = (int64_t)v * N + i;
             if (radii[o] <= 0) continue;
             GeomGrad g;
-            geom_vjp<DEPTH>(cb.cam[v], r, o, conics, v_xy, v_conic, v_opac, v_depths, g);
+            geom_vjp<DEPTH, AA>(cb.cam[v], r, o, conics, v_xy, v_conic, v_opac, v_depths, g);
             ColourGrad c;
             colour_vjp(cb.cam[v], r, o, n_use, rgbs, v_rgbs, c);
             if (first) {
@@ -764,6 +815,7 @@ struct FwdArgs {
     float *rgbs, *opac;
     uint32_t *tile_boxes;                                                 // NULL: gsplat's boxes
     void *stream;
+    float *compensation = nullptr;                                        // non-NULL: antialiased mode, opac and compensation per view
 };
 
 struct BwdArgs {
@@ -775,6 +827,7 @@ struct BwdArgs {
     float *v_means, *v_log_scales, *v_quats, *v_opacity_logits, *v_features_dc, *v_features_rest;
     const float *v_depths;                                                // NULL: the entries without a depth gradient
     void *stream;
+    bool antialiased = false;                                             // v_opac is of the per-view effective opacity
 };
 
 struct CamArgs { const float *viewmat, *projmat, *origin; float fx, fy, cx, cy; };      // one camera, HOST pointers
@@ -808,33 +861,34 @@ template <class F>
 void for_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 // Launches for one camera (Cam) or one group of views (CamBatch); o = element offset of the group's first view in the per-view arrays.
-template <int K> constexpr auto project_sh_fwd_kernel(const Cam &) { return k_project_sh_fwd<K>; }
-template <int K> constexpr auto project_sh_fwd_kernel(const CamBatch &) { return k_project_sh_fwd_views<K>; }
-template <int K, bool ACC, bool DEPTH> constexpr auto project_sh_bwd_kernel(const Cam &) { return k_project_sh_bwd<K, ACC, DEPTH>; }
-template <int K, bool ACC, bool DEPTH> constexpr auto project_sh_bwd_kernel(const CamBatch &) { return k_project_sh_bwd_views<K, ACC, DEPTH>; }
+template <int K, bool AA> constexpr auto project_sh_fwd_kernel(const Cam &) { return k_project_sh_fwd<K, AA>; }
+template <int K, bool AA> constexpr auto project_sh_fwd_kernel(const CamBatch &) { return k_project_sh_fwd_views<K, AA>; }
+template <int K, bool ACC, bool DEPTH, bool AA> constexpr auto project_sh_bwd_kernel(const Cam &) { return k_project_sh_bwd<K, ACC, DEPTH, AA>; }
+template <int K, bool ACC, bool DEPTH, bool AA> constexpr auto project_sh_bwd_kernel(const CamBatch &) { return k_project_sh_bwd_views<K, ACC, DEPTH, AA>; }
 
 
 template <class CamT, class... Pairs>       // Pairs: the batched kernel's trailing depth_pairs
 void launch_project_sh_fwd(const FwdArgs &a, const CamT &cam, size_t o, Pairs... pairs)
 {
-    for_sh_degree(a.sh_degree, [&](auto K) {
-        hipLaunchKernelGGL(project_sh_fwd_kernel<decltype(K)::value>(cam), dim3(gc::cdiv(a.N, 256)), dim3(256), 0, gc::S(a.stream), a.N, cam,
-                           a.degrees_to_use, a.means, a.log_scales, a.quats, a.opacity_logits, a.features_dc, a.features_rest, a.xys + 2 * o,
-                           a.depths + o, a.radii + o, a.conics + 3 * o, a.num_tiles_hit + o, a.rgbs + 3 * o, a.opac,
-                           a.tile_boxes ? a.tile_boxes + o : nullptr, pairs...);
-    });
+    for_sh_degree(a.sh_degree, [&](auto K) { for_flag(a.compensation != nullptr, [&](auto AA) {
+        hipLaunchKernelGGL((project_sh_fwd_kernel<decltype(K)::value, decltype(AA)::value>(cam)), dim3(gc::cdiv(a.N, 256)), dim3(256), 0,
+                           gc::S(a.stream), a.N, cam, a.degrees_to_use, a.means, a.log_scales, a.quats, a.opacity_logits, a.features_dc,
+                           a.features_rest, a.xys + 2 * o, a.depths + o, a.radii + o, a.conics + 3 * o, a.num_tiles_hit + o, a.rgbs + 3 * o,
+                           a.compensation ? a.opac + o : a.opac, a.tile_boxes ? a.tile_boxes + o : nullptr, pairs...,
+                           a.compensation ? a.compensation + o : nullptr);
+    }); });
 }
 
 template <class CamT>
 void launch_project_sh_bwd(const BwdArgs &a, const CamT &cam, bool acc, size_t o)
 {
-    for_sh_degree(a.sh_degree, [&](auto K) { for_flag(acc, [&](auto ACC) { for_flag(a.v_depths != nullptr, [&](auto DEPTH) {
-        hipLaunchKernelGGL((project_sh_bwd_kernel<decltype(K)::value, decltype(ACC)::value, decltype(DEPTH)::value>(cam)),
+    for_sh_degree(a.sh_degree, [&](auto K) { for_flag(acc, [&](auto ACC) { for_flag(a.v_depths != nullptr, [&](auto DEPTH) { for_flag(a.antialiased, [&](auto AA) {
+        hipLaunchKernelGGL((project_sh_bwd_kernel<decltype(K)::value, decltype(ACC)::value, decltype(DEPTH)::value, decltype(AA)::value>(cam)),
                            dim3(gc::cdiv(a.N, 256)), dim3(256), 0, gc::S(a.stream), a.N, cam, a.degrees_to_use, a.means, a.log_scales,
                            a.quats, a.opacity_logits, a.rgbs + 3 * o, a.radii + o, a.conics + 3 * o, a.v_xy + 2 * o, a.v_conic + 3 * o,
                            a.v_rgbs + 3 * o, a.v_opac + o, a.v_means, a.v_log_scales, a.v_quats, a.v_opacity_logits, a.v_features_dc,
                            a.v_features_rest, a.v_depths ? a.v_depths + o : nullptr);
-    }); }); });
+    }); }); }); });
 }
 
 int project_sh_fwd_impl(const char *what, const FwdArgs &a, const CamArgs &c)
@@ -1013,6 +1067,55 @@ int gc_project_sh_bwd_depth_views(int64_t N, int C, int accumulate, const float 
                     v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths, stream};
     if (C == 1 && cams) return project_sh_bwd_impl("gc_project_sh_bwd_depth_views", accumulate != 0, a, packed_cam(cams));
     return project_sh_bwd_views_impl("gc_project_sh_bwd_depth_views", C, accumulate, a, cams);
+}
+
+/* ---- Antialiased rasterize_mode (include/gaussctrl_antialias.h).  The forward over C views with the per-view opacity compensation: opac
+ * [C][N] = sigmoid(logit) * rho, compensation [C][N] = rho; everything else is what gc_project_sh_fwd_views writes, except that the tight
+ * boxes are the effective opacity's.  C = 1 without depth_pairs runs the single-view kernel (same per-view code, same bits). */
+int gc_project_sh_fwd_aa_views(int64_t N, int C, const float *means, const float *log_scales, const float *quats, const float *opacity_logits,
+        const float *features_dc, const float *features_rest, int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w, int tiles_x,
+        int tiles_y, float clip_thresh, float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *rgbs, float *opac,
+        float *compensation, uint32_t *tile_boxes, uint32_t *depth_pairs, void *stream)
+{
+    GC_REQUIRE(N >= 0 && C >= 1 && cams, "N >= 0, C >= 1; cams is a host pointer and must not be NULL");
+    GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
+    GC_REQUIRE(img_h > 0 && img_w > 0 && tiles_x > 0 && tiles_y > 0, "image and tile grid must not be empty");
+    GC_REQUIRE(!tile_boxes || (tiles_x <= 255 && tiles_y <= 255), "packed boxes hold at most 255 x 255 tiles");
+    if (N == 0) return GC_OK;
+    GC_REQUIRE(means && log_scales && quats && opacity_logits && features_dc && (features_rest || sh_degree == 0), "a parameter pointer is NULL");
+    GC_REQUIRE(xys && depths && radii && conics && num_tiles_hit && rgbs && opac && compensation, "an output pointer is NULL");
+    FwdArgs a{N, means, log_scales, quats, opacity_logits, features_dc, features_rest, sh_degree, degrees_to_use, img_h, img_w, tiles_x,
+              tiles_y, clip_thresh, xys, depths, radii, conics, num_tiles_hit, rgbs, opac, tile_boxes, stream};
+    a.compensation = compensation;
+    if (C == 1 && !depth_pairs)
+        launch_project_sh_fwd(a, make_cam(packed_cam(cams), img_h, img_w, tiles_x, tiles_y, clip_thresh), 0);
+    else
+        for (int v0 = 0; v0 < C; v0 += MAXV)
+            launch_project_sh_fwd(a, make_cams(cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, tiles_x, tiles_y, clip_thresh),
+                                  (size_t)v0 * (size_t)N, depth_pairs ? (uint2 *)depth_pairs + (size_t)v0 * (size_t)N : nullptr);
+    return gc::check_launch("gc_project_sh_fwd_aa_views");
+}
+
+/* Its backward: the arguments of gc_project_sh_bwd_depth_views, v_opac [C][N] being the cotangent of the per-view effective opacity (what the
+ * compositing backward returns with shared_opacities = 0).  v_depths may be NULL (no depth term).  `compensation` is the forward's array: it is
+ * validated and part of the contract, but the kernels recompute rho from the covariance they rebuild anyway (see project_one_bwd). */
+int gc_project_sh_bwd_aa_views(int64_t N, int C, int accumulate, const float *means, const float *log_scales, const float *quats,
+        const float *opacity_logits, const float *rgbs, int sh_degree, int degrees_to_use, const float *cams, int img_h, int img_w,
+        const int32_t *radii, const float *conics, const float *compensation, const float *v_xy, const float *v_conic, const float *v_rgbs,
+        const float *v_opac, float *v_means, float *v_log_scales, float *v_quats, float *v_opacity_logits, float *v_features_dc,
+        float *v_features_rest, const float *v_depths, void *stream)
+{
+    GC_REQUIRE(N >= 0 && C >= 1 && cams, "N >= 0, C >= 1; cams is a host pointer and must not be NULL");
+    GC_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && degrees_to_use >= -1 && degrees_to_use <= sh_degree, "SH degree must be 0..3 (degrees_to_use -1: sigmoid colour mode)");
+    if (N == 0) return GC_OK;
+    GC_REQUIRE(means && log_scales && quats && opacity_logits && rgbs && radii && conics && compensation, "an input pointer is NULL");
+    GC_REQUIRE(v_xy && v_conic && v_rgbs && v_opac, "a cotangent pointer is NULL");
+    GC_REQUIRE(v_means && v_log_scales && v_quats && v_opacity_logits && v_features_dc && (v_features_rest || sh_degree == 0), "an output pointer is NULL");
+    BwdArgs a{N, means, log_scales, quats, opacity_logits, rgbs, sh_degree, degrees_to_use, img_h, img_w, radii, conics, v_xy, v_conic, v_rgbs,
+              v_opac, v_means, v_log_scales, v_quats, v_opacity_logits, v_features_dc, v_features_rest, v_depths, stream};
+    a.antialiased = true;
+    if (C == 1) return project_sh_bwd_impl("gc_project_sh_bwd_aa_views", accumulate != 0, a, packed_cam(cams));
+    return project_sh_bwd_views_impl("gc_project_sh_bwd_aa_views", C, accumulate, a, cams);
 }
 
 int gc_raster_finalize(int64_t num_pixels, float *out_img, float *out_extra, const float *final_Ts, float *alpha,

@@ -65,6 +65,27 @@ class GaussCtrlModelConfig(_ModelConfigBase):
     refine_on_device: bool = False                # True (stand-alone model): get_training_callbacks returns [StepCallback, RefineCallback] --
                                                   # splatfacto's whole refinement (statistics, split / duplicate, cull, opacity reset) on the
                                                   # HIP kernels of csrc/train_refine.hip; False: the callbacks as before (CullCallback)
+    rasterize_mode: str = "classic"               # "classic": gsplat 0.1.3's rasterizer, the reference's (every projected covariance gets +0.3 on
+                                                  # its diagonal, opacities untouched); "antialiased": later splatfacto's mode of that name -- each
+                                                  # view also multiplies the opacity by sqrt(det(cov2d) / det(cov2d + 0.3 I)) (ops.RenderAux.antialiased),
+                                                  # for scenes trained that way or rendered below their training resolution.  Declared here, so the
+                                                  # field exists (and defaults to the reference's behaviour) with and without nerfstudio
+
+    def __post_init__(self):
+        parent = getattr(super(), "__post_init__", None)
+        if parent is not None:
+            parent()
+        _antialiased(self.rasterize_mode)
+
+
+RASTERIZE_MODES = ("classic", "antialiased")
+
+
+def _antialiased(mode) -> bool:
+    """rasterize_mode -> RenderAux.antialiased; anything but the two names is a ValueError"""
+    if mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode must be one of {RASTERIZE_MODES}, got {mode!r}")
+    return mode == "antialiased"
 
 
 class GaussCtrlModel(_ModelBase):
@@ -157,6 +178,7 @@ class GaussCtrlModel(_ModelBase):
         # :162-169: SH of degree n (+0.5, clamp) when config.sh_degree > 0, else sigmoid(features_dc) (encoded as n = -1)
         n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else -1
         aux = self._aux = ops.RenderAux()
+        aux.antialiased = _antialiased(getattr(self.config, "rasterize_mode", "classic"))      # (checked again: the field may have been assigned)
         if self.training and getattr(self, "grad_into", None) is not None and self.crop_box is None:
             # the fused backward writes the six leaf gradients straight into the caller's buffers (dist.FlatGrads: ONE flat allocation that
             # RCCL reduces in place) and autograd gets None for them: GaussCtrlPipeline.train_iteration, train_mode "throughput"
@@ -213,6 +235,7 @@ class GaussCtrlModel(_ModelBase):
         background = self.background_color.to(self.device)
         n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else -1
         aux = self._aux = ops.RenderAux()
+        aux.antialiased = _antialiased(getattr(self.config, "rasterize_mode", "classic"))
         rgb, alpha, depth = ops.render_views(self.means, self.scales, self.quats, self.opacities, self.features_dc, self.features_rest,
                                              gcams, background, True, n, aux)
         self.last_size = (H, W)

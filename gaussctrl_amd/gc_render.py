@@ -5,7 +5,8 @@ its only hot-path touch is `pipeline.model.get_outputs_for_camera(...)` (gc_rend
 .npy (gc_render.py:217-221,833-838).  This module keeps that caller -- `render_cameras` -- and a small command line around it:
 
     ns-gaussctrl-render dataset --load-config <config.yml> --output-path <dir>            (under nerfstudio: its eval_setup)
-    ns-gaussctrl-render dataset --load-gaussians scene.npz --cameras cams.json --output-path <dir>   (stand-alone)
+    ns-gaussctrl-render dataset --load-gaussians scene.npz --cameras cams.json --output-path <dir>   (stand-alone;
+        --rasterize-mode antialiased for a scene trained with later splatfacto's rasterize_mode of that name)
 
 Outputs per frame i (1-based, the reference's mid-result layout): rgb/frame_%05d.npy + .ppm, depth_npy/frame_%05d.npy."""
 from __future__ import annotations
@@ -47,27 +48,35 @@ def load_cameras(path):
                    [int(f["w"]) for f in fr], [int(f["h"]) for f in fr])
 
 
-def load_model(npz_path, device="cuda"):
-    """scene.npz with the six splatfacto tensors (means scales quats opacities features_dc features_rest) -> GaussCtrlModel"""
+def load_model(npz_path, device="cuda", rasterize_mode="classic"):
+    """scene.npz with the six splatfacto tensors (means scales quats opacities features_dc features_rest) -> GaussCtrlModel;
+    rasterize_mode: GaussCtrlModelConfig.rasterize_mode ("classic" | "antialiased")"""
     from .gc_model import GaussCtrlModel, GaussCtrlModelConfig
     from .ns_compat import HAVE_NERFSTUDIO
     z = np.load(npz_path)
     params = {k: z[k] for k in ("means", "scales", "quats", "opacities", "features_dc", "features_rest")}
-    cfg = GaussCtrlModelConfig()
+    cfg = GaussCtrlModelConfig(rasterize_mode=rasterize_mode)
     cfg.sh_degree = int(round((params["features_rest"].shape[1] + 1) ** 0.5)) - 1
     if HAVE_NERFSTUDIO:
         raise SystemExit("under nerfstudio load the scene with --load-config (a splatfacto / gaussctrl training run)")
     return GaussCtrlModel(cfg, params=params, device=device)
 
 
-def entrypoint(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser(prog="ns-gaussctrl-render", description=__doc__.split("\n\n")[0])
     ap.add_argument("mode", choices=["dataset"], help="render every camera of the dataset / camera file")
     ap.add_argument("--load-config", help="nerfstudio run config (needs nerfstudio)")
     ap.add_argument("--load-gaussians", help="stand-alone: .npz with the six splatfacto tensors")
     ap.add_argument("--cameras", help="stand-alone: cameras.json")
+    ap.add_argument("--rasterize-mode", choices=["classic", "antialiased"], default="classic",
+                    help="stand-alone: antialiased = later splatfacto's rasterize_mode (per-view opacity compensation); "
+                         "classic = the reference's gsplat 0.1.3 rasterizer (--load-config takes the mode from the run's config)")
     ap.add_argument("--output-path", required=True)
-    a = ap.parse_args(argv)
+    return ap
+
+
+def entrypoint(argv=None):
+    a = make_parser().parse_args(argv)
     if a.load_config:
         from .ns_compat import HAVE_NERFSTUDIO
         if not HAVE_NERFSTUDIO:
@@ -79,7 +88,7 @@ def entrypoint(argv=None):
     else:
         if not (a.load_gaussians and a.cameras):
             raise SystemExit("give --load-config, or --load-gaussians and --cameras")
-        model, cameras = load_model(a.load_gaussians), load_cameras(a.cameras)
+        model, cameras = load_model(a.load_gaussians, rasterize_mode=a.rasterize_mode), load_cameras(a.cameras)
     outs = render_cameras(model, cameras, a.output_path)
     os.makedirs(os.path.join(a.output_path, "rgb"), exist_ok=True)
     for i, o in enumerate(outs):

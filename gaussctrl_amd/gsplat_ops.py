@@ -348,6 +348,12 @@ class RenderAux:
     # Depth supervision: True (with want_depth and parameters that require grad) makes the depth image differentiable -- the backward then
     # runs gc_rasterize_bwd_depth_views / gc_project_sh_bwd_depth_views.  False: depth is marked non-differentiable, as it always was.
     depth_grad = False
+    # rasterize_mode "antialiased" of later splatfacto / gsplat versions (include/gaussctrl_antialias.h): every view multiplies the opacity by
+    # rho = sqrt(max(0, det(cov2d) / det(cov2d + 0.3 I))), so that the 0.3 px^2 blur does not brighten splats thinner than a pixel.  False: the
+    # classic mode, gsplat 0.1.3's (the reference has no other).  `compensation` is rho after an antialiased render: [N] from render_view,
+    # [C, N] from render_views (0 where the view culls the Gaussian); None after a classic one.
+    antialiased = False
+    compensation = None
 
 
 def _finalize(ctx, npix, img, dep, fT):
@@ -415,7 +421,15 @@ class _RenderView(torch.autograd.Function):
         tight = TIGHT_BOXES if (aux is None or aux.tight_boxes is None) else bool(aux.tight_boxes)
         tight = tight and tb[0] <= 255 and tb[1] <= 255
         boxes = torch.empty(N, dtype=torch.int32, device=dev) if tight else None
-        if tight:
+        aa = bool(aux is not None and aux.antialiased)
+        comp = torch.empty(N, device=dev) if aa else None
+        if aa:         # opac is this view's sigmoid(logit) * rho: what the compositing kernels and the tight boxes see
+            L.check(lib.gc_project_sh_fwd_aa_views(
+                L.i64(N), L.i32(1), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree),
+                L.i32(sh_degree_to_use), _cams_host([cam]), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys),
+                L.ptr(depths), L.ptr(radii), L.ptr(conics), L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), None, st),
+                "gc_project_sh_fwd_aa_views")
+        elif tight:
             L.check(lib.gc_project_sh_fwd_boxes(
                 L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree),
                 L.i32(sh_degree_to_use), V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]),
@@ -438,8 +452,10 @@ class _RenderView(torch.autograd.Function):
             aux.tile_boxes = boxes
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
             aux.xys_grad = None
+            aux.compensation = comp
         ctx.meta = (cam, tb, N, sh_degree, int(sh_degree_to_use), V, P, O)
         ctx.aux = aux
+        ctx.comp = comp          # (not an input or output of the function: kept as an attribute)
         dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
                              depths, dep)
         return img, alpha, dep
@@ -470,7 +486,13 @@ class _RenderView(torch.autograd.Function):
         if ctx.aux is not None:
             ctx.aux.xys_grad = v_xy
         (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
-        if v_ex is not None:        # the compositing's v_extra is the projection's v_depths
+        if ctx.comp is not None:    # antialiased: v_op is of the view's effective opacity; v_depths may be NULL
+            L.check(L.lib().gc_project_sh_bwd_aa_views(
+                L.i64(N), L.i32(1), L.i32(int(acc)), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
+                _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col),
+                L.ptr(v_op), L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), L.stream_ptr()),
+                "gc_project_sh_bwd_aa_views")
+        elif v_ex is not None:      # the compositing's v_extra is the projection's v_depths
             L.check(L.lib().gc_project_sh_bwd_depth_views(
                 L.i64(N), L.i32(1), L.i32(int(acc)), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
                 _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
@@ -534,11 +556,21 @@ class _RenderViews(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32); i32 = dict(device=dev, dtype=torch.int32)
         xys = torch.empty(C, N, 2, **f32); depths = torch.empty(C, N, **f32); radii = torch.empty(C, N, **i32)
         conics = torch.empty(C, N, 3, **f32); nth = torch.empty(C, N, **i32); rgbs = torch.empty(C, N, 3, **f32)
-        opac = torch.empty(N, **f32); boxes = torch.empty(C, N, **i32); pairs = torch.empty(C, N, 2, **i32)
-        L.check(lib.gc_project_sh_fwd_views(
-            L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
-            CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
-            L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_views")
+        boxes = torch.empty(C, N, **i32); pairs = torch.empty(C, N, 2, **i32)
+        aa = bool(aux is not None and aux.antialiased)
+        shared_op = 0 if aa else 1          # antialiased: per-view effective opacities [C][N], the compositing kernels' shared_opacities = 0
+        if aa:
+            opac = torch.empty(C, N, **f32); comp = torch.empty(C, N, **f32)
+            L.check(lib.gc_project_sh_fwd_aa_views(
+                L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
+                CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
+                L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_aa_views")
+        else:
+            opac = torch.empty(N, **f32); comp = None
+            L.check(lib.gc_project_sh_fwd_views(
+                L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
+                CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
+                L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_views")
         order = torch.empty(C, N, **i32); cum = torch.empty(C, N, **i32); cnt = torch.empty(C, **i32)
         sorted_boxes = bool(getattr(aux, "sorted_boxes", True)) if aux is not None else True
         if sorted_boxes:      # round 6: the boxes ride through the depth sort, culled Gaussians drop out in its first pass -- no per-Gaussian gathers
@@ -577,7 +609,7 @@ class _RenderViews(torch.autograd.Function):
         assert bg.numel() == (3 if shared_bg else 3 * C)
         img = torch.empty(C, H, W, 3, **f32); fT = torch.empty(C, H, W, **f32); fi = torch.empty(C, H, W, **i32)
         dep = torch.empty(C, H, W, **f32) if want_depth else None
-        L.check(lib.gc_rasterize_fwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
+        L.check(lib.gc_rasterize_fwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
                                            L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac),
                                            L.ptr(depths if want_depth else None), L.ptr(bg), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(fi), st),
                 "gc_rasterize_fwd_views")
@@ -587,8 +619,10 @@ class _RenderViews(torch.autograd.Function):
             aux.M = (cnt, ovf)                          # per-view device counts / overflow flags ([C] each)
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, None
             aux.xys_grad = None
+            aux.compensation = comp
         ctx.meta = (cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, int(sh_degree_to_use))
         ctx.aux = aux
+        ctx.comp = comp
         dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
                              depths, dep)
         return img, alpha, dep
@@ -604,6 +638,7 @@ class _RenderViews(torch.autograd.Function):
         vo = _c(v_img) if v_img is not None else torch.zeros(C, H, W, 3, device=dev)
         va = _c(v_alpha) if v_alpha is not None else None
         with_depth = ctx.depth_grad and v_dep is not None
+        shared_op = 0 if ctx.comp is not None else 1
         vbuf = torch.zeros(C * N * (10 if with_depth else 9), device=dev)   # v_xy | v_conic | v_colors | v_opacity (| v_extra), each [C][N][..]
         v_xy = vbuf[:2 * C * N].view(C, N, 2); v_conic = vbuf[2 * C * N:5 * C * N].view(C, N, 3)
         v_col = vbuf[5 * C * N:8 * C * N].view(C, N, 3); v_op = vbuf[8 * C * N:9 * C * N].view(C, N)
@@ -612,12 +647,12 @@ class _RenderViews(torch.autograd.Function):
             depths, dep = ctx.saved_tensors[17:]
             vd = _c(v_dep)
             L.check(lib.gc_rasterize_bwd_depth_views(
-                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
                 L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
                 L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
                 L.ptr(v_ex), st), "gc_rasterize_bwd_depth_views")
         else:
-            L.check(lib.gc_rasterize_bwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(1), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
+            L.check(lib.gc_rasterize_bwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
                                                L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg),
                                                L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va), L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic),
                                                L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
@@ -625,7 +660,12 @@ class _RenderViews(torch.autograd.Function):
             ctx.aux.xys_grad = v_xy
         (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
         acc = int(acc)
-        if with_depth:              # the compositing's v_extra is the projection's v_depths
+        if ctx.comp is not None:    # antialiased: v_op is of the per-view effective opacities; v_depths may be NULL
+            L.check(lib.gc_project_sh_bwd_aa_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
+                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_aa_views")
+        elif with_depth:            # the compositing's v_extra is the projection's v_depths
             L.check(lib.gc_project_sh_bwd_depth_views(
                 L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
                 L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),

@@ -1,0 +1,83 @@
+"""CPU: the antialiased rasterize_mode's entry points are declared (include/gaussctrl_antialias.h), listed, exported and bound with matching
+argument counts; the config field, the RenderAux switch and the render command's flag exist with the classic default."""
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("gc_project_sh_fwd_aa_views", "gc_project_sh_bwd_aa_views")
+
+
+def _declared(header):
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return src, set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
+
+
+def _call_args(text, start):
+    """number of top-level arguments of the call whose '(' is at text[start]"""
+    depth, n, i = 0, 0, start
+    while True:
+        ch = text[i]
+        if ch in "([{":
+            depth += 1
+        elif ch in ")]}":
+            depth -= 1
+            if depth == 0:
+                return n + 1
+        elif ch == "," and depth == 1:
+            n += 1
+        i += 1
+
+
+def test_antialias_symbols_declared_listed_and_exported():
+    import ctypes
+    from gaussctrl_amd import _lib
+    _, declared = _declared("gaussctrl_antialias.h")
+    assert declared == set(NEW)
+    for name in NEW:
+        assert name in _lib.SYMBOLS, name
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        assert hasattr(lib, name), name
+    _, main = _declared("gaussctrl_hip.h")
+    assert len(main) == 83 and not main & set(NEW)          # the main header is as it was
+
+
+def test_antialias_bindings_pass_the_declared_number_of_arguments():
+    """every lib.gc_project_sh_*_aa_views( call of gsplat_ops passes as many arguments as the header's prototype has parameters"""
+    src, _ = _declared("gaussctrl_antialias.h")
+    declared = {name: _call_args(src, re.search(r"\b" + name + r"\s*\(", src).end() - 1) for name in NEW}
+    assert declared == {"gc_project_sh_fwd_aa_views": 27, "gc_project_sh_bwd_aa_views": 28}
+    host = open(os.path.join(ROOT, "gaussctrl_amd", "gsplat_ops.py")).read()
+    calls = {name: [_call_args(host, m.end() - 1) for m in re.finditer(r"\." + name + r"\s*\(", host)] for name in NEW}
+    for name in NEW:
+        assert len(calls[name]) == 2 and all(n == declared[name] for n in calls[name]), (name, calls[name])      # render_view and render_views
+
+
+def test_rasterize_mode_config_field():
+    import dataclasses
+    from gaussctrl_amd import gsplat_ops
+    from gaussctrl_amd.gc_model import GaussCtrlModelConfig
+    f = {x.name: x for x in dataclasses.fields(GaussCtrlModelConfig)}
+    assert f["rasterize_mode"].type in (str, "str") and f["rasterize_mode"].default == "classic"
+    assert "rasterize_mode" in GaussCtrlModelConfig.__annotations__          # declared on this class: there with and without nerfstudio
+    assert GaussCtrlModelConfig().rasterize_mode == "classic"
+    assert GaussCtrlModelConfig(rasterize_mode="antialiased").rasterize_mode == "antialiased"
+    with pytest.raises(ValueError, match="rasterize_mode"):
+        GaussCtrlModelConfig(rasterize_mode="mip")
+    assert gsplat_ops.RenderAux.antialiased is False and gsplat_ops.RenderAux().antialiased is False
+    assert gsplat_ops.RenderAux().compensation is None
+
+
+def test_render_command_takes_the_mode():
+    import inspect
+    from gaussctrl_amd import gc_render
+    base = ["dataset", "--load-gaussians", "scene.npz", "--cameras", "cams.json", "--output-path", "out"]
+    ap = gc_render.make_parser()
+    assert ap.parse_args(base).rasterize_mode == "classic"
+    assert ap.parse_args(base + ["--rasterize-mode", "antialiased"]).rasterize_mode == "antialiased"
+    with pytest.raises(SystemExit):
+        ap.parse_args(base + ["--rasterize-mode", "mip"])
+    assert inspect.signature(gc_render.load_model).parameters["rasterize_mode"].default == "classic"
