@@ -11,45 +11,15 @@
 //               round 1 (library sort = plumbing here; the hand-written depth-major/tile-minor
 //               two-level binning that replaces it is described in DESIGN.md "next").
 //   tile_bins : 1 lane per intersection, boundary detection
-#include "common.h"
+#include "raster_bin.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
 namespace {
 
-constexpr int TILE = 16;
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_CHUNK = SCAN_THREADS * SCAN_ITEMS;   // 2048
-
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int n = __shfl_up(v, d, 64);
-        if (lane >= d) v += n;
-    }
-    return v;
-}
-
-// block-wide inclusive scan of one int per thread (256 threads = 4 waves); returns inclusive value,
-// *total = block sum.
-__device__ __forceinline__ int block_incl_scan(int v, int *total)
-{
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int s = wave_incl_scan(v);
-    if (lane == 63) wsum[wid] = s;
-    __syncthreads();
-    int off = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-        if (w < wid) off += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return s + off;
-}
 
 // The three scan kernels take the view (camera) index from blockIdx.y (round 5: batched views): in / order / out are [C][N], the block
 // sums of view c live `ws` words after those of view c - 1, count[c].  order != NULL: the input is gathered through it (in[order[i]]) --
@@ -70,7 +40,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_local(int64_t N, const in
         v[k] = run;
     }
     int total;
-    int incl = block_incl_scan(run, &total);
+    int incl = block_incl_scan256(run, &total);
     int excl = incl - run;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
@@ -90,7 +60,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_sums(int nblocks, int32_t
         int i = base + threadIdx.x;
         int x = i < nblocks ? block_sums[i] : 0;
         int total;
-        int incl = block_incl_scan(x, &total);
+        int incl = block_incl_scan256(x, &total);
         if (i < nblocks) block_sums[i] = carry + incl - x;
         carry += total;
     }
@@ -109,8 +79,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_add(int64_t N, int32_t *_
         if (i < N) out[i] += add;
     }
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void k_map_intersects(int64_t N, int64_t M_cap, const float *__restrict__ xys,
                                                         const float *__restrict__ depths, const int32_t *__restrict__ radii,

@@ -12,12 +12,9 @@
 //      so gaussian_ids_sorted / tile_bins stay bit-identical to the oracle.
 //   4. tile bins from the sorted tile ids; the 64-bit keys are re-assembled only on request (tests / API compatibility).
 //
-// Radix pass = histogram kernel (256 LDS counters / workgroup) -> scan of the [digit][workgroup] table (the wave64 scan of
-// raster_bin.hip) -> scatter kernel with a STABLE in-workgroup rank: 4096 items / workgroup, each wave walks its contiguous 1024 in 16
-// rounds of 64; the rank among equal digits = a per-wave running digit counter in LDS (advanced by the leader lane of each digit group,
-// 8 ballots (match-any) + popcount inside the round) + a prefix over the four waves per digit, seeded with the global digit / workgroup
-// offset (round 6: 8 KB of LDS; rounds 1-5 kept a 64 KiB (round, wave) x digit table and ran two workgroups per CU).
-#include "common.h"
+// Radix pass (radix_pass) = k_radix_hist (256 LDS counters / workgroup of 4096 items) -> k_table_scan of the [digit][workgroup] table ->
+// a scatter kernel: 8-bit digits through the stable rank below (8 KB of LDS), the 5 / 6-bit tile passes through k_radix_scatter_staged.
+#include "raster_bin.h"
 
 // raster_bin.hip (internal, not in the public header): scan of C views' tile counts, optionally gathered through `order` first;
 // the three scan kernels run with grid.y = view on per-view scratch regions `ws_view_stride` bytes apart
@@ -27,12 +24,9 @@ extern "C" size_t gc_raster_scan_workspace_bytes(int64_t N);
 
 namespace {
 
-constexpr int TILE = 16;
 constexpr int RT = 256;            // threads
 constexpr int RI = 16;             // items per thread
 constexpr int RB = RT * RI;        // 4096 items per workgroup
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // n_dev (optional): the item count lives on the device (sync-free binning); `n` is then the capacity it is clamped to
 __device__ __forceinline__ int64_t live_count(int64_t n, const int32_t *n_dev)
@@ -56,21 +50,6 @@ struct VS {
     int64_t src;       // per-Gaussian source arrays ([C][N]: depths, radii, num_tiles_hit, tile boxes, xys / 2)
     int nd;            // stride of the device-side counts (n_dev / overflow): 1 per view (0 when unused)
 };
-__device__ __forceinline__ int block_incl_scan256(int v, int *total, int *wsum /* LDS[4] */)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int sc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(sc, d, 64); if (lane >= d) sc += y; }
-    __syncthreads();
-    if (lane == 63) wsum[wid] = sc;
-    __syncthreads();
-    int off = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wid) off += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return sc + off;
-}
 
 // Zero-initialisation of a launch set's counters in ONE launch (round 6): the per-view tickets / first-pass digit tables / tile_bins / overflow
 // flags were one hipMemsetAsync each -- 27 fills of ~5 us per launch set of 8 views, 4 % of the raster-only chain at 1 M Gaussians
@@ -96,7 +75,6 @@ void clear_views(hipStream_t s, int C, const ClearJob &j)
 __global__ __launch_bounds__(256) void k_table_scan(int64_t n, const int32_t *__restrict__ in, int32_t *__restrict__ out,
                                                     int32_t *sums, int32_t *ticket, VS vs)
 {
-    __shared__ int wsum[4];
     __shared__ int s_last;
     const int tid = threadIdx.x;
     { const int64_t o = (int64_t)blockIdx.y * vs.ws; in += o; out += o; sums += o; ticket += o; }
@@ -105,7 +83,7 @@ __global__ __launch_bounds__(256) void k_table_scan(int64_t n, const int32_t *__
 #pragma unroll
     for (int k = 0; k < 8; ++k) { const int64_t i = base + k; run += i < n ? in[i] : 0; v[k] = run; }
     int total;
-    const int excl = block_incl_scan256(run, &total, wsum) - run;
+    const int excl = block_incl_scan256(run, &total) - run;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { const int64_t i = base + k; if (i < n) out[i] = v[k] + excl; }
     if (tid == 0) {
@@ -121,35 +99,105 @@ __global__ __launch_bounds__(256) void k_table_scan(int64_t n, const int32_t *__
         const int i = b0 + tid;
         const int x = i < (int)gridDim.x ? __hip_atomic_load(&sums[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
         int tot;
-        const int incl = block_incl_scan256(x, &tot, wsum);
+        const int incl = block_incl_scan256(x, &tot);
         if (i < (int)gridDim.x) sums[i] = carry + incl - x;
         carry += tot;
     }
     if (tid == 0) *ticket = 0;         // ready for the next pass
 }
 
-// PAIR: keys points at (key, value) uint2 pairs -- the depth passes keep the pair together so that a scattered item is ONE 8-byte store
-template <bool PAIR>
+// Digit histogram of a workgroup's 4096 items of W words, the key first (1: key array, 2: (key, value) pairs, 3: Tri).  Items of 2 or 3 words are
+// the depth passes': always 8-bit digits, so only the tile passes (W = 1) read `dmask`.  VIS: keys 0xFFFFFFFF (culled by the projection) do not
+// count, and the others are added to visible_dev[view] through one more LDS counter.
+template <int W, bool VIS>
 __global__ __launch_bounds__(RT) void k_radix_hist(const uint32_t *__restrict__ keys, int64_t n, const int32_t *__restrict__ n_dev,
-                                                   int shift, unsigned dmask, int nblocks, int32_t *__restrict__ hist /* [digits][nblocks] */, VS vs,
-                                                   int keys_ext /* keys = external [C][vs.ext] pairs, not a workspace buffer */)
+                                                   int shift, unsigned dmask, int nblocks, int32_t *__restrict__ hist /* [digits][nblocks] */,
+                                                   int32_t *__restrict__ visible_dev, VS vs,
+                                                   int keys_ext /* keys = external [C][vs.ext] items, not a workspace buffer */)
 {
-    { const int64_t o = (int64_t)blockIdx.y * vs.ws; keys += keys_ext ? (int64_t)blockIdx.y * 2 * vs.ext : o; hist += o; if (n_dev) n_dev += blockIdx.y * vs.nd; }
+    { const int64_t o = (int64_t)blockIdx.y * vs.ws; keys += keys_ext ? (int64_t)blockIdx.y * W * vs.ext : o; hist += o; if (n_dev) n_dev += blockIdx.y * vs.nd; }
     n = live_count(n, n_dev);
-    __shared__ int h[256];
+    const unsigned dm = W == 1 ? dmask : 255u;
+    __shared__ int h[256 + (VIS ? 1 : 0)];
+    int &vis = h[VIS ? 256 : 0];
     h[threadIdx.x] = 0;
+    if (VIS && threadIdx.x == 0) vis = 0;
     __syncthreads();
     const int64_t base = (int64_t)blockIdx.x * RB;
+    int mine = 0;
 #pragma unroll
     for (int j = 0; j < RI; ++j) {
         const int64_t i = base + j * RT + threadIdx.x;
-        if (i < n) atomicAdd(&h[((PAIR ? keys[2 * i] : keys[i]) >> shift) & dmask], 1);
+        if (i < n) {
+            const uint32_t k = keys[W * i];
+            if (!VIS || k != 0xFFFFFFFFu) { atomicAdd(&h[(k >> shift) & dm], 1); ++mine; }
+        }
     }
+    if (VIS && mine) atomicAdd(&vis, mine);
     __syncthreads();
-    if (threadIdx.x <= dmask) hist[(int64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+    if (threadIdx.x <= dm) hist[(int64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+    if (VIS && threadIdx.x == 0 && vis) atomicAdd(&visible_dev[blockIdx.y], vis);
 }
 
+// One round of 64 items in a wave: the mask of the lanes that hold an item (ok) with this lane's digit -- DB match-any ballots.
+// (A lane without an item gets the mask of the items that share its digit bits; callers use the mask of ok lanes only.)
+template <int DB>
+__device__ __forceinline__ unsigned long long digit_group(bool ok, unsigned d)
+{
+    unsigned long long m = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < DB; ++b) {
+        const unsigned long long bal = __ballot((d >> b) & 1);
+        m &= ((d >> b) & 1) ? bal : ~bal;
+    }
+    return m;
+}
+__device__ __forceinline__ unsigned long long lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
+
+// The STABLE in-workgroup rank of the 8-bit scatter kernels (k_radix_scatter, k_tri_scatter; they differ in how an item is loaded and stored),
+// in 8 KB of LDS.  Wave w owns the CONTIGUOUS items [1024 w, 1024 w + 1024) of the workgroup's 4096 and walks them in 16 rounds of 64
+// (rank_item), so the order of an item is (wave, round, lane).  Its output position is wbase[w][d] + pre:
+//   wbase[w][d] = the exclusive offset of (digit, workgroup) in the scanned table, offs + sums - hist,
+//                 + the items of digit d in the earlier waves: a prefix over the four cnt[w][d]      (rank_bases: thread d, once per workgroup)
+//   pre         = the items of digit d in the earlier rounds of the wave: cnt[w][d], a running counter that the leader (lowest) lane of every
+//                 digit group of a round reads and advances by the group's size; the old value reaches the group through ds_bpermute
+//                 + those in the lower lanes of the round: popcount of the group mask below the lane          (rank_round: -1 without an item)
+// Invariant: cnt[w][d] is handed from the leader lane of round j to the (usually different) leader lane of round j + 1 through LDS, inside ONE
+// wave.  The LDS operations of a wave execute in program order, and the wave barrier (no instruction) tells the compiler to keep them in it.
+// Four workgroups per CU (112 - 120 VGPRs: 4 waves per SIMD) hide the round-to-round LDS latency; a 64 KB (round, wave) x digit table has no
+// such dependency, but only two fit a CU, and that was slower.
+// Schedule of a kernel: rank_begin; 16 x (load, rank_round); rank_bases (barrier, bases, barrier); scatter.
+__device__ __forceinline__ int64_t rank_item(int64_t base, int j) { return base + (threadIdx.x >> 6) * (RI * 64) + j * 64 + (threadIdx.x & 63); }
+__device__ __forceinline__ void rank_begin(int *cnt /* LDS [4][256] */)
+{
+    for (int i = threadIdx.x; i < 4 * 256; i += RT) cnt[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ int rank_round(int *cnt, bool ok, unsigned d)
+{
+    const int lane = threadIdx.x & 63;
+    int *my = cnt + (threadIdx.x >> 6) * 256;
+    const unsigned long long lt = lanes_below(lane), m = digit_group<8>(ok, d);
+    int old = 0;
+    if (ok && (m & lt) == 0) { old = my[d]; my[d] = old + __popcll(m); }
+    __builtin_amdgcn_wave_barrier();
+    old = __shfl(old, ok ? __builtin_ctzll(m) : lane, 64);
+    return ok ? old + __popcll(m & lt) : -1;
+}
 // offs = INCLUSIVE scan of hist ([digit][block] flattened); exclusive offset of (d, b) = offs[d*nb + b] - hist[d*nb + b]
+__device__ __forceinline__ void rank_bases(const int *cnt, int *wbase /* LDS [4][256] */, int nblocks, const int32_t *__restrict__ hist,
+                                           const int32_t *__restrict__ offs, const int32_t *__restrict__ sums)
+{
+    __syncthreads();
+    const int d = threadIdx.x;
+    const int64_t e = (int64_t)d * nblocks + blockIdx.x;
+    int run = offs[e] + sums[e / TS_CHUNK] - hist[e];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { wbase[w * 256 + d] = run; run += cnt[w * 256 + d]; }
+    __syncthreads();
+}
+
+// PAIR: keys points at (key, value) uint2 pairs -- the depth passes keep the pair together so that a scattered item is ONE 8-byte store
 template <bool PAIR>
 __global__ __launch_bounds__(RT) void k_radix_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                       uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, int64_t n,
@@ -168,22 +216,13 @@ __global__ __launch_bounds__(RT) void k_radix_scatter(const uint32_t *__restrict
     n = live_count(n, n_dev);
     const int64_t base = (int64_t)blockIdx.x * RB;
     if (base >= n) return;
-    // Stable rank with 8 KB of LDS (round 6; rounds 1-5 kept a 64 KB (round, wave) x digit table: two workgroups per CU -- occupancy, not bytes,
-    // bounded the pass): wave w owns the CONTIGUOUS items [1024 w, 1024 w + 1024) of the workgroup's 4096 and walks them in 16 rounds of 64, so the
-    // order of an item is (wave, round, lane): a per-wave running digit counter, advanced by the leader lane of every digit group of a round
-    // (old value broadcast with ds_bpermute), + the ballot rank inside the round + one prefix over the four waves per digit.
-    __shared__ int cnt[4 * 256];
-    __shared__ int wbase[4 * 256];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    for (int i = tid; i < 4 * 256; i += RT) cnt[i] = 0;
-    __syncthreads();
+    __shared__ int cnt[4 * 256], wbase[4 * 256];
+    rank_begin(cnt);
     uint32_t k[RI], v[RI];
     int pre[RI];
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    int *my = cnt + wid * 256;
 #pragma unroll
     for (int j = 0; j < RI; ++j) {
-        const int64_t i = base + wid * (RI * 64) + j * 64 + lane;
+        const int64_t i = rank_item(base, j);
         const bool ok = i < n;
         if (PAIR) {
             const uint2 kv = ok ? reinterpret_cast<const uint2 *>(keys)[i] : make_uint2(0xFFFFFFFFu, 0u);
@@ -192,33 +231,13 @@ __global__ __launch_bounds__(RT) void k_radix_scatter(const uint32_t *__restrict
             k[j] = ok ? keys[i] : 0xFFFFFFFFu;
             v[j] = ok ? vals[i] : 0u;
         }
-        const unsigned d = (k[j] >> shift) & 255;
-        unsigned long long m = __ballot(ok);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((d >> b) & 1);
-            m &= ((d >> b) & 1) ? bal : ~bal;
-        }
-        const bool leader = ok && (m & lt) == 0;
-        int old = 0;
-        if (leader) { old = my[d]; my[d] = old + __popcll(m); }
-        old = __shfl(old, ok ? __builtin_ctzll(m) : lane, 64);
-        pre[j] = ok ? old + __popcll(m & lt) : -1;
+        pre[j] = rank_round(cnt, ok, (k[j] >> shift) & 255);
     }
-    __syncthreads();
-    {
-        const int d = tid;
-        const int64_t e = (int64_t)d * nblocks + blockIdx.x;
-        int run = offs[e] + sums[e / TS_CHUNK] - hist[e];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { wbase[w * 256 + d] = run; run += cnt[w * 256 + d]; }
-    }
-    __syncthreads();
+    rank_bases(cnt, wbase, nblocks, hist, offs, sums);
 #pragma unroll
     for (int j = 0; j < RI; ++j) {
         if (pre[j] >= 0) {
-            const unsigned d = (k[j] >> shift) & 255;
-            const int pos = wbase[wid * 256 + d] + pre[j];
+            const int pos = wbase[(threadIdx.x >> 6) * 256 + ((k[j] >> shift) & 255)] + pre[j];
             if (PAIR) {       // keys_out == NULL: last pass, only the values are still needed
                 if (keys_out) reinterpret_cast<uint2 *>(keys_out)[pos] = make_uint2(k[j], v[j]);
                 else vals_out[pos] = v[j];
@@ -232,7 +251,7 @@ __global__ __launch_bounds__(RT) void k_radix_scatter(const uint32_t *__restrict
 
 // Scatter of the TILE passes: few digits (2^DB <= 64; the tile-id bits are split evenly over the two passes), so the (round, wave) x digit
 // table is small and the 4096 items of the workgroup are first put in digit order in LDS and then streamed out: consecutive lanes write
-// consecutive addresses inside each digit run (full-line stores).  The direct form above issues one isolated 4-byte store per item and
+// consecutive addresses inside each digit run (full-line stores).  The direct form (k_radix_scatter<false>) issues one isolated 4-byte store per item and
 // array -- 2 M of them per pass, which is what bounded it (329 us per pass at M = 20 M vs 110 us of bytes at 3 TB/s).
 // PK (round 5): the pair travels as ONE word, (tile << idb) | gaussian id (N <= 2^idb, tile bits + idb <= 32): `vals` is not read, the
 // non-final pass writes 4 bytes per pair instead of 8; the final pass (vals_out != NULL) writes the packed word (k_tile_bins32 reads the tiles
@@ -266,7 +285,7 @@ __global__ __launch_bounds__(RT) void k_radix_scatter_staged(const uint32_t *__r
     const int cnt = (int)(n - base < RB ? n - base : RB);
     uint32_t k[RI], v[RI];
     unsigned short rk[RI];
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const unsigned long long lt = lanes_below(lane);
 #pragma unroll
     for (int j = 0; j < RI; ++j) {
         const int64_t i = base + j * RT + tid;
@@ -274,12 +293,7 @@ __global__ __launch_bounds__(RT) void k_radix_scatter_staged(const uint32_t *__r
         k[j] = ok ? keys[i] : 0xFFFFFFFFu;
         v[j] = (ok && !PK) ? vals[i] : 0u;
         const unsigned d = (k[j] >> shift) & (ND - 1);
-        unsigned long long m = __ballot(ok);
-#pragma unroll
-        for (int b = 0; b < DB; ++b) {
-            const unsigned long long bal = __ballot((d >> b) & 1);
-            m &= ((d >> b) & 1) ? bal : ~bal;
-        }
+        const unsigned long long m = digit_group<DB>(ok, d);
         rk[j] = (unsigned short)__popcll(m & lt);
         if (ok && (m & lt) == 0) tbl[(j * 4 + wid) * ND + d] = __popcll(m);
     }
@@ -461,21 +475,97 @@ __global__ __launch_bounds__(256) void k_tile_bins32(int64_t M, const int32_t *_
     if (i == M - 1) bins[2 * t + 1] = (int32_t)M;
 }
 
+// Round 6: depth order WITHOUT the per-Gaussian gathers.  gc_raster_depth_order_views sorts (depth bits, id) pairs; afterwards the scan reads
+// num_tiles_hit[order[j]] and the emission tile_boxes[order[j]] -- two random 4-byte reads per Gaussian, i.e. two 128-byte line fetches:
+// by the counters (profiles/r05_raster_traffic_views8.json) 2/3 of everything the depth order fetched.  Here the packed tight box rides through
+// the radix passes as a third word of the item (12-byte (key, id, box) triples), so the scan (count = box area) and the emission read their
+// inputs sequentially; and the Gaussians the projection culled (key 0xFFFFFFFF) are dropped by the FIRST pass instead of travelling through
+// all four (its rank only counts visible items; the later passes run on visible_dev[view] items).
+// The order is the same stable LSD sort by (depth bits, id) over the same visible set: gaussian_ids_sorted / tile_bins are bit-identical.
+struct __attribute__((packed, aligned(4))) Tri { uint32_t k, id, box; };
+
+// P0: the items are the projection's external (key, id) pairs [C][N] + tile boxes [C][N], and the culled ones (key 0xFFFFFFFF) are dropped.
+// LAST: the sorted ids and boxes go to the external [C][N] arrays (the keys are not needed any more).
+template <bool P0, bool LAST>
+__global__ __launch_bounds__(RT) void k_tri_scatter(const uint32_t *__restrict__ items, const uint32_t *__restrict__ boxes_in, Tri *__restrict__ out,
+                                                    uint32_t *__restrict__ ids_out, uint32_t *__restrict__ boxes_out, int64_t n,
+                                                    const int32_t *__restrict__ n_dev, int shift, int nblocks, const int32_t *__restrict__ hist,
+                                                    const int32_t *__restrict__ offs, const int32_t *__restrict__ sums, VS vs)
+{
+    {
+        const int64_t o = (int64_t)blockIdx.y * vs.ws;
+        hist += o; offs += o; sums += o;
+        if (!LAST) out = (Tri *)((uint32_t *)out + o);
+        else { ids_out += (int64_t)blockIdx.y * vs.ext; boxes_out += (int64_t)blockIdx.y * vs.ext; }
+        if (P0) boxes_in += (int64_t)blockIdx.y * vs.ext;
+        if (n_dev) n_dev += blockIdx.y * vs.nd;
+    }
+    const uint32_t *src = items + (P0 ? (int64_t)blockIdx.y * 2 * vs.ext : (int64_t)blockIdx.y * vs.ws);
+    n = live_count(n, n_dev);
+    const int64_t base = (int64_t)blockIdx.x * RB;
+    if (base >= n) return;
+    __shared__ int cnt[4 * 256], wbase[4 * 256];
+    rank_begin(cnt);
+    uint32_t k[RI], v[RI], bx[RI];
+    int pre[RI];
+#pragma unroll
+    for (int j = 0; j < RI; ++j) {
+        const int64_t i = rank_item(base, j);
+        bool ok = i < n;
+        k[j] = 0xFFFFFFFFu; v[j] = 0u; bx[j] = 0u;
+        if (ok) {
+            if (P0) {
+                const uint2 kv = reinterpret_cast<const uint2 *>(src)[i];
+                k[j] = kv.x; v[j] = kv.y;
+                ok = kv.x != 0xFFFFFFFFu;
+                if (ok) bx[j] = boxes_in[i];
+            } else {
+                const Tri t = reinterpret_cast<const Tri *>(src)[i];
+                k[j] = t.k; v[j] = t.id; bx[j] = t.box;
+            }
+        }
+        pre[j] = rank_round(cnt, ok, (k[j] >> shift) & 255);
+    }
+    rank_bases(cnt, wbase, nblocks, hist, offs, sums);
+#pragma unroll
+    for (int j = 0; j < RI; ++j) {
+        if (pre[j] >= 0) {
+            const int pos = wbase[(threadIdx.x >> 6) * 256 + ((k[j] >> shift) & 255)] + pre[j];
+            if (LAST) { ids_out[pos] = v[j]; boxes_out[pos] = bx[j]; }
+            else { Tri t; t.k = k[j]; t.id = v[j]; t.box = bx[j]; out[pos] = t; }
+        }
+    }
+}
+
+// tile count of the box at depth position j (0 past the visible ones), written where the in-place scan turns it into cum_sorted
+__global__ __launch_bounds__(256) void k_box_counts(int64_t N, const uint32_t *__restrict__ boxes_sorted, const int32_t *__restrict__ visible_dev,
+                                                    int32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    boxes_sorted += blockIdx.y * N; cnt += blockIdx.y * N;
+    int c = 0;
+    if (i < (int64_t)visible_dev[blockIdx.y]) {
+        const uint32_t bx = boxes_sorted[i];
+        const int w = (int)((bx >> 8) & 255u) - (int)(bx & 255u), h = (int)(bx >> 24) - (int)((bx >> 16) & 255u);
+        c = (w > 0 && h > 0) ? w * h : 0;
+    }
+    cnt[i] = c;
+}
+
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// workspace of a run of radix passes over n (key32, val32) pairs: 2 ping-pong pair buffers + digit tables + scan scratch
-struct Plan {
-    size_t off_keys[2], off_vals[2], off_hist, off_offs, off_scan, scan_bytes, off_cnt, total;
-    int nb;
-};
-
-Plan make_plan(int64_t n)
+// per-view workspace of a run of radix passes over n items: 2 ping-pong item buffers + digit tables + scan scratch + the scan's ticket.
+// item_bytes 8: a buffer is a key array and, val_off bytes on, a value array (the pair form uses the two as one uint2 array); 12: Tri items.
+struct Plan { size_t off_buf[2], val_off, off_hist, off_offs, off_scan, scan_bytes, off_cnt, total; int nb; };
+Plan make_plan(int64_t n, int item_bytes)
 {
     Plan p;
     p.nb = (int)((n + RB - 1) / RB);
     if (p.nb < 1) p.nb = 1;
+    p.val_off = al(4 * (size_t)n + 4);
     size_t o = 0;
-    for (int i = 0; i < 2; ++i) { p.off_keys[i] = o; o += al(4 * (size_t)n + 4); p.off_vals[i] = o; o += al(4 * (size_t)n + 4); }
+    for (int i = 0; i < 2; ++i) { p.off_buf[i] = o; o += item_bytes == 12 ? al(12 * (size_t)n + 16) : 2 * p.val_off; }
     p.off_hist = o; o += al(4 * 256 * (size_t)p.nb);
     p.off_offs = o; o += al(4 * 256 * (size_t)p.nb);
     const int64_t scan_n = 256 * (int64_t)p.nb > n ? 256 * (int64_t)p.nb : n;
@@ -486,44 +576,48 @@ Plan make_plan(int64_t n)
     return p;
 }
 
-void set_attr() {}
-
-// one stable radix pass of `dbits` bits (8: the direct scatter; 5 / 6: the LDS-staged scatter of the tile passes) over C views at once
-// (grid.y = view; per-view workspace regions of vs.ws words).  vals_ext: `vo` is the external [C][vs.ext] array, not a workspace buffer.
-int radix_pass(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, int64_t n, const int32_t *n_dev, int shift,
-               const Plan &p, unsigned char *w, hipStream_t s, int C, const VS &vs, int vals_ext, int dbits = 8, bool pair = false,
-               bool have_hist = false, int keys_ext = 0, int idb = 0)
+// one stable radix pass of `dbits` bits over C views at once (grid.y = view; per-view workspace regions of vs.ws words)
+enum Item { KEYS, PAIRS, TRIS };       // key array + value array | (key, value) uint2 | Tri
+struct Pass {
+    Item item;
+    int shift, dbits;                  // dbits 8: the stable-rank scatter; 5 / 6 (KEYS only): the LDS-staged scatter of the tile passes
+    int idb;                           // KEYS, > 0: packed pairs (tile << idb) | id in the key array, no value array
+    int64_t n; const int32_t *n_dev;
+    const uint32_t *ki, *vi;           // items in (vi: the value array of KEYS, the tile boxes of external TRIS)
+    uint32_t *ko, *vo, *bo;            // items out; ko == NULL: last pass of PAIRS / TRIS, only the values vo (TRIS: and the boxes bo) are written
+    bool in_ext, out_ext;              // ki (+ vi) / vo (+ bo) are external [C][vs.ext] arrays, not workspace buffers
+    bool have_hist;                    // the producer of ki already accumulated this pass's histogram (k_emit_sorted)
+    int32_t *visible_dev;              // external TRIS: culled items are dropped and the others counted here
+};
+void radix_pass(const Pass &a, const Plan &p, unsigned char *w, hipStream_t s, int C, const VS &vs)
 {
-    int32_t *hist = (int32_t *)(w + p.off_hist), *offs = (int32_t *)(w + p.off_offs), *cnt = (int32_t *)(w + p.off_cnt);
-    const int nd = 1 << dbits;
-    const dim3 g((unsigned)p.nb, (unsigned)C);
-    if (have_hist) {}                     // the producer of `ki` already accumulated this pass's histogram (k_emit_sorted)
-    else if (pair) hipLaunchKernelGGL(k_radix_hist<true>, g, dim3(RT), 0, s, ki, n, n_dev, shift, (unsigned)(nd - 1), p.nb, hist, vs, keys_ext);
-    else hipLaunchKernelGGL(k_radix_hist<false>, g, dim3(RT), 0, s, ki, n, n_dev, shift, (unsigned)(nd - 1), p.nb, hist, vs, 0);
     // cnt[0] is the scan's ticket (zeroed once per phase, self-resetting); the scan scratch holds the per-2048-entry offsets
-    int32_t *sums = (int32_t *)(w + p.off_scan);
+    int32_t *hist = (int32_t *)(w + p.off_hist), *offs = (int32_t *)(w + p.off_offs), *cnt = (int32_t *)(w + p.off_cnt), *sums = (int32_t *)(w + p.off_scan);
+    const dim3 g((unsigned)p.nb, (unsigned)C), b(RT);
+    const int nd = 1 << a.dbits;
+    if (!a.have_hist) {
+        const auto k = a.item == KEYS ? k_radix_hist<1, false> : a.item == TRIS && !a.in_ext ? k_radix_hist<3, false>
+                     : a.visible_dev ? k_radix_hist<2, true> : k_radix_hist<2, false>;
+        hipLaunchKernelGGL(k, g, b, 0, s, a.ki, a.n, a.n_dev, a.shift, (unsigned)(nd - 1), p.nb, hist, a.visible_dev, vs, (int)a.in_ext);
+    }
     const int64_t ne = nd * (int64_t)p.nb;
     hipLaunchKernelGGL(k_table_scan, dim3((unsigned)((ne + TS_CHUNK - 1) / TS_CHUNK), (unsigned)C), dim3(256), 0, s, ne, hist, offs, sums, cnt, vs);
-    const uint32_t idmask = idb ? ((1u << idb) - 1u) : 0u;
-    if (dbits == 5 && idb)
-        hipLaunchKernelGGL((k_radix_scatter_staged<5, true>), g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev, shift, p.nb, hist, offs, sums, vs, vals_ext, idmask);
-    else if (dbits == 6 && idb)
-        hipLaunchKernelGGL((k_radix_scatter_staged<6, true>), g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev, shift, p.nb, hist, offs, sums, vs, vals_ext, idmask);
-    else if (dbits == 5)
-        hipLaunchKernelGGL((k_radix_scatter_staged<5, false>), g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev, shift, p.nb, hist, offs, sums, vs, vals_ext, idmask);
-    else if (dbits == 6)
-        hipLaunchKernelGGL((k_radix_scatter_staged<6, false>), g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev, shift, p.nb, hist, offs, sums, vs, vals_ext, idmask);
-    else if (pair)
-        hipLaunchKernelGGL(k_radix_scatter<true>, g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev,
-                           shift, p.nb, hist, offs, sums, vs, vals_ext, keys_ext);
-    else
-        hipLaunchKernelGGL(k_radix_scatter<false>, g, dim3(RT), 0, s, ki, vi, ko, vo, n, n_dev,
-                           shift, p.nb, hist, offs, sums, vs, vals_ext, 0);
-    return GC_OK;
+    if (a.item == TRIS) {
+        const auto k = a.in_ext ? k_tri_scatter<true, false> : a.ko ? k_tri_scatter<false, false> : k_tri_scatter<false, true>;
+        hipLaunchKernelGGL(k, g, b, 0, s, a.ki, a.vi, (Tri *)a.ko, a.vo, a.bo, a.n, a.n_dev, a.shift, p.nb, hist, offs, sums, vs);
+    } else if (a.dbits < 8) {
+        const auto k = a.dbits == 5 ? (a.idb ? k_radix_scatter_staged<5, true> : k_radix_scatter_staged<5, false>)
+                                    : (a.idb ? k_radix_scatter_staged<6, true> : k_radix_scatter_staged<6, false>);
+        hipLaunchKernelGGL(k, g, b, 0, s, a.ki, a.vi, a.ko, a.vo, a.n, a.n_dev, a.shift, p.nb, hist, offs, sums, vs, (int)a.out_ext,
+                           a.idb ? (1u << a.idb) - 1u : 0u);
+    } else {
+        const auto k = a.item == PAIRS ? k_radix_scatter<true> : k_radix_scatter<false>;
+        hipLaunchKernelGGL(k, g, b, 0, s, a.ki, a.vi, a.ko, a.vo, a.n, a.n_dev, a.shift, p.nb, hist, offs, sums, vs, (int)a.out_ext, (int)a.in_ext);
+    }
 }
 
 // per-view region of the depth-order workspace: the radix plan + nothing else (the gathered tile counts are no longer materialised)
-size_t depth_region(int64_t N) { return make_plan(N > 0 ? N : 1).total; }
+size_t depth_region(int64_t N) { return make_plan(N > 0 ? N : 1, 8).total; }
 
 int depth_order_impl(int64_t N, int C, const float *depths, const int32_t *radii, const uint32_t *pairs_in, const int32_t *num_tiles_hit,
                      int32_t *depth_order, int32_t *cum_sorted, int32_t *count_dev, void *workspace, size_t workspace_bytes,
@@ -532,24 +626,23 @@ int depth_order_impl(int64_t N, int C, const float *depths, const int32_t *radii
     hipStream_t s = gc::S(stream);
     if (N == 0) return hipMemsetAsync(count_dev, 0, 4 * (size_t)C, s) == hipSuccess ? GC_OK : GC_ELAUNCH;
     if (!((pairs_in || (depths && radii)) && num_tiles_hit && depth_order && cum_sorted && workspace)) { gc::set_error("%s: null pointer", what); return GC_EINVAL; }
-    const Plan p = make_plan(N);
-    const size_t region = depth_region(N);
+    const Plan p = make_plan(N, 8);
+    const size_t region = p.total;
     if (workspace_bytes < region * (size_t)C) { gc::set_error("%s: workspace too small", what); return GC_ENOSPC; }
-    set_attr();
     unsigned char *w = (unsigned char *)workspace;
     VS vs; vs.ws = (int64_t)(region / 4); vs.ext = N; vs.src = N; vs.nd = 0;
-    uint32_t *k0 = (uint32_t *)(w + p.off_keys[0]), *k1 = (uint32_t *)(w + p.off_keys[1]);
-    // (key, id) pairs ping-pong between the two halves of the view's region (each half = the keys + vals regions of the plan, >= 8 N bytes)
-    uint32_t *pa = k0, *pb = k1;
+    // (key, id) pairs ping-pong between the two buffers of the view's region
+    uint32_t *pa = (uint32_t *)(w + p.off_buf[0]), *pb = (uint32_t *)(w + p.off_buf[1]);
     { ClearJob cj = {}; cj.base[0] = w + p.off_cnt; cj.stride[0] = region; cj.words[0] = 1; clear_views(s, C, cj); }     // tickets of k_table_scan
     // pairs_in: the projection kernel already wrote the (depth bits | 0xFFFFFFFF, id) pairs ([C][N] uint2): the first pass reads them in place
     if (!pairs_in)
         hipLaunchKernelGGL(k_depth_keys, dim3(gc::cdiv(N, 256), (unsigned)C), dim3(256), 0, s, N, depths, radii, (uint2 *)pa, vs);
+    Pass a = {};
+    a.item = PAIRS; a.dbits = 8; a.n = N; a.vo = (uint32_t *)depth_order; a.out_ext = true;
     for (int pass = 0; pass < 4; ++pass) {   // visible depths are > 0: the float bit pattern is monotone
-        const bool ext = pass == 0 && pairs_in;
-        int rc = radix_pass(ext ? pairs_in : pa, nullptr, pass == 3 ? nullptr : pb, (uint32_t *)depth_order, N, nullptr, 8 * pass, p, w, s, C, vs, 1,
-                            8, true, false, ext ? 1 : 0);
-        if (rc != GC_OK) return rc;
+        a.in_ext = pass == 0 && pairs_in;
+        a.ki = a.in_ext ? pairs_in : pa; a.ko = pass == 3 ? nullptr : pb; a.shift = 8 * pass;
+        radix_pass(a, p, w, s, C, vs);
         uint32_t *t = pa; pa = pb; pb = t;
     }
     // inclusive scan of the tile counts TAKEN IN DEPTH ORDER (the gather is fused into the scan's load), per view
@@ -589,8 +682,8 @@ int gc_raster_depth_order_views(int64_t N, int C, const float *depths, const int
                             stream, "gc_raster_depth_order_views");
 }
 
-size_t gc_raster_bin_workspace_bytes(int64_t M) { return make_plan(M > 0 ? M : 1).total; }
-size_t gc_raster_bin_views_workspace_bytes(int64_t M_cap, int C) { return make_plan(M_cap > 0 ? M_cap : 1).total * (size_t)(C > 0 ? C : 1); }
+size_t gc_raster_bin_workspace_bytes(int64_t M) { return make_plan(M > 0 ? M : 1, 8).total; }
+size_t gc_raster_bin_views_workspace_bytes(int64_t M_cap, int C) { return make_plan(M_cap > 0 ? M_cap : 1, 8).total * (size_t)(C > 0 ? C : 1); }
 
 }  // extern "C"
 
@@ -610,13 +703,12 @@ int bin_tiles_impl(int64_t N, int C, int64_t M, const int32_t *m_dev, int32_t *o
     }
     if (num_tiles > 65536) { gc::set_error("%s: at most 65536 tiles", what); return GC_EINVAL; }
     if (!(depth_order && cum_sorted && ((xys && radii) || tile_boxes) && (depths || !isect_ids_sorted) && gaussian_ids_sorted && workspace)) { gc::set_error("%s: null pointer", what); return GC_EINVAL; }
-    const Plan p = make_plan(M);
+    const Plan p = make_plan(M, 8);
     if (workspace_bytes < p.total * (size_t)C) { gc::set_error("%s: workspace too small", what); return GC_ENOSPC; }
-    set_attr();
     unsigned char *w = (unsigned char *)workspace;
     VS vs; vs.ws = (int64_t)(p.total / 4); vs.ext = M; vs.src = N; vs.nd = m_dev ? 1 : 0;
-    uint32_t *k0 = (uint32_t *)(w + p.off_keys[0]), *v0 = (uint32_t *)(w + p.off_vals[0]);
-    uint32_t *k1 = (uint32_t *)(w + p.off_keys[1]), *v1 = (uint32_t *)(w + p.off_vals[1]);
+    uint32_t *k0 = (uint32_t *)(w + p.off_buf[0]), *v0 = (uint32_t *)(w + p.off_buf[0] + p.val_off);
+    uint32_t *k1 = (uint32_t *)(w + p.off_buf[1]), *v1 = (uint32_t *)(w + p.off_buf[1] + p.val_off);
     // the tile-id bits are split evenly over two passes (1024 tiles: 5 + 5, 4096: 6 + 6) and scattered through LDS; above 12 bits
     // (or for a single pass) the 8-bit direct scatter runs
     int tbits = 1;
@@ -640,15 +732,17 @@ int bin_tiles_impl(int64_t N, int C, int64_t M, const int32_t *m_dev, int32_t *o
     hipLaunchKernelGGL(k_emit_sorted, dim3(gc::cdiv(N, 256), (unsigned)C), dim3(256), 0, s, N, M, (const uint32_t *)depth_order, xys, radii,
                        tile_boxes, cum_sorted, tiles_x, tiles_y, k0, v0, fused_hist ? (1u << dbits) - 1u : 0u, fused_hist ? p.nb : 0,
                        (int32_t *)(w + p.off_hist), vs, idb, visible_dev);
-    uint32_t *ks = k0, *vsrc = v0;
+    Pass a = {};
+    a.item = KEYS; a.dbits = dbits; a.idb = idb; a.n = M; a.n_dev = m_dev; a.ki = k0; a.vi = v0;
     for (int pass = 0; pass < passes; ++pass) {
         const bool last = pass == passes - 1;
-        uint32_t *ko = ks == k0 ? k1 : k0, *vo = last ? (uint32_t *)gaussian_ids_sorted : (idb ? (uint32_t *)nullptr : (vsrc == v0 ? v1 : v0));
-        int rc = radix_pass(ks, vsrc, ko, vo, M, m_dev, idb + dbits * pass, p, w, s, C, vs, last ? 1 : 0, dbits, false, fused_hist && pass == 0, 0, idb);
-        if (rc != GC_OK) return rc;
-        ks = ko; vsrc = vo;
+        a.ko = a.ki == k0 ? k1 : k0;
+        a.vo = last ? (uint32_t *)gaussian_ids_sorted : (idb ? (uint32_t *)nullptr : (a.vi == v0 ? v1 : v0));
+        a.out_ext = last; a.shift = idb + dbits * pass; a.have_hist = fused_hist && pass == 0;
+        radix_pass(a, p, w, s, C, vs);
+        a.ki = a.ko; a.vi = a.vo;
     }
-    hipLaunchKernelGGL(k_tile_bins32, dim3(gc::cdiv(M, 256), (unsigned)C), dim3(256), 0, s, M, m_dev, overflow_dev, num_tiles, ks,
+    hipLaunchKernelGGL(k_tile_bins32, dim3(gc::cdiv(M, 256), (unsigned)C), dim3(256), 0, s, M, m_dev, overflow_dev, num_tiles, a.ki,
                        (const uint32_t *)gaussian_ids_sorted, depths, tile_bins, isect_ids_sorted, (int32_t *)nullptr, vs, idb);
     return gc::check_launch(what);
 }
@@ -710,176 +804,7 @@ int gc_raster_bin_tiles_views(int64_t N, int C, int64_t M_cap, const int32_t *co
                           gaussian_ids_sorted, tile_bins, isect_ids_sorted, workspace, workspace_bytes, stream, "gc_raster_bin_tiles_views");
 }
 
-}  // extern "C"
-
-
-// ================================================================================================================================
-// Round 6: depth order WITHOUT the per-Gaussian gathers.  gc_raster_depth_order_views sorts (depth bits, id) pairs; afterwards the scan reads
-// num_tiles_hit[order[j]] and the emission tile_boxes[order[j]] -- two random 4-byte reads per Gaussian, i.e. two 128-byte line fetches:
-// by the counters (profiles/r05_raster_traffic_views8.json) 2/3 of everything the depth order fetched.  Here the packed tight box rides through
-// the radix passes as a third word of the item (12-byte (key, id, box) triples), so the scan (count = box area) and the emission read their
-// inputs sequentially; and the Gaussians the projection culled (key 0xFFFFFFFF) are dropped by the FIRST pass instead of travelling through
-// all four (its rank only counts visible items; the later passes run on visible_dev[view] items).
-// The order is the same stable LSD sort by (depth bits, id) over the same visible set: gaussian_ids_sorted / tile_bins are bit-identical.
-namespace {
-
-struct __attribute__((packed, aligned(4))) Tri { uint32_t k, id, box; };
-
-// P0: the items are the projection's external (key, id) pairs [C][N] + tile boxes [C][N], culled items (key 0xFFFFFFFF) do not count
-template <bool P0>
-__global__ __launch_bounds__(RT) void k_tri_hist(const void *__restrict__ items, int64_t n, const int32_t *__restrict__ n_dev, int shift,
-                                                 int nblocks, int32_t *__restrict__ hist, int32_t *__restrict__ visible_dev, VS vs)
-{
-    hist += (int64_t)blockIdx.y * vs.ws;
-    const uint32_t *keys;
-    if (P0) keys = (const uint32_t *)items + (int64_t)blockIdx.y * 2 * vs.ext;
-    else { keys = (const uint32_t *)items + (int64_t)blockIdx.y * vs.ws; n = (int64_t)n_dev[blockIdx.y] < n ? (int64_t)n_dev[blockIdx.y] : n; }
-    __shared__ int h[256];
-    __shared__ int vis;
-    h[threadIdx.x] = 0;
-    if (threadIdx.x == 0) vis = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * RB;
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < RI; ++j) {
-        const int64_t i = base + j * RT + threadIdx.x;
-        if (i < n) {
-            const uint32_t k = keys[(P0 ? 2 : 3) * i];
-            if (!P0 || k != 0xFFFFFFFFu) { atomicAdd(&h[(k >> shift) & 255], 1); ++mine; }
-        }
-    }
-    if (P0 && mine) atomicAdd(&vis, mine);
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
-    if (P0 && threadIdx.x == 0 && vis) atomicAdd(&visible_dev[blockIdx.y], vis);
-}
-
-// LAST: the sorted ids and boxes go to the external [C][N] arrays (the keys are not needed any more).
-// Stable rank with 8 KB of LDS (the pair kernel above keeps a 64 KB (round, wave) x digit table: two workgroups per CU, and by the counters
-// its passes run at a quarter of the HBM rate although they move few bytes -- occupancy, not traffic, bounds them).  Here wave w owns the
-// CONTIGUOUS items [1024 w, 1024 w + 1024) of the workgroup's 4096 and walks them in 16 rounds of 64: the order of an item is (wave, round,
-// lane), so a per-wave running digit counter (cnt[w][d], read and advanced by the leader lane of every digit group of a round, the old value
-// broadcast to the group with ds_bpermute) gives the rank among the wave's earlier items, the ballots the rank inside the round, and one
-// prefix over the four waves per digit (thread d) the rest.  8+ workgroups per CU hide the round-to-round LDS dependency.
-template <bool P0, bool LAST>
-__global__ __launch_bounds__(RT) void k_tri_scatter(const void *__restrict__ items, const uint32_t *__restrict__ boxes_in, Tri *__restrict__ out,
-                                                    uint32_t *__restrict__ ids_out, uint32_t *__restrict__ boxes_out, int64_t n,
-                                                    const int32_t *__restrict__ n_dev, int shift, int nblocks, const int32_t *__restrict__ hist,
-                                                    const int32_t *__restrict__ offs, const int32_t *__restrict__ sums, VS vs)
-{
-    {
-        const int64_t o = (int64_t)blockIdx.y * vs.ws;
-        hist += o; offs += o; sums += o;
-        if (!LAST) out = (Tri *)((uint32_t *)out + o);
-        else { ids_out += (int64_t)blockIdx.y * vs.ext; boxes_out += (int64_t)blockIdx.y * vs.ext; }
-        if (P0) boxes_in += (int64_t)blockIdx.y * vs.ext;
-    }
-    const uint32_t *src = P0 ? (const uint32_t *)items + (int64_t)blockIdx.y * 2 * vs.ext : (const uint32_t *)items + (int64_t)blockIdx.y * vs.ws;
-    if (!P0) n = (int64_t)n_dev[blockIdx.y] < n ? (int64_t)n_dev[blockIdx.y] : n;
-    const int64_t base = (int64_t)blockIdx.x * RB;
-    if (base >= n) return;
-    __shared__ int cnt[4 * 256];      // running count of digit d among the items wave w has walked
-    __shared__ int wbase[4 * 256];    // output position of wave w's first item with digit d
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    for (int i = tid; i < 4 * 256; i += RT) cnt[i] = 0;
-    __syncthreads();
-    uint32_t k[RI], v[RI], bx[RI];
-    int pre[RI];                      // rank among the wave's items with the same digit (-1: no item)
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    int *my = cnt + wid * 256;
-#pragma unroll
-    for (int j = 0; j < RI; ++j) {
-        const int64_t i = base + wid * (RI * 64) + j * 64 + lane;
-        bool ok = i < n;
-        k[j] = 0xFFFFFFFFu; v[j] = 0u; bx[j] = 0u;
-        if (ok) {
-            if (P0) {
-                const uint2 kv = reinterpret_cast<const uint2 *>(src)[i];
-                k[j] = kv.x; v[j] = kv.y;
-                ok = kv.x != 0xFFFFFFFFu;
-                if (ok) bx[j] = boxes_in[i];
-            } else {
-                const Tri t = reinterpret_cast<const Tri *>(src)[i];
-                k[j] = t.k; v[j] = t.id; bx[j] = t.box;
-            }
-        }
-        const unsigned d = (k[j] >> shift) & 255;
-        unsigned long long m = __ballot(ok);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((d >> b) & 1);
-            m &= ((d >> b) & 1) ? bal : ~bal;
-        }
-        const bool leader = ok && (m & lt) == 0;
-        int old = 0;
-        if (leader) { old = my[d]; my[d] = old + __popcll(m); }        // (LDS operations of one wave execute in program order: round j + 1 sees this)
-        const int lead_lane = ok ? __builtin_ctzll(m) : lane;
-        old = __shfl(old, lead_lane, 64);
-        pre[j] = ok ? old + __popcll(m & lt) : -1;
-    }
-    __syncthreads();
-    {   // thread d: where each wave's items of digit d start (global offset of (d, this workgroup) + the earlier waves' totals)
-        const int d = tid;
-        const int64_t e = (int64_t)d * nblocks + blockIdx.x;
-        int run = offs[e] + sums[e / TS_CHUNK] - hist[e];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { wbase[w * 256 + d] = run; run += cnt[w * 256 + d]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RI; ++j) {
-        if (pre[j] >= 0) {
-            const unsigned d = (k[j] >> shift) & 255;
-            const int pos = wbase[wid * 256 + d] + pre[j];
-            if (LAST) { ids_out[pos] = v[j]; boxes_out[pos] = bx[j]; }
-            else { Tri t; t.k = k[j]; t.id = v[j]; t.box = bx[j]; out[pos] = t; }
-        }
-    }
-}
-
-// tile count of the box at depth position j (0 past the visible ones), written where the in-place scan turns it into cum_sorted
-__global__ __launch_bounds__(256) void k_box_counts(int64_t N, const uint32_t *__restrict__ boxes_sorted, const int32_t *__restrict__ visible_dev,
-                                                    int32_t *__restrict__ cnt)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    boxes_sorted += blockIdx.y * N; cnt += blockIdx.y * N;
-    int c = 0;
-    if (i < (int64_t)visible_dev[blockIdx.y]) {
-        const uint32_t bx = boxes_sorted[i];
-        const int w = (int)((bx >> 8) & 255u) - (int)(bx & 255u), h = (int)(bx >> 24) - (int)((bx >> 16) & 255u);
-        c = (w > 0 && h > 0) ? w * h : 0;
-    }
-    cnt[i] = c;
-}
-
-// per-view workspace of the triple sort: 2 ping-pong triple buffers + digit tables + scan scratch + ticket
-struct TriPlan { size_t off_buf[2], off_hist, off_offs, off_scan, scan_bytes, off_cnt, total; int nb; };
-TriPlan make_tri_plan(int64_t n)
-{
-    TriPlan p;
-    p.nb = (int)((n + RB - 1) / RB);
-    if (p.nb < 1) p.nb = 1;
-    size_t o = 0;
-    for (int i = 0; i < 2; ++i) { p.off_buf[i] = o; o += al(12 * (size_t)n + 16); }
-    p.off_hist = o; o += al(4 * 256 * (size_t)p.nb);
-    p.off_offs = o; o += al(4 * 256 * (size_t)p.nb);
-    const int64_t scan_n = 256 * (int64_t)p.nb > n ? 256 * (int64_t)p.nb : n;
-    p.scan_bytes = al(gc_raster_scan_workspace_bytes(scan_n));
-    p.off_scan = o; o += p.scan_bytes;
-    p.off_cnt = o; o += 256;
-    p.total = o;
-    return p;
-}
-
-void set_attr_tri() {}
-
-}  // namespace
-
-extern "C" {
-
-size_t gc_raster_order_boxes_views_workspace_bytes(int64_t N, int C) { return make_tri_plan(N > 0 ? N : 1).total * (size_t)(C > 0 ? C : 1); }
+size_t gc_raster_order_boxes_views_workspace_bytes(int64_t N, int C) { return make_plan(N > 0 ? N : 1, 12).total * (size_t)(C > 0 ? C : 1); }
 
 /* Depth order of C views on the packed tight boxes (see the block comment above): depth_pairs [C][N][2] and tile_boxes [C][N] as
  * gc_project_sh_fwd_views writes them -> depth_order [C][N] = ids of the VISIBLE Gaussians in (depth bits, id) order (entries past
@@ -896,38 +821,25 @@ int gc_raster_order_boxes_views(int64_t N, int C, const uint32_t *depth_pairs, c
         return hipMemsetAsync(count_dev, 0, 4 * (size_t)C, s) == hipSuccess ? GC_OK : GC_ELAUNCH;
     }
     GC_REQUIRE(depth_pairs && tile_boxes && depth_order && boxes_sorted && cum_sorted && workspace, "null pointer");
-    const TriPlan p = make_tri_plan(N);
+    const Plan p = make_plan(N, 12);
     if (workspace_bytes < p.total * (size_t)C) { gc::set_error("gc_raster_order_boxes_views: workspace too small"); return GC_ENOSPC; }
-    set_attr_tri();
     unsigned char *w = (unsigned char *)workspace;
     VS vs; vs.ws = (int64_t)(p.total / 4); vs.ext = N; vs.src = N; vs.nd = 1;
     {   // visible counts + the tickets of k_table_scan: one launch
         ClearJob cj = {};
         cj.base[0] = (unsigned char *)visible_dev; cj.stride[0] = 4; cj.words[0] = 1;
-        cj.base[1] = w + p.total * (size_t)0 + p.off_cnt; cj.stride[1] = p.total; cj.words[1] = 1;
+        cj.base[1] = w + p.off_cnt; cj.stride[1] = p.total; cj.words[1] = 1;
         clear_views(s, C, cj);
     }
-    int32_t *hist = (int32_t *)(w + p.off_hist), *offs = (int32_t *)(w + p.off_offs), *tick = (int32_t *)(w + p.off_cnt), *sums = (int32_t *)(w + p.off_scan);
-    const dim3 g((unsigned)p.nb, (unsigned)C);
-    const int64_t ne = 256 * (int64_t)p.nb;
-    const dim3 gscan((unsigned)((ne + TS_CHUNK - 1) / TS_CHUNK), (unsigned)C);
-    const size_t lds = 0;
-    Tri *a = (Tri *)(w + p.off_buf[0]), *b = (Tri *)(w + p.off_buf[1]);
-    // pass 0: external pairs + boxes in, visible triples out
-    hipLaunchKernelGGL(k_tri_hist<true>, g, dim3(RT), 0, s, (const void *)depth_pairs, N, (const int32_t *)nullptr, 0, p.nb, hist, visible_dev, vs);
-    hipLaunchKernelGGL(k_table_scan, gscan, dim3(256), 0, s, ne, hist, offs, sums, tick, vs);
-    hipLaunchKernelGGL((k_tri_scatter<true, false>), g, dim3(RT), lds, s, (const void *)depth_pairs, tile_boxes, a, (uint32_t *)nullptr, (uint32_t *)nullptr, N,
-                       (const int32_t *)nullptr, 0, p.nb, hist, offs, sums, vs);
-    for (int pass = 1; pass < 4; ++pass) {   // visible depths are > 0: the float bit pattern is monotone
-        hipLaunchKernelGGL(k_tri_hist<false>, g, dim3(RT), 0, s, (const void *)a, N, (const int32_t *)visible_dev, 8 * pass, p.nb, hist, (int32_t *)nullptr, vs);
-        hipLaunchKernelGGL(k_table_scan, gscan, dim3(256), 0, s, ne, hist, offs, sums, tick, vs);
-        if (pass < 3)
-            hipLaunchKernelGGL((k_tri_scatter<false, false>), g, dim3(RT), lds, s, (const void *)a, (const uint32_t *)nullptr, b, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                               N, (const int32_t *)visible_dev, 8 * pass, p.nb, hist, offs, sums, vs);
-        else
-            hipLaunchKernelGGL((k_tri_scatter<false, true>), g, dim3(RT), lds, s, (const void *)a, (const uint32_t *)nullptr, (Tri *)nullptr, (uint32_t *)depth_order, boxes_sorted,
-                               N, (const int32_t *)visible_dev, 8 * pass, p.nb, hist, offs, sums, vs);
-        Tri *t = a; a = b; b = t;
+    uint32_t *buf[2] = { (uint32_t *)(w + p.off_buf[0]), (uint32_t *)(w + p.off_buf[1]) };
+    Pass a = {};
+    a.item = TRIS; a.dbits = 8; a.n = N; a.vo = (uint32_t *)depth_order; a.bo = boxes_sorted; a.out_ext = true;
+    for (int pass = 0; pass < 4; ++pass) {   // visible depths are > 0: the float bit pattern is monotone
+        a.in_ext = pass == 0;                // pass 0: external pairs + boxes in, visible triples out; then visible_dev[view] triples
+        a.ki = a.in_ext ? depth_pairs : buf[(pass + 1) & 1]; a.vi = a.in_ext ? tile_boxes : nullptr;
+        a.n_dev = a.in_ext ? nullptr : visible_dev; a.visible_dev = a.in_ext ? visible_dev : nullptr;
+        a.ko = pass == 3 ? nullptr : buf[pass & 1]; a.shift = 8 * pass;
+        radix_pass(a, p, w, s, C, vs);
     }
     hipLaunchKernelGGL(k_box_counts, dim3(gc::cdiv(N, 256), (unsigned)C), dim3(256), 0, s, N, (const uint32_t *)boxes_sorted, (const int32_t *)visible_dev, cum_sorted);
     int rc = gc_raster_scan_tiles_views(N, C, cum_sorted, nullptr, cum_sorted, count_dev, w + p.off_scan, p.scan_bytes, (int64_t)p.total, (void *)s);

@@ -43,6 +43,26 @@ def test_loader_symbol_list_matches_header(built):
     assert l.gc_raster_scan_workspace_bytes(ctypes.c_int64(5000)) >= 3 * 4
 
 
+@pytest.mark.parametrize("n", [0, 1, 4095, 4096, 4097, 100003, (1 << 20) + 1])
+def test_binning_workspace_sizes_keep_their_layout(built, n):
+    """The *_workspace_bytes functions of the two-level binning are ABI (callers allocate by them): per view two ping-pong item buffers (pairs: a key
+    and a value array of 4 n + 4 bytes each; triples: 12 n + 16 bytes), two [256][workgroups of 4096] digit tables, the scan scratch (one word per
+    2048 entries of max(table, n), + 1) and 256 bytes for the ticket, every part rounded up to 256 bytes -- whatever computes the layout inside."""
+    from gaussctrl_amd import _lib
+    l = _lib.lib()
+    al = lambda x: (x + 255) & ~255
+    m = max(n, 1)
+    nb = max(1, -(-m // 4096))
+    tail = 2 * al(4 * 256 * nb) + al(4 * (-(-max(256 * nb, m) // 2048) + 1)) + 256
+    pair, tri = 4 * al(4 * m + 4) + tail, 2 * al(12 * m + 16) + tail
+    i64, i32 = ctypes.c_int64, ctypes.c_int
+    assert l.gc_raster_depth_order_workspace_bytes(i64(n)) == pair and l.gc_raster_bin_workspace_bytes(i64(n)) == pair
+    for c in (0, 1, 8):
+        assert l.gc_raster_depth_order_views_workspace_bytes(i64(n), i32(c)) == pair * max(c, 1)
+        assert l.gc_raster_bin_views_workspace_bytes(i64(n), i32(c)) == pair * max(c, 1)
+        assert l.gc_raster_order_boxes_views_workspace_bytes(i64(n), i32(c)) == tri * max(c, 1)
+
+
 def test_documented_entry_point_count_is_current():
     """DESIGN.md / INTEGRATION.md state how many entry points the header declares: the number must be the header's (it went stale twice)"""
     n = len(_declared())

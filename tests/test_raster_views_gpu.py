@@ -407,6 +407,64 @@ def test_sorted_boxes_chain_all_culled_and_capacity():
     assert np.array_equal(ovf, (cnt > mmax // 2).astype(np.int32)) and ovf.max() == 1
 
 
+def test_sorted_boxes_chain_unpacked_staged_tile_passes():
+    """The staged tile scatter with UNPACKED (tile, id) pairs, k_radix_scatter_staged<6, false>: taken only when 2 * 6 + ceil(log2 N) > 32, which no
+    rendered scene of the suite reaches.  N = 2^20 + 1 ids (21 id bits) on a 33 x 33 tile grid (1 089 tiles: 11 tile bits = 6 + 6), C = 1;
+    gc_raster_order_boxes_views + gc_raster_bin_sorted_views called directly on synthetic projection outputs: every key 0xFFFFFFFF (culled) except
+    ~5 000 rows spread over the whole id range, ids 0 and N - 1 among them, with positive float depths of 700 distinct values (ties) and boxes of
+    1 to 3 tiles each way, some ending at tile column / row 32.  Expectation with torch on the CPU: stable sort of the visible ids by key, their
+    boxes in that order, the boxes expanded row-major in that order, stable sort by tile id, bins from the tile counts -- all compared exactly.
+    M > 4096, so both tile passes cross a radix block.  (<5, false> needs N > 4 M Gaussians for at most 10 tile bits; it is the same template and is
+    covered by construction only.)"""
+    from gaussctrl_amd import _lib as L
+    lib = L.lib()
+    N, C, tx, ty = (1 << 20) + 1, 1, 33, 33
+    T = tx * ty
+    g = torch.Generator().manual_seed(11)
+    ids = torch.unique(torch.cat([torch.arange(0, N, 211), torch.tensor([0, N - 1])]))              # ascending
+    V = ids.numel()
+    keys = (0.5 + 0.01 * torch.randint(0, 700, (V,), generator=g).float()).view(torch.int32)    # positive floats: the bits sort like the values
+    w = torch.randint(1, 4, (V,), generator=g); h = torch.randint(1, 4, (V,), generator=g)
+    minx = torch.randint(0, 1 << 30, (V,), generator=g) % (tx - w + 1); miny = torch.randint(0, 1 << 30, (V,), generator=g) % (ty - h + 1)
+    minx[::7] = tx - w[::7]; miny[::5] = ty - h[::5]                                              # boxes that end at the last tile column / row
+    assert int((minx + w).max()) == tx and int((miny + h).max()) == ty and int(minx.min()) >= 0 and int(miny.min()) >= 0
+    pairs = torch.empty(C, N, 2, dtype=torch.int32); pairs[0, :, 0] = -1; pairs[0, :, 1] = torch.arange(N, dtype=torch.int32)
+    pairs[0, ids, 0] = keys
+    boxes = torch.zeros(C, N, dtype=torch.int32)
+    boxes[0, ids] = (minx | ((minx + w) << 8) | (miny << 16) | ((miny + h) << 24)).to(torch.int32)
+    # the expectation
+    o = torch.sort(keys.long(), stable=True).indices
+    e_order = ids[o].to(torch.int32); e_boxes = boxes[0, ids[o]]
+    cnt = (w * h)[o]; M = int(cnt.sum())
+    assert M > 4096 and V > 4096 and len(torch.unique(keys)) < V
+    e_cum = torch.full((N,), M, dtype=torch.int32); e_cum[:V] = torch.cumsum(cnt, 0).to(torch.int32)
+    j = torch.repeat_interleave(torch.arange(V), cnt)
+    i = torch.arange(M) - (torch.cumsum(cnt, 0) - cnt)[j]
+    q = i // w[o][j]
+    tiles = (miny[o][j] + q) * tx + minx[o][j] + (i - q * w[o][j])
+    e_ids = e_order[j][torch.sort(tiles, stable=True).indices]
+    tc = torch.bincount(tiles, minlength=T); end = torch.cumsum(tc, 0)
+    e_bins = torch.where(tc[:, None] > 0, torch.stack([end - tc, end], 1), torch.zeros(T, 2, dtype=torch.long)).to(torch.int32)
+    # the device chain
+    i32 = dict(device=DEV, dtype=torch.int32)
+    d_pairs, d_boxes = pairs.to(DEV), boxes.to(DEV)
+    order = torch.empty(C, N, **i32); bxs = torch.empty(C, N, **i32); cum = torch.empty(C, N, **i32); cnt_d = torch.empty(C, **i32); nvis = torch.empty(C, **i32)
+    st = L.stream_ptr()
+    wb = int(lib.gc_raster_order_boxes_views_workspace_bytes(L.i64(N), L.i32(C)))
+    ws = torch.empty(wb, dtype=torch.uint8, device=DEV)
+    L.check(lib.gc_raster_order_boxes_views(L.i64(N), L.i32(C), L.ptr(d_pairs), L.ptr(d_boxes), L.ptr(order), L.ptr(bxs), L.ptr(cum), L.ptr(cnt_d),
+                                            L.ptr(nvis), L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_order_boxes_views")
+    ids_s = torch.empty(C, M, **i32); bins = torch.empty(C, T, 2, **i32); ovf = torch.empty(C, **i32)
+    bb = int(lib.gc_raster_bin_views_workspace_bytes(L.i64(M), L.i32(C)))
+    bws = torch.empty(bb, dtype=torch.uint8, device=DEV)
+    L.check(lib.gc_raster_bin_sorted_views(L.i64(N), L.i32(C), L.i64(M), L.ptr(cnt_d), L.ptr(ovf), L.ptr(nvis), L.ptr(order), L.ptr(bxs), L.ptr(cum),
+                                           L.i32(tx), L.i32(ty), L.ptr(ids_s), L.ptr(bins), L.ptr(bws), L.C.c_size_t(bb), st), "gc_raster_bin_sorted_views")
+    assert int(nvis[0]) == V and int(cnt_d[0]) == M and int(ovf[0]) == 0
+    assert torch.equal(order[0, :V].cpu(), e_order) and torch.equal(bxs[0, :V].cpu(), e_boxes)
+    assert torch.equal(cum[0].cpu(), e_cum)
+    assert torch.equal(ids_s[0].cpu(), e_ids) and torch.equal(bins[0].cpu(), e_bins)
+
+
 # ---------------------------------------------------------------------------------------- every instantiation of the shared projection pieces
 def _project_views(lib, L, ops, tp, cams, deg, n_use, W, H):
     """gc_project_sh_fwd_views on the test scene: the per-view state [C][N][..] the projection backward takes"""
