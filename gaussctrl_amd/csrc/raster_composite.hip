@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "raster_tile.h"
+#include "../../include/gaussctrl_absgrad.h"
 
 namespace {
 
@@ -139,10 +140,17 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_fwd(int H, int W, int tiles
 // is folded into the pixel load like the clamp's: vE = v_depth / alpha_px, voa += -v_depth * depth / alpha_px; the sentinel carries no
 // gradient.  Per (pixel, splat): g_e = fac * vE, v_alpha += (e_i T - S3 ra) vE, S3 += e_i fac.  A tenth partial rides the same reduction
 // (lane column 9), the staged blue value becomes the forward's SplatC{b, e}.  <false> is the kernel without any of it.
+//
+// ABS (gc_rasterize_bwd_abs_views): absgrad densification (AbsGS; gsplat's `absgrad`).  Next to the signed v_xy the kernel sums |g_x|, |g_y|
+// per (pixel, splat) -- taken after the pixel's whole v_sigma is formed (rgb, alpha and, with HAS_DEPTH, depth combined first), so opposite
+// pulls of different PIXELS no longer cancel while the channels of one pixel still do.  Two more partials ride the same reduction in lane
+// columns NP-2 / NP-1 and the staging lane flushes them into v_xy_abs [C][N][2].  A pair that passes no gradient (alpha cap, !valid) adds 0.
+// <.., false> is the kernel without any of it.
 struct DepthIO { const float *extra, *depth, *v_depth; float *v_extra; };      // [C][N], [C][H][W], [C][H][W]; [C][N] zero on entry
 struct NoDepthIO {};
+struct NoAbsIO {};
 
-template <bool HAS_DEPTH>
+template <bool HAS_DEPTH, bool ABS>
 __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles_x,
                                                          const int32_t *__restrict__ ids_sorted,
                                                          const int32_t *__restrict__ tile_bins,
@@ -154,9 +162,10 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                                                          const float *__restrict__ pre_clamp,
                                                          float *__restrict__ v_xy, float *__restrict__ v_conic,
                                                          float *__restrict__ v_colors, float *__restrict__ v_opacity, CV cv,
-                                                         std::conditional_t<HAS_DEPTH, DepthIO, NoDepthIO> dz)
+                                                         std::conditional_t<HAS_DEPTH, DepthIO, NoDepthIO> dz,
+                                                         std::conditional_t<ABS, float *, NoAbsIO> v_xy_abs)
 {
-    constexpr int NP = HAS_DEPTH ? 10 : 9;                              // partials per splat
+    constexpr int NP = (HAS_DEPTH ? 10 : 9) + (ABS ? 2 : 0);            // partials per splat
     {
         const int64_t v = blockIdx.z, hw = (int64_t)H * W;
         ids_sorted += v * cv.m; tile_bins += v * 2 * cv.tiles; xys += v * 2 * cv.n; conics += v * 3 * cv.n; colors += v * 3 * cv.n;
@@ -166,6 +175,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
         if (pre_clamp) pre_clamp += v * 3 * hw;
         v_xy += v * 2 * cv.n; v_conic += v * 3 * cv.n; v_colors += v * 3 * cv.n; v_opacity += v * cv.n;
         if constexpr (HAS_DEPTH) { dz.extra += v * cv.n; dz.depth += v * hw; dz.v_depth += v * hw; dz.v_extra += v * cv.n; }
+        if constexpr (ABS) v_xy_abs += v * 2 * cv.n;
     }
     __shared__ SplatA sA[BLOCK];
     __shared__ SplatB sB[BLOCK];
@@ -252,6 +262,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 const bool valid = (k <= bin_final) && !(sigma < 0.f || alpha < ALPHA_MIN);
                 if (!__any(valid)) continue;
                 float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_cxx = 0.f, g_cxy = 0.f, g_cyy = 0.f, g_x = 0.f, g_y = 0.f, g_o = 0.f, g_e = 0.f;
+                float g_ax = 0.f, g_ay = 0.f;
                 if (valid) {
                     const float ra = __builtin_amdgcn_rcpf(1.f - alpha);      // 1-ulp reciprocal: alpha <= 0.999, the IEEE division sequence is 10 instructions
                     T *= ra;
@@ -278,6 +289,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                     g_x = v_sigma * (a.cxx * dx + bb.cxy * dy);
                     g_y = v_sigma * (bb.cxy * dx + bb.cyy * dy);
                     g_o = va;
+                    if constexpr (ABS) { g_ax = fabsf(g_x); g_ay = fabsf(g_y); }
                 }
                 g_r = row_sum(g_r); g_g = row_sum(g_g); g_b = row_sum(g_b);
                 g_cxx = row_sum(g_cxx); g_cxy = row_sum(g_cxy); g_cyy = row_sum(g_cyy);
@@ -286,12 +298,13 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 x = col == 1 ? g_g : x; x = col == 2 ? g_b : x; x = col == 3 ? g_cxx : x; x = col == 4 ? g_cxy : x;
                 x = col == 5 ? g_cyy : x; x = col == 6 ? g_x : x; x = col == 7 ? g_y : x; x = col == 8 ? g_o : x;
                 if constexpr (HAS_DEPTH) { g_e = row_sum(g_e); x = col == 9 ? g_e : x; }
+                if constexpr (ABS) { g_ax = row_sum(g_ax); g_ay = row_sum(g_ay); x = col == NP - 2 ? g_ax : x; x = col == NP - 1 ? g_ay : x; }
                 x = xor_rows_sum(x);
                 if (lane < NP) __hip_atomic_fetch_add(&sG[lane * BLOCK + t], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
         __syncthreads();
-        if (gid >= 0) {                                                 // flush: nine (ten) atomics per (tile, splat) that was touched at all
+        if (gid >= 0) {                                                 // flush: NP atomics per (tile, splat) that was touched at all
             float v[NP];
 #pragma unroll
             for (int q = 0; q < NP; ++q) { v[q] = sG[q * BLOCK + tid]; sG[q * BLOCK + tid] = 0.f; }
@@ -309,6 +322,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                 unsafeAtomicAdd(v_xy + 2 * gid + 1, v[7]);
                 unsafeAtomicAdd(v_opacity + gid, v[8]);
                 if constexpr (HAS_DEPTH) unsafeAtomicAdd(dz.v_extra + gid, v[9]);
+                if constexpr (ABS) { unsafeAtomicAdd(v_xy_abs + 2 * gid, v[NP - 2]); unsafeAtomicAdd(v_xy_abs + 2 * gid + 1, v[NP - 1]); }
             }
         }
         // the next staging pass overwrites sA / sB / sMask: every wave has left the loop (barrier above); sG slots are private to
@@ -368,21 +382,23 @@ static int rasterize_bwd_impl(const char *what, int C, int64_t N, int64_t M_cap,
                               const int32_t *tile_bins, const float *xys, const float *conics, const float *colors,
                               const float *opacities, const float *background, const float *final_Ts, const int32_t *final_index,
                               const float *v_out, const float *v_out_alpha, const float *pre_clamp, float *v_xy, float *v_conic,
-                              float *v_colors, float *v_opacity, void *stream, const DepthIO *dz = nullptr)
+                              float *v_colors, float *v_opacity, void *stream, const DepthIO *dz = nullptr, float *v_xy_abs = nullptr)
 {
     if (!(img_h > 0 && img_w > 0 && tiles_x == (img_w + TILE - 1) / TILE && tiles_y == (img_h + TILE - 1) / TILE)) {
         gc::set_error("%s: tile bounds do not match the image size", what); return GC_EINVAL;
     }
     CV cv; cv.n = N; cv.n_op = shared_opacities ? 0 : N; cv.m = M_cap; cv.tiles = tiles_x * tiles_y; cv.bg = shared_background ? 0 : 3;
     dim3 grid(tiles_x, tiles_y, C), block(BLOCK);
-    if (dz)
-        hipLaunchKernelGGL(k_rasterize_bwd<true>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins,
-                           xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic,
-                           v_colors, v_opacity, cv, *dz);
-    else
-        hipLaunchKernelGGL(k_rasterize_bwd<false>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins,
-                           xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic,
-                           v_colors, v_opacity, cv, NoDepthIO{});
+    // the kernel's last two parameters are the empty structs where a switch is off
+    const auto launch = [&](auto kernel, auto dz_arg, auto abs_arg) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                           opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity, cv,
+                           dz_arg, abs_arg);
+    };
+    if (dz && v_xy_abs) launch(k_rasterize_bwd<true, true>, *dz, v_xy_abs);
+    else if (v_xy_abs) launch(k_rasterize_bwd<false, true>, NoDepthIO{}, v_xy_abs);
+    else if (dz) launch(k_rasterize_bwd<true, false>, *dz, NoAbsIO{});
+    else launch(k_rasterize_bwd<false, false>, NoDepthIO{}, NoAbsIO{});
     return gc::check_launch(what);
 }
 
@@ -439,6 +455,28 @@ int gc_rasterize_bwd_depth_views(int C, int64_t N, int64_t M_cap, int shared_opa
     return rasterize_bwd_impl("gc_rasterize_bwd_depth_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
                               gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
                               pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream, &dz);
+}
+
+/* absgrad densification (include/gaussctrl_absgrad.h, k_rasterize_bwd<.., true>): the arguments of gc_rasterize_bwd_depth_views plus v_xy_abs
+ * [C][N][2], ZERO on entry, which receives sum over pixels of (|dL_p/dx|, |dL_p/dy|).  The depth quartet is all NULL (the form without depth)
+ * or all set. */
+int gc_rasterize_bwd_abs_views(int C, int64_t N, int64_t M_cap, int shared_opacities, int shared_background, int img_h, int img_w, int tiles_x,
+                               int tiles_y, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys, const float *conics,
+                               const float *colors, const float *opacities, const float *background, const float *final_Ts,
+                               const int32_t *final_index, const float *v_out, const float *v_out_alpha, const float *pre_clamp, float *v_xy,
+                               float *v_conic, float *v_colors, float *v_opacity, const float *extra, const float *depth, const float *v_depth,
+                               float *v_extra, float *v_xy_abs, void *stream)
+{
+    GC_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && M_cap >= 0, "bad arguments");
+    const int set = (extra != nullptr) + (depth != nullptr) + (v_depth != nullptr) + (v_extra != nullptr);
+    if (N > 0) {      // (the per-Gaussian arrays of an empty scene have no address)
+        GC_REQUIRE(v_xy_abs, "v_xy_abs is required (gc_rasterize_bwd_views / gc_rasterize_bwd_depth_views are the forms without it)");
+        GC_REQUIRE(set == 0 || set == 4, "extra, depth, v_depth and v_extra must be all NULL (no depth) or all set");
+    }
+    const DepthIO dz{extra, depth, v_depth, v_extra};
+    return rasterize_bwd_impl("gc_rasterize_bwd_abs_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
+                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
+                              pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream, set == 4 ? &dz : nullptr, v_xy_abs);
 }
 
 }  // extern "C"

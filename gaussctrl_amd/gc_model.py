@@ -70,6 +70,14 @@ class GaussCtrlModelConfig(_ModelConfigBase):
                                                   # view also multiplies the opacity by sqrt(det(cov2d) / det(cov2d + 0.3 I)) (ops.RenderAux.antialiased),
                                                   # for scenes trained that way or rendered below their training resolution.  Declared here, so the
                                                   # field exists (and defaults to the reference's behaviour) with and without nerfstudio
+    use_absgrad: bool = False                     # True: absgrad densification (AbsGS; later splatfacto's switch of that name) -- the training
+                                                  # backward also sums |dL_p/dxy| per pixel (ops.RenderAux.absgrad -> GaussCtrlModel.xys_absgrad) and
+                                                  # the on-device refinement accumulates ITS norm instead of the signed gradient's, so a large splat
+                                                  # whose pixels pull in opposite directions is still split.  densify_grad_thresh keeps its default
+                                                  # 0.0002: later splatfacto pairs absgrad with about 0.0008 (a figure recalled from nerfstudio 1.1,
+                                                  # not checked against its source) -- raise it yourself, absolute sums are several times larger.
+                                                  # Declared here like rasterize_mode; under nerfstudio only the property is offered, the inherited
+                                                  # splatfacto callbacks keep reading xys_grad
 
     def __post_init__(self):
         parent = getattr(super(), "__post_init__", None)
@@ -185,6 +193,7 @@ class GaussCtrlModel(_ModelBase):
             aux.grad_into, aux.grad_accumulate = self.grad_into, False
         train_depth = bool(self.training and getattr(self.config, "output_depth_during_training", False))
         aux.depth_grad = train_depth
+        aux.absgrad = bool(self.training and getattr(self.config, "use_absgrad", False))
         want_depth = train_depth or not self.training
         rgb, alpha, depth = ops.render_view(*p, cam, background, want_depth, n, aux)
         self.xys, self.radii = aux.xys, aux.radii
@@ -208,6 +217,11 @@ class GaussCtrlModel(_ModelBase):
     def xys_grad(self):
         """gradient of the loss w.r.t. the projected centres (what splatfacto's after_train reads as xys.grad)."""
         return self._aux.xys_grad
+
+    @property
+    def xys_absgrad(self):
+        """sum over pixels of |dL_p/dxy| of the last training backward (config.use_absgrad; None without it or before the backward)."""
+        return self._aux.xys_absgrad
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera: Cameras, obb_box=None) -> Dict[str, torch.Tensor]:    # :208-221

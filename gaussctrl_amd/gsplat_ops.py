@@ -354,6 +354,12 @@ class RenderAux:
     # [C, N] from render_views (0 where the view culls the Gaussian); None after a classic one.
     antialiased = False
     compensation = None
+    # absgrad densification (AbsGS; use_absgrad of later splatfacto, include/gaussctrl_absgrad.h): True makes the compositing backward also sum
+    # |dL_p/dx|, |dL_p/dy| over the pixels p of every Gaussian (rgb, alpha and depth combined per pixel, then abs) into `xys_absgrad`: [N, 2]
+    # from render_view, [C, N, 2] from render_views; None until a backward with the switch has run.  xys_grad and the leaf gradients are what
+    # they are without it.  Combines freely with depth_grad, antialiased and grad_into (the projection backward is not involved).
+    absgrad = False
+    xys_absgrad = None
 
 
 def _finalize(ctx, npix, img, dep, fT):
@@ -452,6 +458,7 @@ class _RenderView(torch.autograd.Function):
             aux.tile_boxes = boxes
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
             aux.xys_grad = None
+            aux.xys_absgrad = None
             aux.compensation = comp
         ctx.meta = (cam, tb, N, sh_degree, int(sh_degree_to_use), V, P, O)
         ctx.aux = aux
@@ -469,7 +476,20 @@ class _RenderView(torch.autograd.Function):
         vo = _c(v_img) if v_img is not None else torch.zeros(H, W, 3, device=dev)
         va = _c(v_alpha) if v_alpha is not None else None
         v_ex = None
-        if ctx.depth_grad and v_dep is not None:          # depth channel: the C = 1 case of the batched entry points
+        with_depth = ctx.depth_grad and v_dep is not None
+        if ctx.aux is not None and ctx.aux.absgrad:        # absgrad: one entry point for both depth forms (NULL quartet = no depth), C = 1
+            depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if with_depth else (None, None, None)
+            vbuf = torch.zeros(N * (12 if with_depth else 11), device=dev)
+            v_xy = vbuf[:2 * N].view(N, 2); v_conic = vbuf[2 * N:5 * N].view(N, 3); v_col = vbuf[5 * N:8 * N].view(N, 3)
+            v_op = vbuf[8 * N:9 * N]; v_abs = vbuf[9 * N:11 * N].view(N, 2)
+            v_ex = vbuf[11 * N:] if with_depth else None
+            L.check(L.lib().gc_rasterize_bwd_abs_views(
+                L.i32(1), L.i64(N), L.i64(ids_s.numel()), L.i32(1), L.i32(1), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+                L.ptr(v_ex), L.ptr(v_abs), L.stream_ptr()), "gc_rasterize_bwd_abs_views")
+            ctx.aux.xys_absgrad = v_abs
+        elif with_depth:                                   # depth channel: the C = 1 case of the batched entry points
             depths, dep = ctx.saved_tensors[17:]
             vd = _c(v_dep)
             vbuf = torch.zeros(N * 10, device=dev)
@@ -619,6 +639,7 @@ class _RenderViews(torch.autograd.Function):
             aux.M = (cnt, ovf)                          # per-view device counts / overflow flags ([C] each)
             aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, None
             aux.xys_grad = None
+            aux.xys_absgrad = None
             aux.compensation = comp
         ctx.meta = (cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, int(sh_degree_to_use))
         ctx.aux = aux
@@ -639,13 +660,22 @@ class _RenderViews(torch.autograd.Function):
         va = _c(v_alpha) if v_alpha is not None else None
         with_depth = ctx.depth_grad and v_dep is not None
         shared_op = 0 if ctx.comp is not None else 1
-        vbuf = torch.zeros(C * N * (10 if with_depth else 9), device=dev)   # v_xy | v_conic | v_colors | v_opacity (| v_extra), each [C][N][..]
+        absgrad = ctx.aux is not None and ctx.aux.absgrad
+        # v_xy | v_conic | v_colors | v_opacity (| v_extra) (| v_xy_abs), each [C][N][..]
+        vbuf = torch.zeros(C * N * ((10 if with_depth else 9) + (2 if absgrad else 0)), device=dev)
         v_xy = vbuf[:2 * C * N].view(C, N, 2); v_conic = vbuf[2 * C * N:5 * C * N].view(C, N, 3)
         v_col = vbuf[5 * C * N:8 * C * N].view(C, N, 3); v_op = vbuf[8 * C * N:9 * C * N].view(C, N)
-        v_ex = vbuf[9 * C * N:].view(C, N) if with_depth else None
-        if with_depth:
-            depths, dep = ctx.saved_tensors[17:]
-            vd = _c(v_dep)
+        v_ex = vbuf[9 * C * N:10 * C * N].view(C, N) if with_depth else None
+        depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if with_depth else (None, None, None)
+        if absgrad:                 # one entry point for both depth forms (NULL quartet = no depth)
+            v_abs = vbuf[vbuf.numel() - 2 * C * N:].view(C, N, 2)
+            L.check(lib.gc_rasterize_bwd_abs_views(
+                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+                L.ptr(v_ex), L.ptr(v_abs), st), "gc_rasterize_bwd_abs_views")
+            ctx.aux.xys_absgrad = v_abs
+        elif with_depth:
             L.check(lib.gc_rasterize_bwd_depth_views(
                 L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
                 L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),

@@ -97,10 +97,16 @@ class RefineState:
                 "gc_refine_accumulate_views")
 
     def accumulate(self, model):
-        """after a training backward: model._aux.xys_grad, model.radii, model.last_size (nothing to do when nothing was rendered)"""
+        """after a training backward: model._aux.xys_grad -- with config.use_absgrad model._aux.xys_absgrad, the per-pixel absolute sums --
+        model.radii, model.last_size (nothing to do when nothing was rendered)"""
         g = model._aux.xys_grad
         if g is None or model.radii is None or model.last_size is None:
             return
+        if getattr(model.config, "use_absgrad", False):
+            g = model._aux.xys_absgrad
+            if g is None:
+                raise L.GaussCtrlHipError("refine.accumulate: config.use_absgrad is set but the backward left no xys_absgrad "
+                                          "(the render did not run with RenderAux.absgrad)")
         self.accumulate_views(g, model.radii, int(model.last_size[0]), int(model.last_size[1]))
 
     # ------------------------------------------------------------------------------------------------------------------
