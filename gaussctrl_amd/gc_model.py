@@ -78,12 +78,28 @@ class GaussCtrlModelConfig(_ModelConfigBase):
                                                   # not checked against its source) -- raise it yourself, absolute sums are several times larger.
                                                   # Declared here like rasterize_mode; under nerfstudio only the property is offered, the inherited
                                                   # splatfacto callbacks keep reading xys_grad
+    densify_strategy: str = "default"             # "default": the refinement above (CullCallback, or RefineCallback with refine_on_device);
+                                                  # "mcmc": the strategy of 3DGS-MCMC (gsplat 1.x MCMCStrategy) on the kernels of
+                                                  # csrc/train_mcmc.hip -- the stand-alone model's callbacks become [StepCallback, McmcCallback]
+                                                  # whatever refine_on_device says, and its loss gains the two regularisers below.  The formulas
+                                                  # are recalled from the paper and gsplat 1.x, not checked against their source
+                                                  # (include/gaussctrl_mcmc.h is the contract).  Under nerfstudio the fields exist and are
+                                                  # validated; the inherited callbacks and loss stay
+    mcmc_cap_max: int = 1_000_000                 # the scene never grows past this many Gaussians
+    mcmc_noise_lr: float = 5e5                    # the perturbation of the means is scaled by (xyz learning rate) * mcmc_noise_lr
+    mcmc_min_opacity: float = 0.005               # sigmoid(opacity) <= this: dead, relocated at the next refinement step
+    mcmc_refine_start_iter: int = 500             # refinement steps: start < step < stop and step % every == 0.  A GaussCtrl run starts at
+    mcmc_refine_stop_iter: int = 25_000           # step 30000: raise mcmc_refine_stop_iter for relocation / growth to act there
+    mcmc_refine_every: int = 100
+    mcmc_opacity_reg: float = 0.01                # loss += mcmc_opacity_reg * mean(sigmoid(opacities))
+    mcmc_scale_reg: float = 0.01                  # loss += mcmc_scale_reg * mean(exp(scales))
 
     def __post_init__(self):
         parent = getattr(super(), "__post_init__", None)
         if parent is not None:
             parent()
         _antialiased(self.rasterize_mode)
+        _mcmc(self.densify_strategy)
 
 
 RASTERIZE_MODES = ("classic", "antialiased")
@@ -94,6 +110,16 @@ def _antialiased(mode) -> bool:
     if mode not in RASTERIZE_MODES:
         raise ValueError(f"rasterize_mode must be one of {RASTERIZE_MODES}, got {mode!r}")
     return mode == "antialiased"
+
+
+DENSIFY_STRATEGIES = ("default", "mcmc")
+
+
+def _mcmc(strategy) -> bool:
+    """densify_strategy -> is it "mcmc"; anything but the two names is a ValueError"""
+    if strategy not in DENSIFY_STRATEGIES:
+        raise ValueError(f"densify_strategy must be one of {DENSIFY_STRATEGIES}, got {strategy!r}")
+    return strategy == "mcmc"
 
 
 class GaussCtrlModel(_ModelBase):
@@ -147,10 +173,13 @@ class GaussCtrlModel(_ModelBase):
         part of refinement_after that still acts after step 30000 (> stop_split_at = 15000): opacity / scale culling every
         `refine_every` steps [recall nerfstudio 1.0.0 splatfacto.py; SURVEY.md 3.5].  With config.refine_on_device the stand-alone model
         runs all of splatfacto's refinement on the device instead (gc_trainer.RefineCallback, which also covers that cull); under nerfstudio
-        the inherited callbacks stay whatever the switch says."""
+        the inherited callbacks stay whatever the switch says.  With config.densify_strategy = "mcmc" the stand-alone model returns
+        [StepCallback, McmcCallback] (gaussctrl_amd/mcmc.py), whatever refine_on_device says."""
         if HAVE_NERFSTUDIO:
             return super().get_training_callbacks(training_callback_attributes)
-        from .gc_trainer import CullCallback, RefineCallback, StepCallback
+        from .gc_trainer import CullCallback, McmcCallback, RefineCallback, StepCallback
+        if _mcmc(getattr(self.config, "densify_strategy", "default")):       # (checked again: the field may have been assigned)
+            return [StepCallback(self), McmcCallback(self, training_callback_attributes.optimizers)]
         if getattr(self.config, "refine_on_device", False):
             dm = getattr(getattr(training_callback_attributes, "pipeline", None), "datamanager", None)
             n_train = len(getattr(dm, "train_data", None) or ())
@@ -269,7 +298,12 @@ class GaussCtrlModel(_ModelBase):
         return {"psnr": -10.0 * torch.log10(mse.clamp_min(1e-12)), "gaussian_count": torch.tensor(self.num_points)}
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, torch.Tensor]:
-        """SplatfactoModel.get_loss_dict [recall, SURVEY 8a/A8]: (1-l)*L1 + l*(1-SSIM), l = 0.2."""
+        """SplatfactoModel.get_loss_dict [recall, SURVEY 8a/A8]: (1-l)*L1 + l*(1-SSIM), l = 0.2.  The stand-alone model with
+        config.densify_strategy = "mcmc" adds the strategy's two regularisers (plain torch: two reductions over N, not the hot path)."""
         from .train_ops import l1_ssim_loss
         gt = batch["image"].to(self.device)
-        return {"main_loss": l1_ssim_loss(outputs["rgb"], gt, self.config.ssim_lambda)}
+        loss = {"main_loss": l1_ssim_loss(outputs["rgb"], gt, self.config.ssim_lambda)}
+        if not HAVE_NERFSTUDIO and _mcmc(getattr(self.config, "densify_strategy", "default")):
+            loss["opacity_reg"] = self.config.mcmc_opacity_reg * torch.sigmoid(self.opacities).mean()
+            loss["scale_reg"] = self.config.mcmc_scale_reg * torch.exp(self.scales).mean()
+        return loss

@@ -527,6 +527,10 @@ class GaussCtrlPipeline(_PipelineBase):
         see train_iteration).  accumulating: the caller accumulates gradients over several steps (gc_trainer gradient_accumulation_steps
         > 1): the autograd .grad path with a flat all-reduce of the accumulated tensors is used instead of the write-once flat buffer."""
         multi = self.world_size > 1
+        if multi and getattr(getattr(self.model, "config", None), "densify_strategy", "default") == "mcmc":
+            # "throughput" / "sharded": the fused backward owns the leaf gradients (grad_into) and the regularisers' autograd gradients would
+            # not reach them; no multi-GPU mode relocates or grows its replicas together
+            raise ValueError("densify_strategy 'mcmc' trains on one GPU only (world_size > 1 is out of its scope)")
         mode = self.config.train_mode if multi else "single"
         if mode not in ("single", "parity", "throughput", "sharded"):
             raise ValueError(f"train_mode must be 'parity', 'throughput' or 'sharded', not {mode!r}")

@@ -247,3 +247,22 @@ class RefineCallback(_Callback):
         if last:
             self.n_culled += last["n_in"] - last["n_survivors"]          # originals that left (culled ones and split sources)
             self.n_added += last["n_out"] - last["n_survivors"]
+
+
+class McmcCallback(_Callback):
+    """The MCMC densification strategy on the device (gaussctrl_amd/mcmc.py, csrc/train_mcmc.hip): at every refinement step of
+    mcmc.schedule dead Gaussians are relocated onto live ones and the scene grows 5 % towards mcmc_cap_max; after EVERY training iteration
+    the means are perturbed with this step's xyz learning rate.  Opt-in: GaussCtrlModelConfig.densify_strategy = "mcmc"."""
+    where = ("after_train_iteration",)
+
+    def __init__(self, model, optimizers: dict):
+        self.model, self.optimizers = model, optimizers
+        self.n_relocated = 0
+        self.n_added = 0
+
+    def run(self, step, sampled_relocate=None, sampled_add=None, noise=None):
+        from . import mcmc
+        if mcmc.schedule(self.model.config, step):
+            self.n_relocated += mcmc.relocate(self.model, self.optimizers, sampled_relocate)
+            self.n_added += mcmc.add_new(self.model, self.optimizers, sampled_add)
+        mcmc.inject_noise(self.model, self.optimizers["xyz"].param_groups[0]["lr"], noise)      # the value train_iteration has just set
