@@ -725,6 +725,41 @@ __global__ __launch_bounds__(NT, 2) void k_gemm(const GemmArgs g)
 // (l&7) ^ ((row>>1)&7)).  Lanes that fall outside the tensor / in the conv padding fetch from a 16-byte zero page.
 // The DMA is issued from inline asm (M0 = LDS base) so hipcc's waitcnt pass does not drain it with vmcnt(0) before every
 // ds_read; ordering is by the explicit vmcnt + s_barrier below.  One workgroup per CU (96-108 KiB LDS), 2 waves per SIMD.
+// INVARIANT: the k loop holds NO compiler-generated VMEM access -- no scratch (private memory) load or store, no spill, no global load the
+// compiler can see.  The wait-count pass does not know the inline-asm DMA is in flight, so it waits for any load of its own with vmcnt(0),
+// which drains the ring every k-tile (tile kt+2 included); and a store counts in vmcnt on gfx9, so every counted vmcnt(N) after one is
+// stricter than written and the 3-stage ring runs as a shallower one.  Loop state therefore lives in registers BY CONSTRUCTION: values passed
+// and returned, never a mutable local that lambdas advance through a reference (the tap cursor of the fast convs did, rounds 1-6: 12 bytes of
+// private memory, 2 scratch loads + vmcnt(0) + 5 scratch stores per k-tile in every MODE 2 / 4 instantiation).  tests/test_kernel_resources.py
+// holds .private_segment_fixed_size and .vgpr_spill_count of these kernels at 0.
+// k-tile cursor of the fast 3x3 convs (k_gemm8 MODE 2 | 4, k_gemm8q MODE 2): the tap and the first input channel of the next k-tile to fetch,
+// as (fast, slow) coordinate of the k order --
+//   tap-inner: fast = tap (0 .. 8, step 1), slow = channel (step bk): the nine taps of a channel slice, then the next slice;
+//   tap-outer: fast = channel (0 .. Cin, step bk), slow = tap (step 1): the slices of a tap, then the next tap.
+// Both orders advance by the same five scalar instructions, and every field is assigned exactly once per k-tile from wave-uniform values, so
+// the cursor stays in SGPRs (see issue_begin in k_gemm8).
+struct KCur { int fast, slow; };
+struct KOrder {
+    int lim, step_fast, step_slow;
+    bool tap_inner;
+    __device__ __forceinline__ KOrder(bool tap_inner_, int bk, int cin)
+        : lim(tap_inner_ ? 9 : cin), step_fast(tap_inner_ ? 1 : bk), step_slow(tap_inner_ ? bk : 1), tap_inner(tap_inner_) {}
+    // cursor of k-tile j of the whole K axis
+    __device__ __forceinline__ KCur at(int j, int bk, int cin) const
+    {
+        const int tap = tap_inner ? j % 9 : (j * bk) / cin, ci = tap_inner ? (j / 9) * bk : j * bk - tap * cin;
+        return tap_inner ? KCur{tap, ci} : KCur{ci, tap};
+    }
+    __device__ __forceinline__ int tap(const KCur c) const { return tap_inner ? c.fast : c.slow; }
+    __device__ __forceinline__ int ci(const KCur c) const { return tap_inner ? c.slow : c.fast; }
+    __device__ __forceinline__ KCur next(const KCur c) const
+    {
+        const int f = c.fast + step_fast;
+        const bool wrap = f >= lim;
+        return KCur{wrap ? f - lim : f, wrap ? c.slow + step_slow : c.slow};
+    }
+};
+
 __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst)
 {
     unsigned keep;
@@ -856,24 +891,26 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
     //     (scripts/ubench/gemm_loop.hip, profiles/r06_gemm_loop_conv_order.txt: 644 -> 864 TF/s at Cin = 320 on the same loop).
     // The products summed per output are the same set; only the summation order differs.
     const bool tap_inner = CONVF && g.conv_korder != 0;
-    int ld_tap = 0, ld_ci = 0;
-    if (CONVF && kt0 > 0) {
-        if (tap_inner) { ld_tap = kt0 % 9; ld_ci = (kt0 / 9) * BK; }
-        else { ld_tap = (kt0 * BK) / g.Cin; ld_ci = kt0 * BK - ld_tap * g.Cin; }
-    }
+    // The (tap, channel slice) of the next k-tile to fetch is a VALUE (KCur / KOrder above): issue_begin takes the cursor and
+    // returns its successor, every field assigned exactly once, so it lives in SGPRs.  As two mutable locals advanced in place behind a
+    // reference capture, the stores of the two k orders were merged into one store through a SELECTED address, the locals stayed in private
+    // memory, and the k loop carried two scratch loads, a compiler-placed vmcnt(0) and five scratch stores per k-tile (the invariant above).
+    const KOrder kord(tap_inner, BK, g.Cin);
+    KCur cur0 = {0, 0};
+    if (CONVF && kt0 > 0) cur0 = kord.at(kt0, BK, g.Cin);
 
     // DMA of one k-tile, split into per-instruction pieces so that the main loop can place them between MFMAs.
-    struct TileSrc { int kb, dy_u, dx_u, tap_off, tap; unsigned sbase; };
-    auto issue_begin = [&](int kt, int stage) __attribute__((always_inline)) -> TileSrc {
+    struct TileSrc { int kb, dy_u, dx_u, tap_off, tap; unsigned sbase; KCur next; };
+    auto issue_begin = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> TileSrc {
         TileSrc t;
-        t.kb = (kt0 + kt) * BK; t.dy_u = 0; t.dx_u = 0; t.tap_off = 0; t.tap = 0;
+        t.kb = (kt0 + kt) * BK; t.dy_u = 0; t.dx_u = 0; t.tap_off = 0; t.tap = 0; t.next = c;
         if (CONVF) {
-            t.tap = ld_tap;
-            t.kb = __builtin_amdgcn_readfirstlane(ld_tap * g.Cin + ld_ci);          // W column of this k-tile (= (kt0 + kt) * BK in the tap-outer order)
-            t.dy_u = ld_tap / 3; t.dx_u = ld_tap - t.dy_u * 3;
-            t.tap_off = UPS ? ld_ci : (t.dy_u * g.Wi + t.dx_u) * g.Cin + ld_ci;
-            if (tap_inner) { if (++ld_tap == 9) { ld_tap = 0; ld_ci += BK; } }
-            else { ld_ci += BK; if (ld_ci >= g.Cin) { ld_ci -= g.Cin; ++ld_tap; } }
+            const int ci = kord.ci(c);
+            t.tap = kord.tap(c);
+            t.kb = __builtin_amdgcn_readfirstlane(t.tap * g.Cin + ci);          // W column of this k-tile (= (kt0 + kt) * BK in the tap-outer order)
+            t.dy_u = t.tap / 3; t.dx_u = t.tap - t.dy_u * 3;
+            t.tap_off = UPS ? ci : (t.dy_u * g.Wi + t.dx_u) * g.Cin + ci;
+            t.next = kord.next(c);
         }
         t.sbase = lds0 + stage * STAGE;
         return t;
@@ -920,12 +957,13 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
             glds16(src, dst);
         }
     };
-    auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
-        const TileSrc t = issue_begin(kt, stage);
+    auto issue = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> KCur {
+        const TileSrc t = issue_begin(kt, stage, c);
 #pragma unroll
         for (int i = 0; i < AI; ++i) issue_a(t, i);
 #pragma unroll
         for (int i = 0; i < WI; ++i) issue_w(t, i, wid + 8 * i < WG);
+        return t.next;
     };
 
     f32x4 acc[NTW][MT];
@@ -981,7 +1019,7 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
     // MFMA block (16-20 x 16 clk) to land.  Counted vmcnt: tile kt+2 stays in flight across the barrier.
     const bool w3 = (wid + 8 * (WI - 1)) < WG;     // this wave owns the last W group (instructions per tile are wave-uniform)
     Frag f0, f1;
-    const TileSrc tnone = {0, 0, 0, 0, 0, 0u};
+    const TileSrc tnone = {0, 0, 0, 0, 0, 0u, {0, 0}};
     // The whole k loop is instantiated twice (W3 = this wave issues WI / WI-1 W loads per tile) so that the counted waits and the
     // DMA pieces carry no run-time branches; the steady state (tiles kt+1 .. kt+3 exist) is a branch-free loop, the last three
     // k-tiles run through the generic tail.
@@ -992,9 +1030,9 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         auto wait_tiles = [&](auto n_) __attribute__((always_inline)) {        // n tiles may stay in flight
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_)::value * GRPW) : "memory");
         };
-        issue(0, 0);
-        if (nk > 1) issue(1, 1);
-        if (nk > 2) issue(2, 2);
+        KCur cur = issue(0, 0, cur0);      // the cursor: a by-value loop variable of this copy of the loop
+        if (nk > 1) cur = issue(1, 1, cur);
+        if (nk > 2) cur = issue(2, 2, cur);
         // lean LayerNorm-folded consumer: the rows' statistics are summed over the producer's slabs HERE, under the first k-tiles' flight (the
         // prologue ends in vmcnt(0): it waits for those tiles too, which the loop would do next anyway)
         if constexpr (LNIN) row_stats_prologue<BM>(g, m_base, srow);
@@ -1008,21 +1046,24 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
             wait_tiles(std::integral_constant<int, 1>{});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of stage st are complete
             __builtin_amdgcn_s_barrier();    // tile kt+1 is in LDS for every wave; every wave finished reading stage st
-            const TileSrc t = issue_begin(kt + 3, st);
+            const TileSrc t = issue_begin(kt + 3, st, cur);
+            cur = t.next;
             block(f1, f0, st1, 0, true, t, std::true_type{}, w3_tag);
             st = st1;
         }
         for (; kt < nk; ++kt) {
             const int st1 = st + 1 == NS ? 0 : st + 1;
             block(f0, f1, st, 1, true, tnone, std::false_type{}, w3_tag);
-            if (kt + 1 < nk) {
+            const bool more = kt + 1 < nk;
+            if (more) {
                 if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-                block(f1, f0, st1, 0, true, tnone, std::false_type{}, w3_tag);
-            } else {
-                block(f1, f0, st1, 0, false, tnone, std::false_type{}, w3_tag);
             }
+            // ONE copy of this MFMA block (the fragment reads inside are the only difference of the last tile).  With a copy in either arm of
+            // the branch the register allocator kept TWO sets of accumulators here (block 1 wrote set B from set A, block 2 set A from set B):
+            // 16 NTW MT registers more than the steady state needs -- every MT 4 instantiation sat at the 256 cap and MODE 0 / 1 spilled.
+            block(f1, f0, st1, 0, more, tnone, std::false_type{}, w3_tag);
             st = st1;
         }
     };
@@ -1633,22 +1674,21 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     const unsigned char *Ab = (const unsigned char *)g.A, *Wb = (const unsigned char *)g.W, *Zp = (const unsigned char *)g.zeros;
     // (k order of the fast convs: tap-inner by default, as in k_gemm8 -- see the comment there; g.conv_korder = 0 restores tap-outer)
     const bool tap_inner = MODE == 2 && g.conv_korder != 0;
-    int ld_tap = 0, ld_ci = 0;
-    if (MODE == 2) {
-        if (tap_inner) { ld_tap = k0 % 9; ld_ci = (k0 / 9) * BKB; }
-        else { ld_tap = (k0 * BKB) / g.Cin; ld_ci = (k0 * BKB) % g.Cin; }
-    }
-    struct TileSrc { int kb, tap, tap_off; unsigned sbase; };
-    auto issue_begin = [&](int kt, int stage) __attribute__((always_inline)) -> TileSrc {
+    // the k-tile cursor is a value carried through the loop (SGPRs, no private memory): as in k_gemm8 -- see the comment there
+    const KOrder kord(tap_inner, BKB, g.Cin);
+    KCur cur0 = {0, 0};
+    if (MODE == 2) cur0 = kord.at(k0, BKB, g.Cin);
+    struct TileSrc { int kb, tap, tap_off; unsigned sbase; KCur next; };
+    auto issue_begin = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> TileSrc {
         TileSrc t;
-        t.kb = (k0 + kt) * BKB; t.tap = 0; t.tap_off = 0;
+        t.kb = (k0 + kt) * BKB; t.tap = 0; t.tap_off = 0; t.next = c;
         if (MODE == 2) {
-            t.tap = ld_tap;
-            t.kb = __builtin_amdgcn_readfirstlane(ld_tap * g.Cin + ld_ci);
-            const int dy = ld_tap / 3, dx = ld_tap - dy * 3;
-            t.tap_off = (dy * g.Wi + dx) * g.Cin + ld_ci;
-            if (tap_inner) { if (++ld_tap == 9) { ld_tap = 0; ld_ci += BKB; } }
-            else { ld_ci += BKB; if (ld_ci >= g.Cin) { ld_ci -= g.Cin; ++ld_tap; } }
+            const int ci = kord.ci(c);
+            t.tap = kord.tap(c);
+            t.kb = __builtin_amdgcn_readfirstlane(t.tap * g.Cin + ci);
+            const int dy = t.tap / 3, dx = t.tap - dy * 3;
+            t.tap_off = (dy * g.Wi + dx) * g.Cin + ci;
+            t.next = kord.next(c);
         }
         t.sbase = lds0 + stage * STAGE;
         return t;
@@ -1662,12 +1702,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     auto issue_w = [&](const TileSrc &t, int i, bool has) __attribute__((always_inline)) {
         if (has) glds16_s(Wb + (size_t)t.kb, (unsigned)w_off[i], t.sbase + (unsigned)(BM * 128 + (wid + 8 * i) * 1024));
     };
-    auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
-        const TileSrc t = issue_begin(kt, stage);
+    auto issue = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> KCur {
+        const TileSrc t = issue_begin(kt, stage, c);
 #pragma unroll
         for (int i = 0; i < AI; ++i) issue_a(t, i);
 #pragma unroll
         for (int i = 0; i < WI; ++i) issue_w(t, i, wid + 8 * i < WG);
+        return t.next;
     };
 
     f32x4 acc[NTW][MT];
@@ -1735,16 +1776,16 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     };
     const bool w3 = (wid + 8 * (WI - 1)) < WG;
     Frag f0, f1;
-    const TileSrc tnone = {0, 0, 0, 0u};
+    const TileSrc tnone = {0, 0, 0, 0u, {0, 0}};
     auto run = [&](auto w3_tag) __attribute__((always_inline)) {
         constexpr bool W3 = decltype(w3_tag)::value;
         constexpr int GRPW = AI + ((W3 || WG % 8 == 0) ? WI : WI - 1);
         auto wait_tiles = [&](auto n_) __attribute__((always_inline)) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_)::value * GRPW) : "memory");
         };
-        issue(0, 0);
-        if (nk > 1) issue(1, 1);
-        if (nk > 2) issue(2, 2);
+        KCur cur = issue(0, 0, cur0);
+        if (nk > 1) cur = issue(1, 1, cur);
+        if (nk > 2) cur = issue(2, 2, cur);
         if (nk > 2) wait_tiles(std::integral_constant<int, 2>{}); else if (nk > 1) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
         __builtin_amdgcn_s_barrier();
         load_frag(f0, 0);
@@ -1755,15 +1796,17 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
                 wait_tiles(std::integral_constant<int, 1>{});
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();                    // tile kt+1 landed for everyone; everyone holds tile kt in registers
-                const TileSrc t = issue_begin(kt + 3, st);
+                const TileSrc t = issue_begin(kt + 3, st, cur);
+                cur = t.next;
                 block(fc_, fn_, st1, true, t, std::true_type{}, w3_tag);
-            } else if (kt + 1 < nk) {
-                if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                block(fc_, fn_, st1, true, tnone, std::false_type{}, w3_tag);
-            } else {
-                block(fc_, fn_, st1, false, tnone, std::false_type{}, w3_tag);
+            } else {                          // the last three k-tiles: ONE copy of the MFMA block (the accumulators stay in place)
+                const bool more = kt + 1 < nk;
+                if (more) {
+                    if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                }
+                block(fc_, fn_, st1, more, tnone, std::false_type{}, w3_tag);
             }
             st = st1; ++kt;
         };

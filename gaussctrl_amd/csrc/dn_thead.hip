@@ -113,9 +113,12 @@ __global__ __launch_bounds__(256, 1) void k_thead(const HeadArgs a)
         unsigned short *r = p + (row0 + wid * 32 + (l & 31)) * ld + 8 * (l >> 5);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const unsigned s0 = up ? src[ks].x : src[ks].z, s1 = up ? src[ks].y : src[ks].w;      // what the partner is missing
+            // (the fragment is read ONCE, as a value: `up ? src[ks].x : src[ks].z` becomes one load through a lane-selected address, and an
+            // array with one such access stays in private memory -- 240 bytes and 570 scratch accesses in this kernel)
+            const uint4 v = src[ks];
+            const unsigned s0 = up ? v.x : v.z, s1 = up ? v.y : v.w;      // what the partner is missing
             const unsigned r0 = __shfl_xor(s0, 32, 64), r1 = __shfl_xor(s1, 32, 64);
-            *reinterpret_cast<uint4 *>(r + 16 * ks) = up ? make_uint4(r0, r1, src[ks].z, src[ks].w) : make_uint4(src[ks].x, src[ks].y, r0, r1);
+            *reinterpret_cast<uint4 *>(r + 16 * ks) = up ? make_uint4(r0, r1, v.z, v.w) : make_uint4(v.x, v.y, r0, r1);
         }
     };
     // the residual stream h goes to the tail kernel only: stored as the fragments themselves ([32-row block][k-step][lane][16 bytes]),
