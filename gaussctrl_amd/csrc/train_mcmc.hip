@@ -14,18 +14,14 @@
 //                         HBM-bound), the gate g and exp(2 s) in float32 as the header states them.
 // update runs before copy, so a copy is the updated row bit for bit and D (up to 51 terms) is formed once per source, not once per draw.
 // Sampled rows and destination rows are disjoint by the caller's contract, so no launch reads what it writes in another lane.
-// Built with the STRICT flags (no contraction).
-#include "common.h"
+#include "train_rows.h"
 #include "../../include/gaussctrl_mcmc.h"
 
 namespace {
 
-constexpr int BLK = 256;                  // Gaussians (or draws) per workgroup, one per lane
-constexpr int MAX_REST = 45;              // floats of features_rest per Gaussian at sh_degree 3
 constexpr int MAX_RATIO = 51;             // r = min(mult + 1, 51)
 constexpr double MAX_OPACITY = 1.0 - 0x1p-23;
 
-__device__ __forceinline__ int lanes_below(uint64_t mask) { return __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1ull)); }
 __device__ __forceinline__ double sigmoid64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
 
 // ---------------------------------------------------------------------------------------------------------------- dead rows
@@ -50,67 +46,31 @@ __global__ __launch_bounds__(256) void k_mcmc_dead_flag(int64_t N, const float *
 // One workgroup: block_sums [nblk] -> exclusive offsets in place, counts = {n_dead, N - n_dead}.
 __global__ __launch_bounds__(256) void k_mcmc_dead_scan(int64_t N, int64_t nblk, int32_t *__restrict__ block_sums, int32_t *__restrict__ counts)
 {
-    __shared__ int32_t wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int32_t carry = 0;
-    for (int64_t base = 0; base < nblk; base += 256) {
-        const int64_t j = base + tid;
-        const int32_t v = j < nblk ? block_sums[j] : 0;
-        int32_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int32_t before = 0;
-        for (int k = 0; k < w; ++k) before += wsum[k];
-        const int32_t all = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        if (j < nblk) block_sums[j] = carry + before + inc - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) { counts[0] = carry; counts[1] = (int32_t)(N - carry); }
+    const int32_t n_dead = scan_counts(block_sums, nblk, true);
+    if (threadIdx.x == 0) { counts[0] = n_dead; counts[1] = (int32_t)(N - n_dead); }
 }
 
 __global__ __launch_bounds__(256) void k_mcmc_dead_compact(int64_t N, const float *__restrict__ weights, const int32_t *__restrict__ block_offs,
                                                            int32_t *__restrict__ dead_idx)
 {
     __shared__ int32_t wcnt[4];
-    const int tid = threadIdx.x, w = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * BLK + tid;
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const bool dead = i < N && weights[i] == 0.f;      // weight 0 and dead are the same fact (min_opacity >= 0)
     const uint64_t b = __ballot(dead);
-    if ((tid & 63) == 0) wcnt[w] = __popcll(b);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(b);
     __syncthreads();
     if (!dead) return;
-    int32_t r = block_offs[blockIdx.x] + lanes_below(b);
-    for (int k = 0; k < w; ++k) r += wcnt[k];
+    const int32_t r = ballot_rank(block_offs[blockIdx.x], b, wcnt);
     if (r >= 0 && r < N) dead_idx[r] = (int32_t)i;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- relocate / grow
-// the six tensors in the order means, scales, quats, opacities, features_dc, features_rest; [0] parameters, [1] exp_avg, [2] exp_avg_sq
-struct Rows { float *t[3][6]; };
-
 __global__ __launch_bounds__(256) void k_mcmc_count(int64_t N, int64_t n, const int32_t *__restrict__ sampled, int32_t *__restrict__ mult)
 {
     const int64_t j = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (j >= n) return;
     const int32_t s = sampled[j];
     if (s >= 0 && s < N) atomicAdd(&mult[s], 1);
-}
-
-template <int W>
-__device__ __forceinline__ void zero_row(float *__restrict__ dst, int64_t row)
-{
-    if (!dst) return;
-#pragma unroll
-    for (int c = 0; c < W; ++c) dst[row * W + c] = 0.f;
-}
-template <int W>
-__device__ __forceinline__ void copy_row(float *__restrict__ t, int64_t from, int64_t to)
-{
-#pragma unroll
-    for (int c = 0; c < W; ++c) t[to * W + c] = t[from * W + c];
 }
 
 template <int R>
@@ -138,10 +98,7 @@ __global__ __launch_bounds__(256) void k_mcmc_update(int64_t N, const int32_t *_
         for (int a = 0; a < 3; ++a) ls[3 * i + a] = (float)((double)ls[3 * i + a] + inc);
         const double oc = fmin(fmax(o_new, (double)min_opacity), MAX_OPACITY);
         t.t[0][3][i] = (float)(log(oc) - log1p(-oc));
-#pragma unroll
-        for (int q = 1; q < 3; ++q) {
-            zero_row<3>(t.t[q][0], i); zero_row<3>(t.t[q][1], i); zero_row<4>(t.t[q][2], i); zero_row<1>(t.t[q][3], i); zero_row<3>(t.t[q][4], i);
-        }
+        zero_narrow_moments(t, i);
     }
     if constexpr (R > 0) {
         hit[tid] = m > 0;
@@ -171,12 +128,8 @@ __global__ __launch_bounds__(256) void k_mcmc_copy(int64_t N, int64_t n, int64_t
         if (s0 >= 0 && s0 < N && d0 >= 0 && d0 < n_rows) { s = s0; d = (int32_t)d0; }      // an index out of range: the entry is skipped
     }
     if (s >= 0) {
-        copy_row<3>(t.t[0][0], s, d); copy_row<3>(t.t[0][1], s, d); copy_row<4>(t.t[0][2], s, d); copy_row<1>(t.t[0][3], s, d);
-        copy_row<3>(t.t[0][4], s, d);
-#pragma unroll
-        for (int q = 1; q < 3; ++q) {
-            zero_row<3>(t.t[q][0], d); zero_row<3>(t.t[q][1], d); zero_row<4>(t.t[q][2], d); zero_row<1>(t.t[q][3], d); zero_row<3>(t.t[q][4], d);
-        }
+        copy_narrow(t, s, d);
+        zero_narrow_moments(t, d);
     }
     if constexpr (R > 0) {
         ssrc[tid] = s; sdst[tid] = d;
@@ -209,22 +162,15 @@ __global__ __launch_bounds__(256) void k_mcmc_inject_noise(int64_t N, float *__r
     const float4 qf = reinterpret_cast<const float4 *>(quats)[i];
     const float e0 = expf(2.f * log_scales[3 * i]), e1 = expf(2.f * log_scales[3 * i + 1]), e2 = expf(2.f * log_scales[3 * i + 2]);
     const double n0 = noise[3 * i], n1 = noise[3 * i + 1], n2 = noise[3 * i + 2];
-    const double qw = qf.x, qx = qf.y, qy = qf.z, qz = qf.w;
-    const double inv = 1.0 / sqrt((qw * qw + qx * qx) + (qy * qy + qz * qz));
-    const double w = qw * inv, x = qx * inv, y = qy * inv, z = qz * inv;
-    const double R00 = 1.0 - 2.0 * (y * y + z * z), R01 = 2.0 * (x * y - w * z), R02 = 2.0 * (x * z + w * y);
-    const double R10 = 2.0 * (x * y + w * z), R11 = 1.0 - 2.0 * (x * x + z * z), R12 = 2.0 * (y * z - w * x);
-    const double R20 = 2.0 * (x * z - w * y), R21 = 2.0 * (y * z + w * x), R22 = 1.0 - 2.0 * (x * x + y * y);
     // R^T n, scaled by exp(2 s), then R v: the covariance never exists as a matrix
-    const double v0 = (double)e0 * ((R00 * n0 + R10 * n1) + R20 * n2), v1 = (double)e1 * ((R01 * n0 + R11 * n1) + R21 * n2),
-                 v2 = (double)e2 * ((R02 * n0 + R12 * n1) + R22 * n2);
+    const Rot64 rot(qf.x, qf.y, qf.z, qf.w);
+    const Vec64 u = rot.mul_t(n0, n1, n2);
+    const Vec64 d = rot.mul((double)e0 * u.x, (double)e1 * u.y, (double)e2 * u.z);
     const double k = (double)gs;
-    means[3 * i] = (float)((double)means[3 * i] + ((R00 * v0 + R01 * v1) + R02 * v2) * k);
-    means[3 * i + 1] = (float)((double)means[3 * i + 1] + ((R10 * v0 + R11 * v1) + R12 * v2) * k);
-    means[3 * i + 2] = (float)((double)means[3 * i + 2] + ((R20 * v0 + R21 * v1) + R22 * v2) * k);
+    means[3 * i] = (float)((double)means[3 * i] + d.x * k);
+    means[3 * i + 1] = (float)((double)means[3 * i + 1] + d.y * k);
+    means[3 * i + 2] = (float)((double)means[3 * i + 2] + d.z * k);
 }
-
-inline bool fits_i32(int64_t elements) { return elements < (1ll << 31); }
 
 }  // namespace
 
@@ -263,27 +209,14 @@ int gc_mcmc_relocate(int64_t N, int64_t n, int rest_floats, const int32_t *sampl
     if (N == 0 || n == 0) return GC_OK;
     GC_REQUIRE(sampled_idx && mult && params, "null argument");
     Rows t;
-    for (int k = 0; k < 6; ++k) {
-        const bool used = k < 5 || rest_floats > 0;
-        GC_REQUIRE(!used || params[k], "null parameter tensor");
-        t.t[0][k] = used ? params[k] : nullptr;
-        t.t[1][k] = used && exp_avg ? exp_avg[k] : nullptr;
-        t.t[2][k] = used && exp_avg_sq ? exp_avg_sq[k] : nullptr;
-    }
+    GC_REQUIRE(fill_rows(t, rest_floats, params, exp_avg, exp_avg_sq), "null parameter tensor");
     hipStream_t s = gc::S(stream);
     if (hipMemsetAsync(mult, 0, sizeof(int32_t) * (size_t)N, s) != hipSuccess) return gc::check_launch("gc_mcmc_relocate");
     hipLaunchKernelGGL(k_mcmc_count, dim3(gc::cdiv(n, BLK)), dim3(BLK), 0, s, N, n, sampled_idx, mult);
-    const dim3 gsrc(gc::cdiv(N, BLK)), gdst(gc::cdiv(n, BLK)), block(BLK);
-#define GC_MCMC_RELOCATE(R)                                                                                         \
-    hipLaunchKernelGGL(k_mcmc_update<R>, gsrc, block, 0, s, N, (const int32_t *)mult, min_opacity, t);              \
-    hipLaunchKernelGGL(k_mcmc_copy<R>, gdst, block, 0, s, N, n, n_rows, sampled_idx, dest_idx, t)
-    switch (rest_floats) {
-    case 0: GC_MCMC_RELOCATE(0); break;
-    case 9: GC_MCMC_RELOCATE(9); break;
-    case 24: GC_MCMC_RELOCATE(24); break;
-    default: GC_MCMC_RELOCATE(45); break;
-    }
-#undef GC_MCMC_RELOCATE
+    with_rest_floats(rest_floats, [&](auto R) {
+        hipLaunchKernelGGL(k_mcmc_update<decltype(R)::value>, dim3(gc::cdiv(N, BLK)), dim3(BLK), 0, s, N, (const int32_t *)mult, min_opacity, t);
+        hipLaunchKernelGGL(k_mcmc_copy<decltype(R)::value>, dim3(gc::cdiv(n, BLK)), dim3(BLK), 0, s, N, n, n_rows, sampled_idx, dest_idx, t);
+    });
     return gc::check_launch("gc_mcmc_relocate");
 }
 

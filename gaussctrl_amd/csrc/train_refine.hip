@@ -15,13 +15,11 @@
 //   k_refine_reset_opacity  opacities = min(opacities, reset_logit), both moments zero.
 // All HBM-bound: apply moves 59 x 4 x 3 = 708 B in and 708 B out per surviving Gaussian.  Built with the STRICT flags (no contraction):
 // the decisions compare float expressions with thresholds, and the expressions are the ones written here.
-#include "common.h"
+#include "train_rows.h"
 #include "../../include/gaussctrl_refine.h"
 
 namespace {
 
-constexpr int BLK = 256;                  // Gaussians per workgroup, one per lane
-constexpr int MAX_REST = 45;              // floats of features_rest per Gaussian at sh_degree 3
 constexpr float LOG_SIZE_FAC = 0.4700036292457356f;      // log(1.6): a split child's scales are the source's - log(1.6)
 
 __global__ __launch_bounds__(256) void k_refine_accumulate(int64_t N, int C, const float *__restrict__ xys_grad, const int32_t *__restrict__ radii,
@@ -49,8 +47,6 @@ struct PlanArgs {
     int densify, n_split, split_by_screen, cull_by_scale, cull_by_screen;
     float max_dim, densify_grad_thresh, densify_size_thresh, split_screen_size, cull_alpha_thresh, cull_scale_thresh, cull_screen_size;
 };
-
-__device__ __forceinline__ int lanes_below(uint64_t mask) { return __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1ull)); }
 
 // per-workgroup counts: block_sums [4][nblk] = survivors, emitting split sources, emitting duplicate sources, rows below the alpha threshold
 __global__ __launch_bounds__(256) void k_refine_decide(int64_t N, int64_t nblk, const float *__restrict__ log_scales, const float *__restrict__ op_logit,
@@ -108,33 +104,12 @@ __global__ __launch_bounds__(256) void k_refine_decide(int64_t N, int64_t nblk, 
 // n_split_src, n_dup_src, n_out, n_below_alpha}.
 __global__ __launch_bounds__(256) void k_refine_scan_blocks(int64_t nblk, int n_split, int32_t *__restrict__ block_sums, int32_t *__restrict__ counts)
 {
-    __shared__ int32_t wsum[4];
-    __shared__ int32_t total[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (int q = 0; q < 4; ++q) {
-        int32_t carry = 0;
-        for (int64_t base = 0; base < nblk; base += 256) {
-            const int64_t j = base + tid;
-            const int32_t v = j < nblk ? block_sums[q * nblk + j] : 0;
-            int32_t inc = v;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-            if (lane == 63) wsum[w] = inc;
-            __syncthreads();
-            int32_t before = 0;
-            for (int k = 0; k < w; ++k) before += wsum[k];
-            const int32_t all = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-            if (j < nblk && q < 3) block_sums[q * nblk + j] = carry + before + inc - v;
-            carry += all;
-            __syncthreads();
-        }
-        if (tid == 0) total[q] = carry;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        counts[0] = total[0]; counts[1] = total[1]; counts[2] = total[2];
-        counts[3] = total[0] + n_split * total[1] + total[2];
-        counts[4] = total[3];
+    const int32_t n_surv = scan_counts(block_sums, nblk, true), n_split_src = scan_counts(block_sums + nblk, nblk, true),
+                  n_dup_src = scan_counts(block_sums + 2 * nblk, nblk, true), n_below = scan_counts(block_sums + 3 * nblk, nblk, false);
+    if (threadIdx.x == 0) {
+        counts[0] = n_surv; counts[1] = n_split_src; counts[2] = n_dup_src;
+        counts[3] = n_surv + n_split * n_split_src + n_dup_src;
+        counts[4] = n_below;
     }
 }
 
@@ -143,50 +118,19 @@ __global__ __launch_bounds__(256) void k_refine_ranks(int64_t N, int64_t nblk, c
                                                       int32_t *__restrict__ ranks)
 {
     __shared__ int32_t wcnt[3][4];
-    const int tid = threadIdx.x, w = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * BLK + tid;
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const uint32_t act = i < N ? action[i] : 0u;
     const uint64_t b0 = __ballot((act & GC_REFINE_KEEP) != 0), b1 = __ballot((act & GC_REFINE_EMIT_SPLIT) != 0), b2 = __ballot((act & GC_REFINE_EMIT_DUP) != 0);
-    if ((tid & 63) == 0) { wcnt[0][w] = __popcll(b0); wcnt[1][w] = __popcll(b1); wcnt[2][w] = __popcll(b2); }
+    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; wcnt[0][w] = __popcll(b0); wcnt[1][w] = __popcll(b1); wcnt[2][w] = __popcll(b2); }
     __syncthreads();
     if (i >= N) return;
-    int32_t r0 = block_offs[blockIdx.x] + lanes_below(b0), r1 = block_offs[nblk + blockIdx.x] + lanes_below(b1),
-            r2 = block_offs[2 * nblk + blockIdx.x] + lanes_below(b2);
-    for (int k = 0; k < w; ++k) { r0 += wcnt[0][k]; r1 += wcnt[1][k]; r2 += wcnt[2][k]; }
-    ranks[i] = r0; ranks[N + i] = r1; ranks[2 * N + i] = r2;
+    ranks[i] = ballot_rank(block_offs[blockIdx.x], b0, wcnt[0]);
+    ranks[N + i] = ballot_rank(block_offs[nblk + blockIdx.x], b1, wcnt[1]);
+    ranks[2 * N + i] = ballot_rank(block_offs[2 * nblk + blockIdx.x], b2, wcnt[2]);
 }
 
-// the six tensors in the order means, scales, quats, opacities, features_dc, features_rest; [0] parameters, [1] exp_avg, [2] exp_avg_sq
-struct Scene { const float *t[3][6]; };
-struct SceneOut { float *t[3][6]; };
-
-template <int W>
-__device__ __forceinline__ void load_row(const float *__restrict__ src, int64_t i, float (&v)[W])
-{
-#pragma unroll
-    for (int c = 0; c < W; ++c) v[c] = src[i * W + c];
-}
-template <int W>
-__device__ __forceinline__ void store_row(float *__restrict__ dst, int64_t row, const float (&v)[W])
-{
-#pragma unroll
-    for (int c = 0; c < W; ++c) dst[row * W + c] = v[c];
-}
-
-// a moment tensor of one of the five narrow tensors: the survivor's row is copied, every child row (bit j of cmask: crow[j]) is zero
-template <int W>
-__device__ __forceinline__ void move_moment(const float *__restrict__ src, float *__restrict__ dst, int64_t i, bool keep, int row,
-                                            uint32_t cmask, const int (&crow)[5])
-{
-    if (!src || !dst) return;
-    if (keep) { float v[W]; load_row<W>(src, i, v); store_row<W>(dst, row, v); }
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-        if (cmask >> j & 1u) {
-#pragma unroll
-            for (int c = 0; c < W; ++c) dst[(int64_t)crow[j] * W + c] = 0.f;
-        }
-}
+// output rows of one source Gaussian's children: [k] the k-th split child, [4] the duplicate; bit j of mask: emitted
+struct Children { int row[5]; uint32_t mask; };
 
 // one contiguous span of output rows of features_rest (or of one of its moments): row r of the span is source row list[r] of the LDS block
 template <int R>
@@ -206,7 +150,7 @@ __device__ __forceinline__ void write_span(float *__restrict__ dst, int64_t firs
 template <int R>
 __global__ __launch_bounds__(256) void k_refine_apply(int64_t N, int n_split, int64_t n_surv, int64_t n_split_src, int64_t n_out,
                                                       const uint32_t *__restrict__ action, const int32_t *__restrict__ ranks,
-                                                      const float *__restrict__ samples, Scene in, SceneOut out)
+                                                      const float *__restrict__ samples, ConstRows in, Rows out)
 {
     __shared__ __attribute__((aligned(16))) float srest[R > 0 ? BLK * R : 4];
     __shared__ uint16_t list[3][BLK];
@@ -216,8 +160,7 @@ __global__ __launch_bounds__(256) void k_refine_apply(int64_t N, int n_split, in
     const int nhere = (int)(N - i0 < BLK ? N - i0 : BLK);
     const int64_t dup_base = n_surv + (int64_t)n_split * n_split_src;
     uint32_t act = 0;
-    int crow[5] = {0, 0, 0, 0, 0};       // output rows of the children: [k] the k-th split child, [4] the duplicate; bit j of cmask: emitted
-    uint32_t cmask = 0;
+    Children ch = {{0, 0, 0, 0, 0}, 0};
     int row = 0;
     bool keep = false;
     if (i < N) {
@@ -228,53 +171,37 @@ __global__ __launch_bounds__(256) void k_refine_apply(int64_t N, int n_split, in
 #pragma unroll
         for (int k = 0; k < GC_REFINE_MAX_SPLIT; ++k) {
             const int64_t r = n_surv + (int64_t)k * n_split_src + r1;
-            if ((act & GC_REFINE_EMIT_SPLIT) && k < n_split && r1 < n_split_src && r < n_out) { crow[k] = (int)r; cmask |= 1u << k; }
+            if ((act & GC_REFINE_EMIT_SPLIT) && k < n_split && r1 < n_split_src && r < n_out) { ch.row[k] = (int)r; ch.mask |= 1u << k; }
         }
-        if ((act & GC_REFINE_EMIT_DUP) && dup_base + r2 < n_out) { crow[4] = (int)(dup_base + r2); cmask |= 16u; }
+        if ((act & GC_REFINE_EMIT_DUP) && dup_base + r2 < n_out) { ch.row[4] = (int)(dup_base + r2); ch.mask |= 16u; }
         // ---- the five narrow tensors, per lane
-        float mean[3], ls[3], q[4], op[1], dc[3];
-        load_row<3>(in.t[0][0], i, mean); load_row<3>(in.t[0][1], i, ls); load_row<4>(in.t[0][2], i, q);
-        load_row<1>(in.t[0][3], i, op); load_row<3>(in.t[0][4], i, dc);
-        if (keep) {
-            store_row<3>(out.t[0][0], row, mean); store_row<3>(out.t[0][1], row, ls); store_row<4>(out.t[0][2], row, q);
-            store_row<1>(out.t[0][3], row, op); store_row<3>(out.t[0][4], row, dc);
-        }
-        if (cmask & 15u) {
+        const Narrow src = load_narrow(in, 0, i);
+        if (keep) store_narrow(out, 0, row, src);
+        if (ch.mask & 15u) {
             // child k: mean + Rot(q / |q|) (exp(scales) * z_k), scales - log 1.6, the rest unchanged.  The offset is formed in double and
             // rounded once: a few dozen operations on the ~5 % of lanes that split, invisible next to the 1.4 KB the lane moves.
-            const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-            const double inv = 1.0 / sqrt((qw * qw + qx * qx) + (qy * qy + qz * qz));
-            const double w = qw * inv, x = qx * inv, y = qy * inv, z = qz * inv;
-            const double e0 = exp((double)ls[0]), e1 = exp((double)ls[1]), e2 = exp((double)ls[2]);
-            const double R00 = 1.0 - 2.0 * (y * y + z * z), R01 = 2.0 * (x * y - w * z), R02 = 2.0 * (x * z + w * y);
-            const double R10 = 2.0 * (x * y + w * z), R11 = 1.0 - 2.0 * (x * x + z * z), R12 = 2.0 * (y * z - w * x);
-            const double R20 = 2.0 * (x * z - w * y), R21 = 2.0 * (y * z + w * x), R22 = 1.0 - 2.0 * (x * x + y * y);
-            const float cls[3] = {ls[0] - LOG_SIZE_FAC, ls[1] - LOG_SIZE_FAC, ls[2] - LOG_SIZE_FAC};
+            const Rot64 rot(src.v[QUAT_AT], src.v[QUAT_AT + 1], src.v[QUAT_AT + 2], src.v[QUAT_AT + 3]);
+            const double e0 = exp((double)src.v[SCALE_AT]), e1 = exp((double)src.v[SCALE_AT + 1]), e2 = exp((double)src.v[SCALE_AT + 2]);
+            Narrow child = src;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) child.v[SCALE_AT + a] = src.v[SCALE_AT + a] - LOG_SIZE_FAC;
 #pragma unroll
             for (int k = 0; k < GC_REFINE_MAX_SPLIT; ++k) {
-                if (!(cmask >> k & 1u)) continue;
-                const int64_t r = crow[k], srow = r - n_surv;              // samples row = k * n_split_src + split rank
-                const double v0 = e0 * (double)samples[3 * srow], v1 = e1 * (double)samples[3 * srow + 1], v2 = e2 * (double)samples[3 * srow + 2];
-                const float cm[3] = {(float)((double)mean[0] + ((R00 * v0 + R01 * v1) + R02 * v2)),
-                                     (float)((double)mean[1] + ((R10 * v0 + R11 * v1) + R12 * v2)),
-                                     (float)((double)mean[2] + ((R20 * v0 + R21 * v1) + R22 * v2))};
-                store_row<3>(out.t[0][0], r, cm); store_row<3>(out.t[0][1], r, cls); store_row<4>(out.t[0][2], r, q);
-                store_row<1>(out.t[0][3], r, op); store_row<3>(out.t[0][4], r, dc);
+                if (!(ch.mask >> k & 1u)) continue;
+                const int64_t r = ch.row[k], srow = r - n_surv;            // samples row = k * n_split_src + split rank
+                const Vec64 d = rot.mul(e0 * (double)samples[3 * srow], e1 * (double)samples[3 * srow + 1], e2 * (double)samples[3 * srow + 2]);
+                child.v[MEAN_AT] = (float)((double)src.v[MEAN_AT] + d.x);
+                child.v[MEAN_AT + 1] = (float)((double)src.v[MEAN_AT + 1] + d.y);
+                child.v[MEAN_AT + 2] = (float)((double)src.v[MEAN_AT + 2] + d.z);
+                store_narrow(out, 0, r, child);
             }
         }
-        if (cmask & 16u) {
-            const int64_t r = crow[4];
-            store_row<3>(out.t[0][0], r, mean); store_row<3>(out.t[0][1], r, ls); store_row<4>(out.t[0][2], r, q);
-            store_row<1>(out.t[0][3], r, op); store_row<3>(out.t[0][4], r, dc);
-        }
+        if (ch.mask & 16u) store_narrow(out, 0, ch.row[4], src);
+        // the moments of the narrow tensors: the survivor's rows are copied, every child row is zero
+        if (keep) { store_narrow(out, 1, row, load_narrow(in, 1, i)); store_narrow(out, 2, row, load_narrow(in, 2, i)); }
 #pragma unroll
-        for (int m = 1; m < 3; ++m) {
-            move_moment<3>(in.t[m][0], out.t[m][0], i, keep, row, cmask, crow);
-            move_moment<3>(in.t[m][1], out.t[m][1], i, keep, row, cmask, crow);
-            move_moment<4>(in.t[m][2], out.t[m][2], i, keep, row, cmask, crow);
-            move_moment<1>(in.t[m][3], out.t[m][3], i, keep, row, cmask, crow);
-            move_moment<3>(in.t[m][4], out.t[m][4], i, keep, row, cmask, crow);
-        }
+        for (int j = 0; j < 5; ++j)
+            if (ch.mask >> j & 1u) zero_narrow_moments(out, ch.row[j]);
         // ---- features_rest: this workgroup's members of each output span, in index order
         if (R > 0) {
             const int32_t f0 = ranks[i0], f1 = ranks[N + i0], f2 = ranks[2 * N + i0];       // ranks of the workgroup's first Gaussian
@@ -317,8 +244,6 @@ __global__ __launch_bounds__(256) void k_refine_reset_opacity(int64_t N, float r
     if (m) m[i] = 0.f;
     if (v) v[i] = 0.f;
 }
-
-inline bool fits_i32(int64_t elements) { return elements < (1ll << 31); }
 
 }  // namespace
 
@@ -382,28 +307,17 @@ int gc_refine_apply(int64_t N, int n_split_samples, int rest_floats, int64_t n_s
     if (N == 0 || n_out == 0) return GC_OK;
     GC_REQUIRE(action && ranks && params && out_params, "null argument");
     GC_REQUIRE(n_split_src == 0 || samples, "split children need samples");
-    Scene in;
-    SceneOut out;
-    for (int t = 0; t < 6; ++t) {
-        const bool used = t < 5 || rest_floats > 0;
-        GC_REQUIRE(!used || (params[t] && out_params[t]), "null parameter tensor");
-        in.t[0][t] = params[t]; out.t[0][t] = out_params[t];
-        const float *m = exp_avg ? exp_avg[t] : nullptr, *v = exp_avg_sq ? exp_avg_sq[t] : nullptr;
-        float *om = out_exp_avg ? out_exp_avg[t] : nullptr, *ov = out_exp_avg_sq ? out_exp_avg_sq[t] : nullptr;
-        GC_REQUIRE((m != nullptr) == (om != nullptr) && (v != nullptr) == (ov != nullptr), "a moment needs both its input and its output");
-        in.t[1][t] = m; out.t[1][t] = om; in.t[2][t] = v; out.t[2][t] = ov;
-    }
-    hipStream_t s = gc::S(stream);
-    const dim3 grid(gc::cdiv(N, BLK)), block(BLK);
-#define GC_REFINE_APPLY(R)                                                                                                             \
-    hipLaunchKernelGGL(k_refine_apply<R>, grid, block, 0, s, N, n_split_samples, n_survivors, n_split_src, n_out, action, ranks, samples, in, out)
-    switch (rest_floats) {
-    case 0: GC_REFINE_APPLY(0); break;
-    case 9: GC_REFINE_APPLY(9); break;
-    case 24: GC_REFINE_APPLY(24); break;
-    default: GC_REFINE_APPLY(45); break;
-    }
-#undef GC_REFINE_APPLY
+    ConstRows in;
+    Rows out;
+    GC_REQUIRE(fill_rows(in, rest_floats, params, exp_avg, exp_avg_sq) && fill_rows(out, rest_floats, out_params, out_exp_avg, out_exp_avg_sq),
+               "null parameter tensor");
+    for (int t = 0; t < 6; ++t)
+        GC_REQUIRE((in.t[1][t] != nullptr) == (out.t[1][t] != nullptr) && (in.t[2][t] != nullptr) == (out.t[2][t] != nullptr),
+                   "a moment needs both its input and its output");
+    with_rest_floats(rest_floats, [&](auto R) {
+        hipLaunchKernelGGL(k_refine_apply<decltype(R)::value>, dim3(gc::cdiv(N, BLK)), dim3(BLK), 0, gc::S(stream), N, n_split_samples,
+                           n_survivors, n_split_src, n_out, action, ranks, samples, in, out);
+    });
     return gc::check_launch("gc_refine_apply");
 }
 

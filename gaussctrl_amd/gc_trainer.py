@@ -206,21 +206,15 @@ class CullCallback(_Callback):
             culls = culls | (torch.exp(m.scales).max(dim=-1).values > c.cull_scale_thresh)
         if not bool(culls.any()):
             return
+        from .scene_rows import MOMENTS, swap_rows
         keep = ~culls
-        m._cull_keep = keep              # train_mode "sharded" prunes its optimizer-state slices with the same mask (GaussCtrlPipeline._sharded_adam)
         self.n_culled += int(culls.sum())
-        groups = m.get_param_groups()
-        for gname, params in groups.items():
+        for gname, params in m.get_param_groups().items():      # parameter by parameter: each old tensor goes before the next is pruned
             opt = self.optimizers.get(gname)
             for p in params:
-                st = opt.state.pop(p, None) if opt is not None else None
-                p.data = p.data[keep].contiguous()
-                p.grad = None
-                if st:
-                    for k in ("exp_avg", "exp_avg_sq"):
-                        if k in st:
-                            st[k] = st[k][keep].contiguous()
-                    opt.state[p] = st
+                st = opt.state.get(p) if opt is not None else None
+                swap_rows(m, [(opt, p, st)], [p.data[keep].contiguous()],          # whichever of the moments exist are pruned
+                          [{k: st[k][keep].contiguous() for k in MOMENTS if k in st} if st else None], keep)
 
 
 class RefineCallback(_Callback):

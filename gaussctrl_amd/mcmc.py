@@ -7,7 +7,7 @@ header states them and is the contract.
   relocate(model, optimizers, sampled)   : dead Gaussians (sigmoid(opacity) <= mcmc_min_opacity) become copies of live ones drawn with
                                            probability proportional to their opacity; no tensor changes size or storage;
   add_new(model, optimizers, sampled)    : grow by 5 % towards mcmc_cap_max with copies drawn the same way (new tensors, optimizer state
-                                           re-keyed as refine.RefineState._rebuild does);
+                                           re-keyed by scene_rows.swap_rows);
   inject_noise(model, lr, noise)         : after every optimizer step, means += Cov noise * g(opacity) * lr * mcmc_noise_lr in ONE launch.
 
 A relocation is  gc_mcmc_dead -> an 8-byte read-back of {n_dead, n_alive} (its only synchronisation) -> torch.multinomial on the device ->
@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from .refine import NAMES, _optimizer_of, _ptr_array
+from .scene_rows import check_params, leaf_states, moment_ptrs, new_rows, ptr_array, rest_floats, swap_rows
 
 MAX_CATEGORIES = 1 << 24          # torch.multinomial takes fewer categories than this
 
@@ -34,15 +34,8 @@ def schedule(config, step: int) -> bool:
 def _check_model(model, what: str) -> int:
     if not model.means.is_cuda:
         raise L.GaussCtrlHipError(f"mcmc.{what} needs GPU parameters (HIP path only; no CPU fallback)")
-    for n in NAMES:
-        t = getattr(model, n).data
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise L.GaussCtrlHipError(f"mcmc.{what} needs contiguous float32 parameters")
+    check_params(model, f"mcmc.{what}")
     return int(model.means.shape[0])
-
-
-def _rest_floats(model) -> int:
-    return int(model.features_rest[0].numel()) if model.features_rest.shape[0] > 0 else 0
 
 
 def dead_rows(opacities: torch.Tensor, min_opacity: float):
@@ -79,27 +72,11 @@ def _draw(weights: torch.Tensor, n: int, sampled: Optional[torch.Tensor], what: 
     return idx.to(torch.int32).contiguous()
 
 
-def _moments(model, optimizers):
-    """per tensor of NAMES: (optimizer | None, parameter, state dict with both moments | None)"""
-    owners = _optimizer_of(model, optimizers)
-    out = []
-    for n in NAMES:
-        opt, p = owners.get(n, (None, getattr(model, n)))
-        st = opt.state.get(p) if opt is not None else None
-        st = st if st and "exp_avg" in st and "exp_avg_sq" in st else None
-        if st is not None:
-            for key in ("exp_avg", "exp_avg_sq"):
-                t = st[key]
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != p.shape:
-                    raise L.GaussCtrlHipError("mcmc needs contiguous float32 Adam moments shaped like their parameter")
-        out.append((opt, p, st))
-    return out
-
-
-def _relocate_call(N, n, rest, sampled, dest, min_opacity, params, m, v):
+def _relocate_call(N, n, rest, sampled, dest, min_opacity, params, moments):
     mult = torch.empty(N, dtype=torch.int32, device=sampled.device)
     L.check(L.lib().gc_mcmc_relocate(L.i64(N), L.i64(n), L.i32(rest), L.ptr(sampled), L.ptr(dest), L.f32(min_opacity), L.ptr(mult),
-                                     _ptr_array(params), _ptr_array(m), _ptr_array(v), L.stream_ptr()), "gc_mcmc_relocate")
+                                     ptr_array(params), moment_ptrs(moments, "exp_avg"), moment_ptrs(moments, "exp_avg_sq"), L.stream_ptr()),
+            "gc_mcmc_relocate")
     return mult
 
 
@@ -119,9 +96,9 @@ def relocate(model, optimizers, sampled: Optional[torch.Tensor] = None) -> int:
     if n_dead == 0 or n_alive == 0:
         return 0
     src = _draw(weights, n_dead, sampled, "relocate")
-    states = _moments(model, optimizers)
-    _relocate_call(N, n_dead, _rest_floats(model), src, dead_idx[:n_dead], float(c.mcmc_min_opacity), [p.data for _, p, _ in states],
-                   [st["exp_avg"] if st else None for _, _, st in states], [st["exp_avg_sq"] if st else None for _, _, st in states])
+    states = leaf_states(model, optimizers, "mcmc.relocate", params_checked=True)
+    _relocate_call(N, n_dead, rest_floats(model), src, dead_idx[:n_dead], float(c.mcmc_min_opacity), [p.data for _, p, _ in states],
+                   [st for _, _, st in states])
     for _, p, _ in states:
         p.grad = None
     return n_dead
@@ -145,26 +122,10 @@ def add_new(model, optimizers, sampled: Optional[torch.Tensor] = None) -> int:
     if n_alive == 0:
         return 0
     src = _draw(weights, n_new, sampled, "add_new")
-    states = _moments(model, optimizers)
-    dev = model.means.device
-
-    def grown(t):
-        out = torch.empty((N + n_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-        out[:N].copy_(t)
-        return out
-
-    params = [grown(p.data) for _, p, _ in states]
-    m = [grown(st["exp_avg"]) if st else None for _, _, st in states]
-    v = [grown(st["exp_avg_sq"]) if st else None for _, _, st in states]
-    _relocate_call(N, n_new, _rest_floats(model), src, None, float(c.mcmc_min_opacity), params, m, v)
-    for k, (opt, p, st) in enumerate(states):
-        full = opt.state.pop(p, None) if opt is not None else None
-        p.data = params[k]
-        p.grad = None
-        if full:                       # (the new tensors replace the old ones under the same nn.Parameter: same key, new moments)
-            if st is not None:
-                full["exp_avg"], full["exp_avg_sq"] = m[k], v[k]
-            opt.state[p] = full
+    states = leaf_states(model, optimizers, "mcmc.add_new", params_checked=True)
+    params, moments = new_rows(states, N + n_new, keep_old=True)
+    _relocate_call(N, n_new, rest_floats(model), src, None, float(c.mcmc_min_opacity), params, moments)
+    swap_rows(model, states, params, moments)
     return n_new
 
 

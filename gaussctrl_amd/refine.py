@@ -13,14 +13,13 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from . import _lib as L
+from .scene_rows import NAMES, WIDTHS, leaf_states, moment_ptrs, new_rows, ptr_array, rest_floats, swap_rows      # noqa: F401  (NAMES, WIDTHS: importable from here)
 
-NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")      # the order of the C ABI
-WIDTHS = (3, 3, 4, 1, 3)
 # bits of the per-Gaussian action word (include/gaussctrl_refine.h GC_REFINE_*)
 KEEP, SPLIT, DUP, EMIT_SPLIT, EMIT_DUP, BELOW_ALPHA, TOO_BIG, ON_SCREEN = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -49,21 +48,6 @@ def schedule(config, step: int, num_train_data: int) -> Schedule:
 def reset_logit(cull_alpha_thresh: float) -> float:
     """logit(2 * cull_alpha_thresh) in float32: the value splatfacto clamps the opacities to."""
     return float(torch.logit(torch.tensor(2.0 * cull_alpha_thresh, dtype=torch.float32)))
-
-
-def _ptr_array(tensors):
-    return (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def _optimizer_of(model, optimizers) -> Dict[str, tuple]:
-    """parameter name -> (optimizer | None, nn.Parameter) through the model's param groups"""
-    out = {}
-    by_id = {id(getattr(model, n)): n for n in NAMES}
-    for gname, params in model.get_param_groups().items():
-        for p in params:
-            if id(p) in by_id:
-                out[by_id[id(p)]] = ((optimizers or {}).get(gname), p)
-    return out
 
 
 class RefineState:
@@ -139,8 +123,8 @@ class RefineState:
     @torch.no_grad()
     def refine(self, model, optimizers, step: int, num_train_data: int, samples: Optional[torch.Tensor] = None) -> Schedule:
         """What splatfacto's refinement_after does at `step`.  Swaps new tensors into the model's nn.Parameters, re-keys each optimizer's
-        state (state["step"] kept; survivors' moments copied, children's zero), sets model._cull_keep when nothing was added (pure cull), and
-        drops the statistics.  samples: [n_split_samples * n_split_src, 3] standard-normal draws for the split children (default:
+        state (state["step"] kept; survivors' moments copied, children's zero), sets model._cull_keep to the row mask of a pure cull and to None when
+        rows were added (scene_rows.swap_rows), and drops the statistics.  samples: [n_split_samples * n_split_src, 3] standard-normal draws for the split children (default:
         torch.randn on the model's device).  Returns the step's Schedule; self.last holds the counts."""
         sch = schedule(model.config, step, num_train_data)
         if not sch.refine:
@@ -151,9 +135,8 @@ class RefineState:
         if sch.densify or sch.cull_only:
             self._rebuild(model, optimizers, sch, samples)
         if sch.reset:
-            entry = _optimizer_of(model, optimizers).get("opacities", (None, model.opacities))
-            st = entry[0].state.get(entry[1]) if entry[0] is not None else None
-            m, v = (st.get("exp_avg"), st.get("exp_avg_sq")) if st else (None, None)
+            st = leaf_states(model, optimizers, "refine")[NAMES.index("opacities")][2]
+            m, v = (st["exp_avg"], st["exp_avg_sq"]) if st else (None, None)
             L.check(L.lib().gc_refine_reset_opacity(L.i64(model.opacities.numel()), L.f32(reset_logit(model.config.cull_alpha_thresh)),
                                                     L.ptr(model.opacities.data), L.ptr(m), L.ptr(v), L.stream_ptr()), "gc_refine_reset_opacity")
         self.clear()
@@ -164,10 +147,7 @@ class RefineState:
         N = model.means.shape[0]
         dev = model.means.device
         max_dim = float(max(model.last_size)) if model.last_size is not None else 1.0
-        for n in NAMES:
-            t = getattr(model, n).data
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise L.GaussCtrlHipError("refine needs contiguous float32 parameters")
+        states = leaf_states(model, optimizers, "refine")
         action, ranks, (n_surv, n_split_src, n_dup_src, n_out, n_below) = self.plan(model, sch, max_dim)
         self.last = dict(n_in=N, n_out=n_out, n_survivors=n_surv, n_split_src=n_split_src, n_dup_src=n_dup_src, n_below_alpha=n_below)
         if N == 0 or (n_surv == N and n_split_src == 0 and n_dup_src == 0):
@@ -181,35 +161,15 @@ class RefineState:
             samples = samples.to(dev, torch.float32).contiguous()
         else:
             samples = None
-        owners = _optimizer_of(model, optimizers)
-        params, m_in, v_in, p_out, m_out, v_out, states = [], [], [], [], [], [], []
-        for n in NAMES:
-            opt, p = owners.get(n, (None, getattr(model, n)))
-            st = opt.state.get(p) if opt is not None else None
-            st = st if st and "exp_avg" in st and "exp_avg_sq" in st else None
-            new_shape = (n_out,) + tuple(p.shape[1:])
-            params.append(p.data); p_out.append(torch.empty(new_shape, dtype=torch.float32, device=dev))
-            for key, src, dst in (("exp_avg", m_in, m_out), ("exp_avg_sq", v_in, v_out)):
-                t = st[key] if st is not None else None
-                if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != p.shape):
-                    raise L.GaussCtrlHipError("refine needs contiguous float32 Adam moments shaped like their parameter")
-                src.append(t); dst.append(torch.empty(new_shape, dtype=torch.float32, device=dev) if t is not None else None)
-            states.append((opt, p, st))
-        rest = int(model.features_rest[0].numel()) if N > 0 else 0
+        moments = [st for _, _, st in states]
+        p_out, m_out = new_rows(states, n_out)
         L.check(L.lib().gc_refine_apply(
-            L.i64(N), L.i32(ns), L.i32(rest), L.i64(n_surv), L.i64(n_split_src), L.i64(n_dup_src), L.ptr(action), L.ptr(ranks), L.ptr(samples),
-            _ptr_array(params), _ptr_array(m_in), _ptr_array(v_in), _ptr_array(p_out), _ptr_array(m_out), _ptr_array(v_out), L.stream_ptr()),
-            "gc_refine_apply")
-        for k, (opt, p, st) in enumerate(states):
-            full = opt.state.pop(p, None) if opt is not None else None
-            p.data = p_out[k]
-            p.grad = None
-            if full:                       # (the new tensors replace the old ones under the same nn.Parameter: same key, new moments)
-                if st is not None:
-                    full["exp_avg"], full["exp_avg_sq"] = m_out[k], v_out[k]
-                opt.state[p] = full
-        if n_split_src == 0 and n_dup_src == 0:          # pure cull: train_mode "sharded" prunes its optimizer-state slices with the same mask
-            model._cull_keep = (action & KEEP) != 0
+            L.i64(N), L.i32(ns), L.i32(rest_floats(model)), L.i64(n_surv), L.i64(n_split_src), L.i64(n_dup_src), L.ptr(action), L.ptr(ranks),
+            L.ptr(samples), ptr_array([p.data for _, p, _ in states]), moment_ptrs(moments, "exp_avg"), moment_ptrs(moments, "exp_avg_sq"),
+            ptr_array(p_out), moment_ptrs(m_out, "exp_avg"), moment_ptrs(m_out, "exp_avg_sq"), L.stream_ptr()), "gc_refine_apply")
+        # pure cull: train_mode "sharded" prunes its optimizer-state slices with the same mask
+        keep = (action & KEEP) != 0 if n_split_src == 0 and n_dup_src == 0 else None
+        swap_rows(model, states, p_out, m_out, keep)
 
 
 def _state(model) -> RefineState:

@@ -111,3 +111,12 @@ def test_bench_attention_kernel_uses_no_private_memory(kernels):
     hit = {k: v for k, v in kernels.items() if re.search(BENCH_ATTN5, k)}
     assert len(hit) == 2, sorted(hit)
     assert all(v == (0, 0) for v in hit.values()), hit
+
+
+def test_densification_kernels_use_no_private_memory(kernels):
+    """every k_refine_* and k_mcmc_* kernel (csrc/train_refine.hip, train_mcmc.hip on the shared csrc/train_rows.h): no scratch, no spilled
+    VGPRs.  The header hands per-lane state (row values, child rows, masks) in and out by value; a helper that advanced a caller's array
+    through a reference would show here first.  The count is asserted so that no kernel is silently missed."""
+    hit = {k: v for k, v in kernels.items() if re.search(r"\bk_(refine|mcmc)_", k)}
+    assert len(hit) == 22, sorted(hit)
+    assert all(v == (0, 0) for v in hit.values()), {k: v for k, v in hit.items() if v != (0, 0)}

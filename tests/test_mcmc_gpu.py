@@ -35,6 +35,7 @@ DEV = "cuda:0"
 EPS = 2.0 ** -24
 NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
 SIZES = (1, 255, 256, 257, 70001)
+SCAN_CHUNK = (65536, 65537)               # exactly 256 workgroup counts and one more: the chunk boundary of the one-workgroup scan's carry
 MIN_OP = 0.005
 MIN_OP32 = float(torch.tensor(MIN_OP, dtype=torch.float32))          # what the C ABI receives
 MAX_OP = 1.0 - 2.0 ** -23
@@ -95,7 +96,7 @@ def _check_dead(op, tag):
     return n_dead
 
 
-@pytest.mark.parametrize("N", SIZES)
+@pytest.mark.parametrize("N", SIZES + SCAN_CHUNK)
 def test_dead(N):
     g = torch.Generator().manual_seed(300 + N)
     alpha = _pick(g, N, [0.6, 0.3, 0.02, 0.0051, 0.0049, 0.004, 0.001])
@@ -383,8 +384,8 @@ def _model(N, seed=31, dead_frac=0.1, **cfg):
 
 
 def _state_of(model, opts):
-    from gaussctrl_amd.refine import _optimizer_of
-    return {n: (opt, p, opt.state[p]) for n, (opt, p) in _optimizer_of(model, opts).items()}
+    from gaussctrl_amd.scene_rows import owners
+    return {n: (opt, p, opt.state[p]) for n, (opt, p) in owners(model, opts).items()}
 
 
 def test_host_relocate():

@@ -23,6 +23,7 @@ EPS = 2.0 ** -24
 KEEP, SPLIT, DUP, EMIT_SPLIT, EMIT_DUP, BELOW_ALPHA, TOO_BIG, ON_SCREEN = 1, 2, 4, 8, 16, 32, 64, 128
 NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
 SIZES = (1, 255, 256, 257, 70001)
+SCAN_CHUNK = (65536, 65537)               # exactly 256 workgroup counts and one more: the chunk boundary of the one-workgroup scan's carry
 
 # thresholds of the populations below (splatfacto's defaults except where a smaller scene needs another scale)
 TH = dict(max_dim=64.0, densify_grad_thresh=0.0002, densify_size_thresh=0.01, split_screen_size=0.05, cull_alpha_thresh=0.1,
@@ -294,8 +295,7 @@ def test_accumulate(N, C):
 
 
 # ------------------------------------------------------------------------------------------------------------ plan + apply
-@pytest.mark.parametrize("N", SIZES)
-@pytest.mark.parametrize("ns", [2, 3])
+@pytest.mark.parametrize("ns,N", [(ns, N) for ns in (2, 3) for N in SIZES + (SCAN_CHUNK if ns == 2 else ())])
 def test_plan_apply_mixed(N, ns):
     P, stats = _population(N, seed=N + ns)
     mom = _moments(P, seed=N)
