@@ -20,16 +20,7 @@
 
 namespace {
 
-// Batched views (round 5: gc_rasterize_fwd_views / gc_rasterize_bwd_views): blockIdx.z = view (camera); per-view arrays are [C][...] with
-// the strides below (elements).  A single-view launch has gridDim.z == 1: every offset is 0.
-struct CV {
-    int64_t n;       // per-Gaussian arrays of a view: xys / 2, conics / 3, colors / 3, extra, v_* ([C][N])
-    int64_t n_op;    // opacities: N when per view, 0 when one array serves every view (sigmoid(opacity) does not depend on the camera)
-    int64_t m;       // gaussian_ids_sorted ([C][M_cap])
-    int tiles;       // tile_bins ([C][T][2])
-    int bg;          // background: 3 when per view, 0 when shared
-};
-
+// Batched views (gc_rasterize_fwd_views / gc_rasterize_bwd_views): blockIdx.z = view, strides in CV (raster_tile.h).
 struct SplatB { float cxy, cyy, r, g; };
 struct SplatC { float b, e; };
 
@@ -54,37 +45,30 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_fwd(int H, int W, int tiles
     __shared__ SplatB sB[BLOCK];
     __shared__ SplatC sC[BLOCK];
     __shared__ unsigned char sMask[BLOCK];
-    const int tile = blockIdx.y * tiles_x + blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int j = blockIdx.x * TILE + 8 * (wid & 1) + (lane & 7);       // wave = one 8x8 pixel block of the tile
-    const int i = blockIdx.y * TILE + 8 * (wid >> 1) + (lane >> 3);
-    const bool inside = (i < H) && (j < W);
-    const float px = (float)j, py = (float)i;
-    const float tx0 = (float)(blockIdx.x * TILE), ty0 = (float)(blockIdx.y * TILE);
-    const int start = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
-    bool done = !inside;
-    float T = 1.f, r = 0.f, g = 0.f, b = 0.f, e = 0.f;
+    const TileCtx tc = tile_ctx(H, W, tiles_x, tile_bins);
+    const int tid = tc.tid, lane = tc.lane, wid = tc.wid, end = tc.end;
+    bool done = !tc.inside;
+    float T = 1.f;
     int last = 0;
-    for (int bs = start; bs < end; bs += BLOCK) {
+    float r = 0.f, g = 0.f, b = 0.f, e = 0.f;
+    for (int bs = tc.start; bs < end; bs += BLOCK) {
         if (__syncthreads_and(done)) break;
         const int idx = bs + tid;
         unsigned mk = 0;
         if (idx < end) {
             const int gid = ids_sorted[idx];
-            const float2 xy = *reinterpret_cast<const float2 *>(xys + 2 * gid);
-            const float c0 = conics[3 * gid], c1 = conics[3 * gid + 1], c2 = conics[3 * gid + 2];
-            const float op = opacities[gid];
-            sA[tid] = {xy.x, xy.y, op, c0};
-            sB[tid] = {c1, c2, colors[3 * gid], colors[3 * gid + 1]};
+            const Geom s = load_geometry(gid, xys, conics, opacities);
+            sA[tid] = s.a;
+            sB[tid] = {s.cxy, s.cyy, colors[3 * gid], colors[3 * gid + 1]};
             sC[tid] = {colors[3 * gid + 2], HAS_EXTRA ? extra[gid] : 0.f};
-            mk = block_mask(xy.x, xy.y, op, c0, c1, c2, tx0, ty0);
+            mk = block_mask(s, tc.tx0, tc.ty0);
         }
         sMask[tid] = (unsigned char)mk;
         __syncthreads();
         const int n = min(BLOCK, end - bs);
-        bool wave_done = __all(done);                                  // a finished wave only helps staging
+        bool wave_done = __all(done);                                // a finished wave only helps staging
         for (int c = 0; c * 64 < n && !wave_done; ++c) {
-            unsigned long long bal = __ballot((sMask[c * 64 + lane] >> wid) & 1);
+            unsigned long long bal = block_ballot(sMask, c, lane, wid);
             if (!bal) continue;
             // scalar walk over the splats that can touch this block; branch-free body (selects), the next record is read from LDS
             // while the current one is evaluated
@@ -100,27 +84,18 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_fwd(int H, int W, int tiles
                 const SplatA an = sA[tn];
                 const SplatB bn = sB[tn];
                 const SplatC cn = sC[tn];
-                const float dx = a.x - px, dy = a.y - py;
-                const float sigma = 0.5f * (a.cxx * dx * dx + bb.cyy * dy * dy) + bb.cxy * dx * dy;
-                const float alpha = fminf(ALPHA_CAP, a.opac * __expf(-sigma));
-                const bool hit = !done && !(sigma < 0.f || alpha < ALPHA_MIN);
-                const float next_T = T * (1.f - alpha);
-                const bool stop = hit && next_T <= T_STOP;
-                const bool add = hit && !stop;
-                const float vis = add ? alpha * T : 0.f;
-                r += bb.r * vis; g += bb.g * vis; b += cc.b * vis;
-                if (HAS_EXTRA) e += cc.e * vis;
-                T = add ? next_T : T;
-                last = add ? bs + t : last;
-                done |= stop;
+                const FwdStep f = fwd_step(a, bb.cxy, bb.cyy, tc.px, tc.py, bs + t, T, last, done);
+                r += bb.r * f.vis; g += bb.g * f.vis; b += cc.b * f.vis;
+                if (HAS_EXTRA) e += cc.e * f.vis;
+                T = f.T; last = f.last; done = f.done;
                 if (!more) break;
                 if (__all(done)) { wave_done = true; break; }
                 t = tn; a = an; bb = bn; cc = cn;
             }
         }
     }
-    if (inside) {
-        const int pix = i * W + j;
+    if (tc.inside) {
+        const int pix = tc.i * W + tc.j;
         final_Ts[pix] = T;
         final_index[pix] = last;
         out_img[3 * pix] = r + T * background[0];
@@ -183,19 +158,14 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
     __shared__ float sG[BLOCK * NP];
     __shared__ unsigned char sMask[BLOCK];
     __shared__ int sMax[4];
-    const int tile = blockIdx.y * tiles_x + blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int j = blockIdx.x * TILE + 8 * (wid & 1) + (lane & 7);       // wave = one 8x8 pixel block of the tile
-    const int i = blockIdx.y * TILE + 8 * (wid >> 1) + (lane >> 3);
-    const bool inside = (i < H) && (j < W);
-    const float px = (float)j, py = (float)i;
-    const float tx0 = (float)(blockIdx.x * TILE), ty0 = (float)(blockIdx.y * TILE);
-    const int start = tile_bins[2 * tile], end = tile_bins[2 * tile + 1];
-    if (end <= start) return;
-    const int pix = inside ? i * W + j : 0;
-    const float T_final = inside ? final_Ts[pix] : 1.f;
+    const TileCtx tc = tile_ctx(H, W, tiles_x, tile_bins);
+    const int tid = tc.tid, lane = tc.lane, wid = tc.wid, start = tc.start;
+    const bool inside = tc.inside;
+    if (tc.end <= start) return;
+    const BwdPixel fp = bwd_pixel(tc, W, final_Ts, final_index);
+    const int pix = fp.pix;
+    const float T_final = fp.T_final;
     float T = T_final;
-    const int bin_final = inside ? final_index[pix] : -1;
     float vo0 = 0.f, vo1 = 0.f, vo2 = 0.f, voa = 0.f;
     if (inside) {
         vo0 = v_out[3 * pix]; vo1 = v_out[3 * pix + 1]; vo2 = v_out[3 * pix + 2];
@@ -215,58 +185,40 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
     }
     const float bgdot = background[0] * vo0 + background[1] * vo1 + background[2] * vo2;
     float S0 = 0.f, S1 = 0.f, S2 = 0.f;
-    // wave / workgroup maxima of final_index: nothing beyond them was composited
-    int wmax = bin_final;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d, 64));
-    wmax = __builtin_amdgcn_readfirstlane(wmax);                       // wave-uniform: keeps the splat walk below in scalar registers
-    if (lane == 0) sMax[wid] = wmax;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) sG[q * BLOCK + tid] = 0.f;
-    __syncthreads();
-    const int kmax = __builtin_amdgcn_readfirstlane(max(max(sMax[0], sMax[1]), max(sMax[2], sMax[3])));
-    if (kmax < start) return;
+    const WalkMax wm = bwd_walk_max<NP>(fp.bin_final, tid, lane, wid, sG, sMax);
+    if (wm.kmax < start) return;
     const int col = lane & 15;
-    for (int batch_end = kmax; batch_end >= start; batch_end -= BLOCK) {
+    for (int batch_end = wm.kmax; batch_end >= start; batch_end -= BLOCK) {
         const int idx = batch_end - tid;
         int gid = -1;
         unsigned mk = 0;
         if (idx >= start) {
             gid = ids_sorted[idx];
-            const float2 xy = *reinterpret_cast<const float2 *>(xys + 2 * gid);
-            const float op = opacities[gid], c0 = conics[3 * gid], c1 = conics[3 * gid + 1], c2 = conics[3 * gid + 2];
-            sA[tid] = {xy.x, xy.y, op, c0};
-            sB[tid] = {c1, c2, colors[3 * gid], colors[3 * gid + 1]};
+            const Geom s = load_geometry(gid, xys, conics, opacities);
+            sA[tid] = s.a;
+            sB[tid] = {s.cxy, s.cyy, colors[3 * gid], colors[3 * gid + 1]};
             if constexpr (HAS_DEPTH) sBlue[tid] = {colors[3 * gid + 2], dz.extra[gid]};
             else sBlue[tid] = colors[3 * gid + 2];
-            mk = block_mask(xy.x, xy.y, op, c0, c1, c2, tx0, ty0);
+            mk = block_mask(s, tc.tx0, tc.ty0);
         }
         sMask[tid] = (unsigned char)mk;
         __syncthreads();
-        const int n = min(BLOCK, batch_end - start + 1);
-        const int t0 = max(0, batch_end - wmax);                       // wave-uniform: splats behind every pixel's last one
-        for (int c = t0 >> 6; c * 64 < n; ++c) {
-            unsigned long long bal = __ballot((sMask[c * 64 + lane] >> wid) & 1);
-            if (c * 64 < t0) bal &= ~0ull << (t0 - c * 64);
+        const BwdBatch bt = bwd_batch(batch_end, start, wm.wmax);
+        for (int c = bt.t0 >> 6; c * 64 < bt.n; ++c) {
+            unsigned long long bal = block_ballot_from(sMask, c, lane, wid, bt.t0);
             while (bal) {
                 const int t = c * 64 + __builtin_ctzll(bal);
                 bal &= bal - 1;
-                const int k = batch_end - t;
                 const SplatA a = sA[t];
                 const SplatB bb = sB[t];
-                const float dx = a.x - px, dy = a.y - py;
-                const float sigma = 0.5f * (a.cxx * dx * dx + bb.cyy * dy * dy) + bb.cxy * dx * dy;
-                const float vis = __expf(-sigma);
-                const float araw = a.opac * vis;
-                const float alpha = fminf(ALPHA_CAP, araw);
-                const bool valid = (k <= bin_final) && !(sigma < 0.f || alpha < ALPHA_MIN);
-                if (!__any(valid)) continue;
-                float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_cxx = 0.f, g_cxy = 0.f, g_cyy = 0.f, g_x = 0.f, g_y = 0.f, g_o = 0.f, g_e = 0.f;
-                float g_ax = 0.f, g_ay = 0.f;
-                if (valid) {
-                    const float ra = __builtin_amdgcn_rcpf(1.f - alpha);      // 1-ulp reciprocal: alpha <= 0.999, the IEEE division sequence is 10 instructions
-                    T *= ra;
-                    const float fac = alpha * T;
+                const Pair pr = pair_eval(a, bb.cxy, bb.cyy, tc.px, tc.py, batch_end - t, fp.bin_final);
+                if (!__any(pr.valid)) continue;
+                float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_e = 0.f, g_ax = 0.f, g_ay = 0.f;
+                GeomGrad gg{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (pr.valid) {
+                    const PairT w = pair_weight(pr.alpha, T);
+                    const float ra = w.ra, fac = w.fac;
+                    T = w.T;
                     g_r = fac * vo0; g_g = fac * vo1; g_b = fac * vo2;
                     float cb, ce = 0.f;
                     if constexpr (HAS_DEPTH) { const SplatC cc = sBlue[t]; cb = cc.b; ce = cc.e; }
@@ -280,23 +232,15 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
                     v_alpha += T_final * ra * voa;
                     v_alpha += -T_final * ra * bgdot;
                     S0 += bb.r * fac; S1 += bb.g * fac; S2 += cb * fac;
-                    // alpha clamped at the cap passes no gradient to sigma / opacity (select instead of a nested exec-mask branch)
-                    const float va = araw > ALPHA_CAP ? 0.f : vis * v_alpha;
-                    const float v_sigma = -a.opac * va;
-                    g_cxx = 0.5f * v_sigma * dx * dx;
-                    g_cxy = v_sigma * dx * dy;
-                    g_cyy = 0.5f * v_sigma * dy * dy;
-                    g_x = v_sigma * (a.cxx * dx + bb.cxy * dy);
-                    g_y = v_sigma * (bb.cxy * dx + bb.cyy * dy);
-                    g_o = va;
-                    if constexpr (ABS) { g_ax = fabsf(g_x); g_ay = fabsf(g_y); }
+                    gg = geom_grad(v_alpha, pr, a, bb.cxy, bb.cyy);
+                    if constexpr (ABS) { g_ax = fabsf(gg.x); g_ay = fabsf(gg.y); }
                 }
                 g_r = row_sum(g_r); g_g = row_sum(g_g); g_b = row_sum(g_b);
-                g_cxx = row_sum(g_cxx); g_cxy = row_sum(g_cxy); g_cyy = row_sum(g_cyy);
-                g_x = row_sum(g_x); g_y = row_sum(g_y); g_o = row_sum(g_o);
+                gg.cxx = row_sum(gg.cxx); gg.cxy = row_sum(gg.cxy); gg.cyy = row_sum(gg.cyy);
+                gg.x = row_sum(gg.x); gg.y = row_sum(gg.y); gg.o = row_sum(gg.o);
                 float x = g_r;                                          // lane column c keeps value c
-                x = col == 1 ? g_g : x; x = col == 2 ? g_b : x; x = col == 3 ? g_cxx : x; x = col == 4 ? g_cxy : x;
-                x = col == 5 ? g_cyy : x; x = col == 6 ? g_x : x; x = col == 7 ? g_y : x; x = col == 8 ? g_o : x;
+                x = col == 1 ? g_g : x; x = col == 2 ? g_b : x; x = col == 3 ? gg.cxx : x; x = col == 4 ? gg.cxy : x;
+                x = col == 5 ? gg.cyy : x; x = col == 6 ? gg.x : x; x = col == 7 ? gg.y : x; x = col == 8 ? gg.o : x;
                 if constexpr (HAS_DEPTH) { g_e = row_sum(g_e); x = col == 9 ? g_e : x; }
                 if constexpr (ABS) { g_ax = row_sum(g_ax); g_ay = row_sum(g_ay); x = col == NP - 2 ? g_ax : x; x = col == NP - 1 ? g_ay : x; }
                 x = xor_rows_sum(x);
@@ -305,12 +249,7 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
         }
         __syncthreads();
         if (gid >= 0) {                                                 // flush: NP atomics per (tile, splat) that was touched at all
-            float v[NP];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) { v[q] = sG[q * BLOCK + tid]; sG[q * BLOCK + tid] = 0.f; }
-            bool any = false;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) any |= v[q] != 0.f;
+            const auto [v, any] = take_partials<NP>(sG, tid);
             if (any) {
                 unsafeAtomicAdd(v_colors + 3 * gid, v[0]);
                 unsafeAtomicAdd(v_colors + 3 * gid + 1, v[1]);
@@ -330,38 +269,55 @@ __global__ __launch_bounds__(BLOCK) void k_rasterize_bwd(int H, int W, int tiles
     }
 }
 
+// the launches: every entry point fills CompositeArgs (what each compositing launch reads) and the IO struct of its direction, and names itself
+struct FwdIO { const float *extra; float *out_img, *out_extra, *final_Ts; int32_t *final_index; };
+struct BwdIO {
+    const float *final_Ts; const int32_t *final_index; const float *v_out, *v_out_alpha, *pre_clamp;
+    float *v_xy, *v_conic, *v_colors, *v_opacity;
+};
+
+int rasterize_fwd_impl(const char *what, int C, const CompositeArgs &a, const FwdIO &o, void *stream)
+{
+    if (const int rc = check_tiles(what, a.H, a.W, a.tiles_x, a.tiles_y)) return rc;
+    if ((o.extra == nullptr) != (o.out_extra == nullptr)) { gc::set_error("%s: extra and out_extra must be given together", what); return GC_EINVAL; }
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(a.tiles_x, a.tiles_y, C), dim3(BLOCK), 0, gc::S(stream), a.H, a.W, a.tiles_x, a.ids, a.bins, a.xys, a.conics,
+                           a.colors, a.opac, o.extra, a.bg, o.out_img, o.out_extra, o.final_Ts, o.final_index, a.cv);
+    };
+    if (o.extra) launch(k_rasterize_fwd<true>);
+    else launch(k_rasterize_fwd<false>);
+    return gc::check_launch(what);
+}
+
+int rasterize_bwd_impl(const char *what, int C, const CompositeArgs &a, const BwdIO &o, void *stream, const DepthIO *dz = nullptr,
+                       float *v_xy_abs = nullptr)
+{
+    if (const int rc = check_tiles(what, a.H, a.W, a.tiles_x, a.tiles_y)) return rc;
+    // the kernel's last two parameters are the empty structs where a switch is off
+    const auto launch = [&](auto kernel, auto dz_arg, auto abs_arg) {
+        hipLaunchKernelGGL(kernel, dim3(a.tiles_x, a.tiles_y, C), dim3(BLOCK), 0, gc::S(stream), a.H, a.W, a.tiles_x, a.ids, a.bins, a.xys, a.conics,
+                           a.colors, a.opac, a.bg, o.final_Ts, o.final_index, o.v_out, o.v_out_alpha, o.pre_clamp, o.v_xy, o.v_conic, o.v_colors,
+                           o.v_opacity, a.cv, dz_arg, abs_arg);
+    };
+    if (dz && v_xy_abs) launch(k_rasterize_bwd<true, true>, *dz, v_xy_abs);
+    else if (v_xy_abs) launch(k_rasterize_bwd<false, true>, NoDepthIO{}, v_xy_abs);
+    else if (dz) launch(k_rasterize_bwd<true, false>, *dz, NoAbsIO{});
+    else launch(k_rasterize_bwd<false, false>, NoDepthIO{}, NoAbsIO{});
+    return gc::check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
-
-static int rasterize_fwd_impl(const char *what, int C, int64_t N, int64_t M_cap, int shared_opacities, int shared_background, int img_h, int img_w,
-                              int tiles_x, int tiles_y, const int32_t *gaussian_ids_sorted,
-                              const int32_t *tile_bins, const float *xys, const float *conics, const float *colors,
-                              const float *opacities, const float *extra, const float *background, float *out_img,
-                              float *out_extra, float *final_Ts, int32_t *final_index, void *stream)
-{
-    if (!(img_h > 0 && img_w > 0 && tiles_x == (img_w + TILE - 1) / TILE && tiles_y == (img_h + TILE - 1) / TILE)) {
-        gc::set_error("%s: tile bounds do not match the image size", what); return GC_EINVAL;
-    }
-    if ((extra == nullptr) != (out_extra == nullptr)) { gc::set_error("%s: extra and out_extra must be given together", what); return GC_EINVAL; }
-    CV cv; cv.n = N; cv.n_op = shared_opacities ? 0 : N; cv.m = M_cap; cv.tiles = tiles_x * tiles_y; cv.bg = shared_background ? 0 : 3;
-    dim3 grid(tiles_x, tiles_y, C), block(BLOCK);
-    if (extra)
-        hipLaunchKernelGGL(k_rasterize_fwd<true>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted,
-                           tile_bins, xys, conics, colors, opacities, extra, background, out_img, out_extra, final_Ts, final_index, cv);
-    else
-        hipLaunchKernelGGL(k_rasterize_fwd<false>, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted,
-                           tile_bins, xys, conics, colors, opacities, extra, background, out_img, out_extra, final_Ts, final_index, cv);
-    return gc::check_launch(what);
-}
 
 int gc_rasterize_fwd(int img_h, int img_w, int tiles_x, int tiles_y, const int32_t *gaussian_ids_sorted,
                      const int32_t *tile_bins, const float *xys, const float *conics, const float *colors,
                      const float *opacities, const float *extra, const float *background, float *out_img,
                      float *out_extra, float *final_Ts, int32_t *final_index, void *stream)
 {
-    return rasterize_fwd_impl("gc_rasterize_fwd", 1, 0, 0, 1, 1, img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors,
-                              opacities, extra, background, out_img, out_extra, final_Ts, final_index, stream);
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(0, 0, 1, 1, tiles_x * tiles_y)};
+    return rasterize_fwd_impl("gc_rasterize_fwd", 1, a, {extra, out_img, out_extra, final_Ts, final_index}, stream);
 }
 
 /* C views in one launch (grid.z = view): gaussian_ids_sorted [C][M_cap], tile_bins [C][T][2], xys / conics / colors / extra [C][N][..],
@@ -372,34 +328,9 @@ int gc_rasterize_fwd_views(int C, int64_t N, int64_t M_cap, int shared_opacities
                            float *out_extra, float *final_Ts, int32_t *final_index, void *stream)
 {
     GC_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && M_cap >= 0, "bad arguments");
-    return rasterize_fwd_impl("gc_rasterize_fwd_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
-                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, extra, background, out_img, out_extra, final_Ts,
-                              final_index, stream);
-}
-
-static int rasterize_bwd_impl(const char *what, int C, int64_t N, int64_t M_cap, int shared_opacities, int shared_background, int img_h, int img_w,
-                              int tiles_x, int tiles_y, const int32_t *gaussian_ids_sorted,
-                              const int32_t *tile_bins, const float *xys, const float *conics, const float *colors,
-                              const float *opacities, const float *background, const float *final_Ts, const int32_t *final_index,
-                              const float *v_out, const float *v_out_alpha, const float *pre_clamp, float *v_xy, float *v_conic,
-                              float *v_colors, float *v_opacity, void *stream, const DepthIO *dz = nullptr, float *v_xy_abs = nullptr)
-{
-    if (!(img_h > 0 && img_w > 0 && tiles_x == (img_w + TILE - 1) / TILE && tiles_y == (img_h + TILE - 1) / TILE)) {
-        gc::set_error("%s: tile bounds do not match the image size", what); return GC_EINVAL;
-    }
-    CV cv; cv.n = N; cv.n_op = shared_opacities ? 0 : N; cv.m = M_cap; cv.tiles = tiles_x * tiles_y; cv.bg = shared_background ? 0 : 3;
-    dim3 grid(tiles_x, tiles_y, C), block(BLOCK);
-    // the kernel's last two parameters are the empty structs where a switch is off
-    const auto launch = [&](auto kernel, auto dz_arg, auto abs_arg) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, gc::S(stream), img_h, img_w, tiles_x, gaussian_ids_sorted, tile_bins, xys, conics, colors,
-                           opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity, cv,
-                           dz_arg, abs_arg);
-    };
-    if (dz && v_xy_abs) launch(k_rasterize_bwd<true, true>, *dz, v_xy_abs);
-    else if (v_xy_abs) launch(k_rasterize_bwd<false, true>, NoDepthIO{}, v_xy_abs);
-    else if (dz) launch(k_rasterize_bwd<true, false>, *dz, NoAbsIO{});
-    else launch(k_rasterize_bwd<false, false>, NoDepthIO{}, NoAbsIO{});
-    return gc::check_launch(what);
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, M_cap, shared_opacities, shared_background, tiles_x * tiles_y)};
+    return rasterize_fwd_impl("gc_rasterize_fwd_views", C, a, {extra, out_img, out_extra, final_Ts, final_index}, stream);
 }
 
 int gc_rasterize_bwd(int img_h, int img_w, int tiles_x, int tiles_y, int64_t N, const int32_t *gaussian_ids_sorted,
@@ -408,8 +339,9 @@ int gc_rasterize_bwd(int img_h, int img_w, int tiles_x, int tiles_y, int64_t N, 
                      const float *v_out, const float *v_out_alpha, float *v_xy, float *v_conic, float *v_colors,
                      float *v_opacity, void *stream)
 {
-    return rasterize_bwd_impl("gc_rasterize_bwd", 1, N, 0, 1, 1, img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors,
-                              opacities, background, final_Ts, final_index, v_out, v_out_alpha, nullptr, v_xy, v_conic, v_colors, v_opacity, stream);
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, 0, 1, 1, tiles_x * tiles_y)};
+    return rasterize_bwd_impl("gc_rasterize_bwd", 1, a, {final_Ts, final_index, v_out, v_out_alpha, nullptr, v_xy, v_conic, v_colors, v_opacity}, stream);
 }
 
 /* the same with the backward of get_outputs' rgb clamp folded into the pixel load: v_out is masked where pre_clamp > 1 */
@@ -420,9 +352,10 @@ int gc_rasterize_bwd_clamped(int img_h, int img_w, int tiles_x, int tiles_y, int
                              float *v_colors, float *v_opacity, void *stream)
 {
     GC_REQUIRE(pre_clamp, "pre_clamp image required (gc_rasterize_bwd is the form without the clamp)");
-    return rasterize_bwd_impl("gc_rasterize_bwd_clamped", 1, N, 0, 1, 1, img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics,
-                              colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity,
-                              stream);
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, 0, 1, 1, tiles_x * tiles_y)};
+    return rasterize_bwd_impl("gc_rasterize_bwd_clamped", 1, a,
+                              {final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity}, stream);
 }
 
 /* C views in one launch: v_out [C][H][W][3], v_out_alpha [C][H][W] or NULL, pre_clamp [C][H][W][3] or NULL (clamp backward folded in);
@@ -434,9 +367,10 @@ int gc_rasterize_bwd_views(int C, int64_t N, int64_t M_cap, int shared_opacities
                            float *v_conic, float *v_colors, float *v_opacity, void *stream)
 {
     GC_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && M_cap >= 0, "bad arguments");
-    return rasterize_bwd_impl("gc_rasterize_bwd_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
-                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
-                              pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream);
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, M_cap, shared_opacities, shared_background, tiles_x * tiles_y)};
+    return rasterize_bwd_impl("gc_rasterize_bwd_views", C, a,
+                              {final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity}, stream);
 }
 
 /* gc_rasterize_bwd_views with the depth channel differentiable (k_rasterize_bwd<true>): extra [C][N] = what the forward composited, depth
@@ -451,10 +385,11 @@ int gc_rasterize_bwd_depth_views(int C, int64_t N, int64_t M_cap, int shared_opa
 {
     GC_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && M_cap >= 0, "bad arguments");
     GC_REQUIRE(extra && depth && v_depth && v_extra, "extra, depth, v_depth and v_extra are required (gc_rasterize_bwd_views is the form without depth)");
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, M_cap, shared_opacities, shared_background, tiles_x * tiles_y)};
     const DepthIO dz{extra, depth, v_depth, v_extra};
-    return rasterize_bwd_impl("gc_rasterize_bwd_depth_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
-                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
-                              pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream, &dz);
+    return rasterize_bwd_impl("gc_rasterize_bwd_depth_views", C, a,
+                              {final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity}, stream, &dz);
 }
 
 /* absgrad densification (include/gaussctrl_absgrad.h, k_rasterize_bwd<.., true>): the arguments of gc_rasterize_bwd_depth_views plus v_xy_abs
@@ -473,10 +408,12 @@ int gc_rasterize_bwd_abs_views(int C, int64_t N, int64_t M_cap, int shared_opaci
         GC_REQUIRE(v_xy_abs, "v_xy_abs is required (gc_rasterize_bwd_views / gc_rasterize_bwd_depth_views are the forms without it)");
         GC_REQUIRE(set == 0 || set == 4, "extra, depth, v_depth and v_extra must be all NULL (no depth) or all set");
     }
+    const CompositeArgs a{img_h, img_w, tiles_x, tiles_y, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                          view_strides(N, M_cap, shared_opacities, shared_background, tiles_x * tiles_y)};
     const DepthIO dz{extra, depth, v_depth, v_extra};
-    return rasterize_bwd_impl("gc_rasterize_bwd_abs_views", C, N, M_cap, shared_opacities, shared_background, img_h, img_w, tiles_x, tiles_y,
-                              gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_index, v_out, v_out_alpha,
-                              pre_clamp, v_xy, v_conic, v_colors, v_opacity, stream, set == 4 ? &dz : nullptr, v_xy_abs);
+    return rasterize_bwd_impl("gc_rasterize_bwd_abs_views", C, a,
+                              {final_Ts, final_index, v_out, v_out_alpha, pre_clamp, v_xy, v_conic, v_colors, v_opacity}, stream,
+                              set == 4 ? &dz : nullptr, v_xy_abs);
 }
 
 }  // extern "C"

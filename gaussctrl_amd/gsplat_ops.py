@@ -14,6 +14,8 @@ compositing sweep for RGB + depth + alpha, and a fused backward to the six leaf 
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 
 from . import _lib as L
@@ -225,21 +227,14 @@ def _rasterize_fwd(H, W, tb, ids_s, bins, xys, conics, colors, opac, extra, back
     return out, out_e, fT, fi
 
 
-def _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, background, fT, fi, v_out, v_alpha, pre_clamp=None):
-    """pre_clamp: the un-clamped composited image -> the clamp(max=1) backward of gc_model.py:188 happens in the kernel's pixel load"""
+def _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, background, fT, fi, v_out, v_alpha):
     dev = xys.device
     v_xy = torch.zeros(N, 2, device=dev); v_conic = torch.zeros(N, 3, device=dev)
     v_col = torch.zeros(N, 3, device=dev); v_op = torch.zeros(N, device=dev)
-    if pre_clamp is None:
-        L.check(L.lib().gc_rasterize_bwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.ptr(ids_s), L.ptr(bins),
-                                         L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT),
-                                         L.ptr(fi), L.ptr(v_out), L.ptr(v_alpha), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col),
-                                         L.ptr(v_op), L.stream_ptr()), "gc_rasterize_bwd")
-    else:
-        L.check(L.lib().gc_rasterize_bwd_clamped(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.ptr(ids_s), L.ptr(bins),
-                                                 L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT),
-                                                 L.ptr(fi), L.ptr(v_out), L.ptr(v_alpha), L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic),
-                                                 L.ptr(v_col), L.ptr(v_op), L.stream_ptr()), "gc_rasterize_bwd_clamped")
+    L.check(L.lib().gc_rasterize_bwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.ptr(ids_s), L.ptr(bins),
+                                     L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT),
+                                     L.ptr(fi), L.ptr(v_out), L.ptr(v_alpha), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col),
+                                     L.ptr(v_op), L.stream_ptr()), "gc_rasterize_bwd")
     return v_xy, v_conic, v_col, v_op
 
 
@@ -375,20 +370,6 @@ def _finalize(ctx, npix, img, dep, fT):
     return img, alpha, None
 
 
-def _save_and_mark(ctx, aux, want_depth, saved, depths, dep):
-    """save_for_backward, with the two depth tensors when the depth image is differentiable (RenderAux.depth_grad); otherwise depth is
-    marked non-differentiable.  Returns the depth output (empty when there is none)."""
-    ctx.depth_grad = bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
-    if ctx.depth_grad:
-        ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
-        ctx.save_for_backward(*saved, depths, dep)
-    else:
-        ctx.save_for_backward(*saved)
-        if dep is not None:
-            ctx.mark_non_differentiable(dep)
-    return dep if dep is not None else torch.empty(0, device=saved[0].device)
-
-
 def _leaf_grad_buffers(aux, m, ls, q, dc, rest):
     """The six leaf-gradient tensors the projection backward fills: RenderAux.grad_into's (validated) or fresh ones.
     Returns (vm, vls, vq, vop, vdc, vrest), into (the caller's dict or None), acc (add to the buffers' contents)."""
@@ -404,6 +385,136 @@ def _leaf_grad_buffers(aux, m, ls, q, dc, rest):
     return bufs, into, bool(aux.grad_accumulate)
 
 
+def _cams_host(cams: list):
+    """list of `cam` dicts (camera_to_gsplat) -> ctypes float array [C][GC_VIEW_CAM_FLOATS = 35]"""
+    flat = []
+    for cam in cams:
+        flat += list(cam["viewmat"])[:12] + list(cam["fullproj"])[:16] + list(cam["origin"])[:3] + [cam["fx"], cam["fy"], cam["cx"], cam["cy"]]
+    return L.host_floats(flat)
+
+
+def _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest):
+    """the six leaf tensors as the kernels read them (detached, fp32, contiguous, opacities flat) and the SH degree of features_rest"""
+    sh_degree = {1: 0, 4: 1, 9: 2, 16: 3}[features_rest.shape[1] + 1]
+    return (_c(means), _c(log_scales), _c(quats), _c(opacities).reshape(-1), _c(features_dc), _c(features_rest)), sh_degree
+
+
+# what a fused backward needs next to the saved tensors; cams_host None: built when a batched entry point needs it; single: render_view
+_RenderMeta = collections.namedtuple("_RenderMeta", "C N M_cap shared_op shared_bg H W tb sh_degree n_use cams cams_host single")
+
+
+def _end_forward(ctx, aux, want_depth, meta, comp, saved, depths, dep, nth, M, boxes, keys_s):
+    """What both fused forwards do last: fill `aux` (the gradients of an earlier backward are dropped), keep the backward's bookkeeping on
+    ctx and save the tensors -- with the two depth tensors when the depth image is differentiable (RenderAux.depth_grad); otherwise depth
+    is marked non-differentiable.  Returns the depth output (empty when there is none)."""
+    m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp = saved
+    if aux is not None:
+        aux.xys, aux.radii, aux.num_tiles_hit, aux.M, aux.depths, aux.tile_boxes = xys, radii, nth, M, depths, boxes
+        aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
+        aux.xys_grad = aux.xys_absgrad = None
+        aux.compensation = comp
+    ctx.meta, ctx.aux = meta, aux
+    ctx.comp = comp          # (not an input or output of the function: kept as an attribute)
+    ctx.depth_grad = bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
+    if ctx.depth_grad:
+        ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
+        ctx.save_for_backward(*saved, depths, dep)
+    else:
+        ctx.save_for_backward(*saved)
+        if dep is not None:
+            ctx.mark_non_differentiable(dep)
+    return dep if dep is not None else torch.empty(0, device=m.device)
+
+
+def _composite_bwd(ctx, v_img, v_alpha, v_dep):
+    """The compositing backward of render_view (C = 1, the batched entry points' single-view case) and render_views: ONE zeroed buffer for
+    every output, the entry point picked by the switches.  Returns (v_xy, v_conic, v_col, v_op, v_ex | None, v_abs | None), shaped [N, ..]
+    for render_view and [C, N, ..] for render_views, and leaves aux.xys_grad / aux.xys_absgrad (views of the buffer)."""
+    conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp = ctx.saved_tensors[7:17]
+    mt = ctx.meta
+    C, N, M_cap, shared_op, shared_bg, H, W, tb = mt.C, mt.N, mt.M_cap, mt.shared_op, mt.shared_bg, mt.H, mt.W, mt.tb
+    lead = (N,) if mt.single else (C, N)
+    dev = xys.device
+    vo = _c(v_img) if v_img is not None else torch.zeros(C, H, W, 3, device=dev)
+    va = _c(v_alpha) if v_alpha is not None else None
+    absgrad = ctx.aux is not None and ctx.aux.absgrad
+    depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if ctx.depth_grad and v_dep is not None else (None, None, None)
+    parts = [("v_xy", 2), ("v_conic", 3), ("v_col", 3), ("v_op", 1)] + ([("v_ex", 1)] if vd is not None else []) + ([("v_abs", 2)] if absgrad else [])
+    vbuf = torch.zeros(C * N * sum(w for _, w in parts), device=dev)
+    v = {k: t.view(*lead, *((w,) if w > 1 else ())) for (k, w), t in zip(parts, vbuf.split([C * N * w for _, w in parts]))}
+    v_xy, v_conic, v_col, v_op, v_ex, v_abs = (v.get(k) for k in ("v_xy", "v_conic", "v_col", "v_op", "v_ex", "v_abs"))
+    lib = L.lib()
+    st = L.stream_ptr()
+    # (clamp(max=1) backward, gc_model.py:188: applied by the kernel when it loads the pixel's gradient)
+    if absgrad:                 # one entry point for both depth forms (NULL quartet = no depth)
+        L.check(lib.gc_rasterize_bwd_abs_views(
+            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+            L.ptr(v_ex), L.ptr(v_abs), st), "gc_rasterize_bwd_abs_views")
+    elif vd is not None:
+        L.check(lib.gc_rasterize_bwd_depth_views(
+            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
+            L.ptr(v_ex), st), "gc_rasterize_bwd_depth_views")
+    else:
+        L.check(lib.gc_rasterize_bwd_views(
+            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
+            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
+            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
+    if ctx.aux is not None:
+        ctx.aux.xys_grad = v_xy
+        if absgrad:
+            ctx.aux.xys_absgrad = v_abs
+    return v_xy, v_conic, v_col, v_op, v_ex, v_abs
+
+
+def _project_bwd(ctx, v_xy, v_conic, v_col, v_op, v_ex):
+    """The projection / SH backward to the six leaf tensors (or into RenderAux.grad_into: then autograd gets None for them).  The plain form
+    of render_view launches the single-view kernel (its own memory schedule); everything else is a batched entry point, C = 1 included."""
+    m, ls, q, op, dc, rest, radii, conics, _, rgbs = ctx.saved_tensors[:10]
+    mt = ctx.meta
+    C, N, H, W, sh_degree, n_use = mt.C, mt.N, mt.H, mt.W, mt.sh_degree, mt.n_use
+    (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
+    lib = L.lib()
+    st = L.stream_ptr()
+    if mt.single and ctx.comp is None and v_ex is None:
+        cam = mt.cams[0]
+        fn = lib.gc_project_sh_bwd_accumulate if acc else lib.gc_project_sh_bwd
+        L.check(fn(
+            L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), L.host_floats(cam["viewmat"]),
+            L.host_floats(cam["fullproj"]), L.host_floats(cam["origin"]), L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]),
+            L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+            L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_accumulate" if acc else "gc_project_sh_bwd")
+    else:
+        CH = mt.cams_host if mt.cams_host is not None else _cams_host(mt.cams)
+        acc = int(acc)
+        if ctx.comp is not None:    # antialiased: v_op is of the per-view effective opacities; v_depths may be NULL
+            L.check(lib.gc_project_sh_bwd_aa_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
+                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_aa_views")
+        elif v_ex is not None:      # the compositing's v_extra is the projection's v_depths
+            L.check(lib.gc_project_sh_bwd_depth_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_depth_views")
+        else:
+            L.check(lib.gc_project_sh_bwd_views(
+                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
+                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
+                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
+    if into is not None:
+        return (None,) * 11
+    return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
+
+
+def _render_bwd(ctx, v_img, v_alpha, v_dep):
+    v_xy, v_conic, v_col, v_op, v_ex, _ = _composite_bwd(ctx, v_img, v_alpha, v_dep)
+    return _project_bwd(ctx, v_xy, v_conic, v_col, v_op, v_ex)
+
+
 class _RenderView(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, log_scales, quats, opacities, features_dc, features_rest, cam, background, want_depth,
@@ -415,10 +526,7 @@ class _RenderView(torch.autograd.Function):
         dev = means.device
         H, W = cam["H"], cam["W"]
         tb = ((W + TILE - 1) // TILE, (H + TILE - 1) // TILE, 1)
-        K = features_rest.shape[1] + 1
-        sh_degree = {1: 0, 4: 1, 9: 2, 16: 3}[K]
-        m, ls, q = _c(means), _c(log_scales), _c(quats)
-        op, dc, rest = _c(opacities).reshape(-1), _c(features_dc), _c(features_rest)
+        (m, ls, q, op, dc, rest), sh_degree = _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest)
         V, P, O = L.host_floats(cam["viewmat"]), L.host_floats(cam["fullproj"]), L.host_floats(cam["origin"])
         xys = torch.empty(N, 2, device=dev); depths = torch.empty(N, device=dev)
         radii = torch.empty(N, dtype=torch.int32, device=dev); conics = torch.empty(N, 3, device=dev)
@@ -453,81 +561,12 @@ class _RenderView(torch.autograd.Function):
         extra = depths if want_depth else None
         img, dep, fT, fi = _rasterize_fwd(H, W, tb, ids_s, bins, xys, conics, rgbs, opac, extra, bg)
         img, alpha, pre_clamp = _finalize(ctx, H * W, img, dep, fT)
-        if aux is not None:
-            aux.xys, aux.radii, aux.num_tiles_hit, aux.M, aux.depths = xys, radii, nth, M, depths
-            aux.tile_boxes = boxes
-            aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
-            aux.xys_grad = None
-            aux.xys_absgrad = None
-            aux.compensation = comp
-        ctx.meta = (cam, tb, N, sh_degree, int(sh_degree_to_use), V, P, O)
-        ctx.aux = aux
-        ctx.comp = comp          # (not an input or output of the function: kept as an attribute)
-        dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
-                             depths, dep)
+        meta = _RenderMeta(1, N, ids_s.numel(), 1, 1, H, W, tb, sh_degree, int(sh_degree_to_use), [cam], None, True)
+        dep = _end_forward(ctx, aux, want_depth, meta, comp, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
+                           depths, dep, nth, M, boxes, keys_s)
         return img, alpha, dep
 
-    @staticmethod
-    def backward(ctx, v_img, v_alpha, v_dep):
-        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors[:17]
-        cam, tb, N, sh_degree, n_use, V, P, O = ctx.meta
-        H, W = cam["H"], cam["W"]
-        dev = m.device
-        vo = _c(v_img) if v_img is not None else torch.zeros(H, W, 3, device=dev)
-        va = _c(v_alpha) if v_alpha is not None else None
-        v_ex = None
-        with_depth = ctx.depth_grad and v_dep is not None
-        if ctx.aux is not None and ctx.aux.absgrad:        # absgrad: one entry point for both depth forms (NULL quartet = no depth), C = 1
-            depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if with_depth else (None, None, None)
-            vbuf = torch.zeros(N * (12 if with_depth else 11), device=dev)
-            v_xy = vbuf[:2 * N].view(N, 2); v_conic = vbuf[2 * N:5 * N].view(N, 3); v_col = vbuf[5 * N:8 * N].view(N, 3)
-            v_op = vbuf[8 * N:9 * N]; v_abs = vbuf[9 * N:11 * N].view(N, 2)
-            v_ex = vbuf[11 * N:] if with_depth else None
-            L.check(L.lib().gc_rasterize_bwd_abs_views(
-                L.i32(1), L.i64(N), L.i64(ids_s.numel()), L.i32(1), L.i32(1), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-                L.ptr(v_ex), L.ptr(v_abs), L.stream_ptr()), "gc_rasterize_bwd_abs_views")
-            ctx.aux.xys_absgrad = v_abs
-        elif with_depth:                                   # depth channel: the C = 1 case of the batched entry points
-            depths, dep = ctx.saved_tensors[17:]
-            vd = _c(v_dep)
-            vbuf = torch.zeros(N * 10, device=dev)
-            v_xy = vbuf[:2 * N].view(N, 2); v_conic = vbuf[2 * N:5 * N].view(N, 3); v_col = vbuf[5 * N:8 * N].view(N, 3)
-            v_op = vbuf[8 * N:9 * N]; v_ex = vbuf[9 * N:]
-            L.check(L.lib().gc_rasterize_bwd_depth_views(
-                L.i32(1), L.i64(N), L.i64(ids_s.numel()), L.i32(1), L.i32(1), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-                L.ptr(v_ex), L.stream_ptr()), "gc_rasterize_bwd_depth_views")
-        else:
-            # (clamp(max=1) backward, gc_model.py:188: applied by the kernel when it loads the pixel's gradient)
-            v_xy, v_conic, v_col, v_op = _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp)
-        if ctx.aux is not None:
-            ctx.aux.xys_grad = v_xy
-        (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
-        if ctx.comp is not None:    # antialiased: v_op is of the view's effective opacity; v_depths may be NULL
-            L.check(L.lib().gc_project_sh_bwd_aa_views(
-                L.i64(N), L.i32(1), L.i32(int(acc)), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
-                _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col),
-                L.ptr(v_op), L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), L.stream_ptr()),
-                "gc_project_sh_bwd_aa_views")
-        elif v_ex is not None:      # the compositing's v_extra is the projection's v_depths
-            L.check(L.lib().gc_project_sh_bwd_depth_views(
-                L.i64(N), L.i32(1), L.i32(int(acc)), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
-                _cams_host([cam]), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
-                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), L.stream_ptr()),
-                "gc_project_sh_bwd_depth_views")
-        else:
-            fn = L.lib().gc_project_sh_bwd_accumulate if acc else L.lib().gc_project_sh_bwd
-            L.check(fn(
-                L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use),
-                V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]), L.i32(H), L.i32(W),
-                L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.stream_ptr()), "gc_project_sh_bwd_accumulate" if acc else "gc_project_sh_bwd")
-        if into is not None:
-            return (None,) * 11
-        return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
+    backward = staticmethod(_render_bwd)
 
 
 def render_view(means, log_scales, quats, opacities, features_dc, features_rest, cam: dict, background, want_depth: bool,
@@ -539,15 +578,7 @@ def render_view(means, log_scales, quats, opacities, features_dc, features_rest,
                              sh_degree_to_use, aux)
 
 
-# --------------------------------------------------------------------------------------------- batched views (round 5)
-def _cams_host(cams: list):
-    """list of `cam` dicts (camera_to_gsplat) -> ctypes float array [C][GC_VIEW_CAM_FLOATS = 35]"""
-    flat = []
-    for cam in cams:
-        flat += list(cam["viewmat"])[:12] + list(cam["fullproj"])[:16] + list(cam["origin"])[:3] + [cam["fx"], cam["fy"], cam["cx"], cam["cy"]]
-    return L.host_floats(flat)
-
-
+# --------------------------------------------------------------------------------------------- batched views
 class _RenderViews(torch.autograd.Function):
     """C cameras of one scene through ONE set of launches (include/gaussctrl_hip.h "Batched views"): the parameter record is read once
     per batch by the projection / SH kernel and once by its backward, the sort / binning / compositing kernels run with the view as a
@@ -568,10 +599,7 @@ class _RenderViews(torch.autograd.Function):
         T = tb[0] * tb[1]
         if tb[0] > 255 or tb[1] > 255:
             raise ValueError("render_views: at most 255 x 255 tiles (packed tile boxes)")
-        K = features_rest.shape[1] + 1
-        sh_degree = {1: 0, 4: 1, 9: 2, 16: 3}[K]
-        m, ls, q = _c(means), _c(log_scales), _c(quats)
-        op, dc, rest = _c(opacities).reshape(-1), _c(features_dc), _c(features_rest)
+        (m, ls, q, op, dc, rest), sh_degree = _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest)
         CH = _cams_host(cams)
         f32 = dict(device=dev, dtype=torch.float32); i32 = dict(device=dev, dtype=torch.int32)
         xys = torch.empty(C, N, 2, **f32); depths = torch.empty(C, N, **f32); radii = torch.empty(C, N, **i32)
@@ -634,80 +662,13 @@ class _RenderViews(torch.autograd.Function):
                                            L.ptr(depths if want_depth else None), L.ptr(bg), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(fi), st),
                 "gc_rasterize_fwd_views")
         img, alpha, pre_clamp = _finalize(ctx, C * H * W, img, dep, fT)
-        if aux is not None:
-            aux.xys, aux.radii, aux.num_tiles_hit, aux.depths, aux.tile_boxes = xys, radii, nth, depths, boxes
-            aux.M = (cnt, ovf)                          # per-view device counts / overflow flags ([C] each)
-            aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, None
-            aux.xys_grad = None
-            aux.xys_absgrad = None
-            aux.compensation = comp
-        ctx.meta = (cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, int(sh_degree_to_use))
-        ctx.aux = aux
-        ctx.comp = comp
-        dep = _save_and_mark(ctx, aux, want_depth, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
-                             depths, dep)
+        meta = _RenderMeta(C, N, M_cap, shared_op, shared_bg, H, W, tb, sh_degree, int(sh_degree_to_use), cams, CH, False)
+        # aux.M: per-view device counts / overflow flags ([C] each)
+        dep = _end_forward(ctx, aux, want_depth, meta, comp, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
+                           depths, dep, nth, (cnt, ovf), boxes, None)
         return img, alpha, dep
 
-    @staticmethod
-    def backward(ctx, v_img, v_alpha, v_dep):
-        (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp) = ctx.saved_tensors[:17]
-        cams, CH, tb, N, C, M_cap, shared_bg, sh_degree, n_use = ctx.meta
-        H, W = cams[0]["H"], cams[0]["W"]
-        dev = m.device
-        lib = L.lib()
-        st = L.stream_ptr()
-        vo = _c(v_img) if v_img is not None else torch.zeros(C, H, W, 3, device=dev)
-        va = _c(v_alpha) if v_alpha is not None else None
-        with_depth = ctx.depth_grad and v_dep is not None
-        shared_op = 0 if ctx.comp is not None else 1
-        absgrad = ctx.aux is not None and ctx.aux.absgrad
-        # v_xy | v_conic | v_colors | v_opacity (| v_extra) (| v_xy_abs), each [C][N][..]
-        vbuf = torch.zeros(C * N * ((10 if with_depth else 9) + (2 if absgrad else 0)), device=dev)
-        v_xy = vbuf[:2 * C * N].view(C, N, 2); v_conic = vbuf[2 * C * N:5 * C * N].view(C, N, 3)
-        v_col = vbuf[5 * C * N:8 * C * N].view(C, N, 3); v_op = vbuf[8 * C * N:9 * C * N].view(C, N)
-        v_ex = vbuf[9 * C * N:10 * C * N].view(C, N) if with_depth else None
-        depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if with_depth else (None, None, None)
-        if absgrad:                 # one entry point for both depth forms (NULL quartet = no depth)
-            v_abs = vbuf[vbuf.numel() - 2 * C * N:].view(C, N, 2)
-            L.check(lib.gc_rasterize_bwd_abs_views(
-                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-                L.ptr(v_ex), L.ptr(v_abs), st), "gc_rasterize_bwd_abs_views")
-            ctx.aux.xys_absgrad = v_abs
-        elif with_depth:
-            L.check(lib.gc_rasterize_bwd_depth_views(
-                L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-                L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-                L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-                L.ptr(v_ex), st), "gc_rasterize_bwd_depth_views")
-        else:
-            L.check(lib.gc_rasterize_bwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
-                                               L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg),
-                                               L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va), L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic),
-                                               L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
-        if ctx.aux is not None:
-            ctx.aux.xys_grad = v_xy
-        (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
-        acc = int(acc)
-        if ctx.comp is not None:    # antialiased: v_op is of the per-view effective opacities; v_depths may be NULL
-            L.check(lib.gc_project_sh_bwd_aa_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
-                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_aa_views")
-        elif with_depth:            # the compositing's v_extra is the projection's v_depths
-            L.check(lib.gc_project_sh_bwd_depth_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_depth_views")
-        else:
-            L.check(lib.gc_project_sh_bwd_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
-        if into is not None:
-            return (None,) * 11
-        return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
+    backward = staticmethod(_render_bwd)
 
 
 def render_views(means, log_scales, quats, opacities, features_dc, features_rest, cams: list, backgrounds, want_depth: bool,

@@ -50,8 +50,8 @@ def test_absgrad_symbol_declared_listed_and_exported():
 
 
 def test_absgrad_bindings_pass_the_declared_number_of_arguments():
-    """the prototype is gc_rasterize_bwd_depth_views' plus v_xy_abs before stream, and both calls of gsplat_ops (render_view, render_views)
-    pass that many arguments"""
+    """the prototype is gc_rasterize_bwd_depth_views' plus v_xy_abs before stream, and the call of gsplat_ops (_composite_bwd, which serves
+    render_view and render_views) passes that many arguments"""
     src, _ = _declared("gaussctrl_absgrad.h")
     main, _ = _declared("gaussctrl_hip.h")
     proto = lambda text, name: re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1)
@@ -62,7 +62,7 @@ def test_absgrad_bindings_pass_the_declared_number_of_arguments():
     assert n == 31
     host = open(os.path.join(ROOT, "gaussctrl_amd", "gsplat_ops.py")).read()
     calls = [_call_args(host, m.end() - 1) for m in re.finditer(r"\." + NEW + r"\s*\(", host)]
-    assert calls == [n, n], calls
+    assert calls == [n], calls
 
 
 def test_absgrad_switches_default_to_off():

@@ -120,3 +120,18 @@ def test_densification_kernels_use_no_private_memory(kernels):
     hit = {k: v for k, v in kernels.items() if re.search(r"\bk_(refine|mcmc)_", k)}
     assert len(hit) == 22, sorted(hit)
     assert all(v == (0, 0) for v in hit.values()), {k: v for k, v in hit.items() if v != (0, 0)}
+
+
+def test_compositing_kernels_use_no_private_memory(kernels):
+    """the 18 tile compositors (csrc/raster_composite.hip, raster_composite_nd.hip on the shared csrc/raster_tile.h): k_rasterize_fwd x 2,
+    k_rasterize_bwd x 4, k_rasterize_nd_fwd / _bwd x 6 channel widths each -- no scratch, no spilled VGPRs.  The header's pieces hand the pixel
+    and pair state in and out by value, and the staged record is stored before the culling mask's branches; a piece that kept either in
+    memory would show here first.  The counts are asserted so that no instantiation is silently missed."""
+    want = {r"\bk_rasterize_fwd<": 2, r"\bk_rasterize_bwd<": 4, r"\bk_rasterize_nd_fwd<": 6, r"\bk_rasterize_nd_bwd<": 6}
+    hit = {}
+    for p, n in want.items():
+        fam = {k: v for k, v in kernels.items() if re.search(p, k)}
+        assert len(fam) == n, (p, sorted(fam))
+        hit.update(fam)
+    assert len(hit) == 18, sorted(hit)
+    assert all(v == (0, 0) for v in hit.values()), {k: v for k, v in hit.items() if v != (0, 0)}
