@@ -6,6 +6,7 @@ import dataclasses
 import numpy as np
 import pytest
 from _margins import within
+from _redzone import on_device
 import torch
 import torch.nn.functional as F
 
@@ -29,7 +30,10 @@ def _close(got, ref, dt, extra=1.0):
 
 def _rand(shape, dt, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(dt).to(DEV)
+    v = (torch.randn(shape, generator=g) * scale).to(dt)
+    out = torch.empty(v.shape, dtype=dt, device=DEV)          # (a torch factory, not .to(DEV): under the red-zone guard the input is carved too)
+    out.copy_(v)
+    return out
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -237,7 +241,7 @@ def test_cross_view_attention(dt, f, L, heads, D, coeff):
     got = ops.attention(q, k, vt, heads, sets, f, Lk=L)
     _close(got, ref, dt, extra=8.0)      # P is rounded to the activation dtype before P V (as in the reference's fp16 bmm)
     # the same through a separate reference bank (cached reference K/V)
-    bank_idx = torch.cat([torch.arange(4), f + torch.arange(4)]).to(DEV)
+    bank_idx = on_device(torch.cat([torch.arange(4), f + torch.arange(4)]), DEV)
     got2 = ops.attention(q, k, vt, heads, sets, f, Lk=L, kref=k[bank_idx].contiguous(), vtref=vt[bank_idx].contiguous(), ref_fph=4)
     assert torch.equal(got, got2)
     # product path: softmax scale * log2(e) already folded into Q (weights.prepare(heads=...)): P = exp2(q'.k)
@@ -602,7 +606,7 @@ def test_conv3x3_fp8(dt, B, H, W, Cin, Cout, stride):
         wr = _deq(w8, wsc).reshape(-1, 3, 3, Cp)[:Cout, :, :, :Cin].permute(0, 3, 1, 2)
         ref = F.conv2d(xr.permute(0, 3, 1, 2), wr, b[:Cout].double(), stride=stride, padding=1).permute(0, 2, 3, 1)
         gs = torch.zeros(B, 32, 2, device=DEV) if w8.shape[0] % 32 == 0 and (ref.shape[1] * ref.shape[2]) % 16 == 0 else None
-        got = ops.conv3x3_fp8(x8.to(DEV), w8.to(DEV), wsc.to(DEV), dt, b.to(DEV), stride=stride, a_scale=a_scale, group_stats=gs)
+        got = ops.conv3x3_fp8(on_device(x8, DEV), on_device(w8, DEV), on_device(wsc, DEV), dt, on_device(b, DEV), stride=stride, a_scale=a_scale, group_stats=gs)
         _close(got[..., :Cout], ref, dt)
         if gs is not None and w8.shape[0] == Cout:
             _stats_close(gs, _group_sums(got.reshape(B, -1, Cout), 32), _group_sums_abs(got.reshape(B, -1, Cout), 32))
@@ -618,7 +622,7 @@ def test_linear_fp8(dt, M, N, K):
     w8, wsc = quantize_rows_e4m3(torch.randn(N, K, generator=g) * K ** -0.5)
     b = torch.randn(N, generator=g); r = _rand((M, N), dt, 1.0, 3)
     ref = _deq(x8) @ _deq(w8, wsc).T + b.double()
-    got = ops.linear_fp8(x8.to(DEV), w8.to(DEV), wsc.to(DEV), dt, b.to(DEV), residual=r)
+    got = ops.linear_fp8(on_device(x8, DEV), on_device(w8, DEV), on_device(wsc, DEV), dt, on_device(b, DEV), residual=r)
     _close(got, ref + r.double().cpu(), dt)
 
 
@@ -704,7 +708,7 @@ def test_linear_fp8_qkv_transposed_v(dt, B, L, C):
     ref = _deq(x8) @ _deq(w8, wsc).T
     Lp = (L + 7) // 8 * 8
     vt = torch.zeros(B, C, Lp, dtype=dt, device=DEV)
-    qk = ops.linear_fp8(x8.to(DEV), w8.to(DEV), wsc.to(DEV), dt, rows_per_batch=L, out_t=vt, ldt=Lp, t_batch_stride=C * Lp, t_col0=2 * C,
+    qk = ops.linear_fp8(on_device(x8, DEV), on_device(w8, DEV), on_device(wsc, DEV), dt, rows_per_batch=L, out_t=vt, ldt=Lp, t_batch_stride=C * Lp, t_col0=2 * C,
                         out_cols=2 * C)
     assert qk.shape == (B, L, 2 * C)
     _close(qk, ref[..., :2 * C], dt)

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 from _margins import within
+from _redzone import on_device
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -231,13 +232,13 @@ def test_sharded_adam_slice_update_is_the_fused_adam_kernel():
     g = torch.Generator().manual_seed(0)
     init = {k: torch.randn(*s, generator=g) for k, s in shapes.items()}
     a = {k: torch.nn.Parameter(v.clone().to(dev)) for k, v in init.items()}
-    b = {k: torch.nn.Parameter(v.clone().to(dev)) for k, v in init.items()}
+    b = {k: torch.nn.Parameter(on_device(v, dev)) for k, v in init.items()}
     fp = FlatParams(a, 1); fg = FlatGrads(a, pad_to=fp.flat.numel()); sa = ShardedAdam(fp, fg, 1, 0)
     opts = {k: FusedAdam([b[k]], lr=hyper[k][0], eps=hyper[k][1]) for k in b}
     for step in range(3):
         for k in a:
             gk = torch.randn(*shapes[k], generator=g).to(dev)
-            fg.views[k].copy_(gk); b[k].grad = gk.clone()
+            fg.views[k].copy_(gk); b[k].grad = on_device(gk, dev)
         sa.step(hyper)
         for o in opts.values():
             o.step()

@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from _margins import within
+from _redzone import on_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -68,7 +69,7 @@ def _pick(g, n, values):
 def _dead(op, min_opacity=MIN_OP):
     L = _lib(); lib = L.lib()
     N = op.shape[0]
-    d = op.to(DEV).contiguous()
+    d = on_device(op, DEV)
     weights = torch.full((N,), float("nan"), device=DEV); dead_idx = torch.full((N,), -1, dtype=torch.int32, device=DEV)
     counts = torch.full((2,), -1, dtype=torch.int32, device=DEV)
     nb = lib.gc_mcmc_dead_workspace_bytes(L.i64(N))
@@ -201,8 +202,8 @@ def _relocate(P, mom, sampled, dest, n_rows, min_op=MIN_OP):
     arr = lambda ts: (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in ts])
     ts = [[dev(P[k]) for k in NAMES]] + [[None if m is None else dev(m[k]) for k in NAMES] for m in mom]
     mult = torch.full((max(N, 1),), -3, dtype=torch.int32, device=DEV)
-    s = sampled.to(DEV).contiguous()
-    d = None if dest is None else dest.to(DEV).contiguous()
+    s = on_device(sampled, DEV)
+    d = None if dest is None else on_device(dest, DEV)
     rest = int(P["features_rest"][0].numel()) if N else 45
     L.check(lib.gc_mcmc_relocate(L.i64(N), L.i64(s.numel()), L.i32(rest), L.ptr(s), L.ptr(d), L.f32(min_op), L.ptr(mult), arr(ts[0]),
                                  None if mom[0] is None else arr(ts[1]), None if mom[1] is None else arr(ts[2]), L.stream_ptr()), "gc_mcmc_relocate")
@@ -326,8 +327,8 @@ def _restate_noise(P, noise, scaler):
 def _noise_call(P, noise, scaler):
     L = _lib(); lib = L.lib()
     N = P["means"].shape[0]
-    d = {k: P[k].to(DEV).contiguous() for k in ("means", "scales", "quats", "opacities")}
-    nz = noise.to(DEV).contiguous()
+    d = {k: on_device(P[k], DEV) for k in ("means", "scales", "quats", "opacities")}
+    nz = on_device(noise, DEV)
     L.check(lib.gc_mcmc_inject_noise(L.i64(N), L.ptr(d["means"]), L.ptr(d["scales"]), L.ptr(d["quats"]), L.ptr(d["opacities"]), L.ptr(nz),
                                      L.f32(scaler), L.stream_ptr()), "gc_mcmc_inject_noise")
     torch.cuda.synchronize()

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 from _margins import within
+from _redzone import on_device
 import torch
 
 pytestmark = pytest.mark.gpu
@@ -214,23 +215,23 @@ def test_l1_ssim_loss_and_fused_adam():
     g = torch.Generator().manual_seed(0)
     for (H, W) in ((64, 48), (100, 75), (512, 512)):
         for valid in (True, False):
-            pred = torch.rand(H, W, 3, generator=g).to(DEV).requires_grad_(True)
-            tgt = torch.rand(H, W, 3, generator=g).to(DEV)
+            pred = on_device(torch.rand(H, W, 3, generator=g), DEV).requires_grad_(True)
+            tgt = on_device(torch.rand(H, W, 3, generator=g), DEV)
             ref = sd.splat_loss(pred.double(), tgt.double(), 0.2, valid=valid)
             (gref,) = torch.autograd.grad(ref, pred)
-            pred2 = pred.detach().clone().requires_grad_(True)
+            pred2 = on_device(pred.detach(), DEV).requires_grad_(True)
             got = l1_ssim_loss(pred2, tgt, 0.2, valid_window=valid)
             (3.0 * got).backward()
             assert abs(float(got) - float(ref)) < 2e-6 * max(1.0, abs(float(ref))), (H, W, valid, float(got), float(ref))
             err = float((pred2.grad / 3.0 - gref).abs().max() / gref.abs().max())
             assert err < 1e-4, (H, W, valid, err)
     ps = [torch.randn(1001, 3, generator=g).to(DEV), torch.randn(77, 15, 3, generator=g).to(DEV), torch.randn(5, generator=g).to(DEV)]
-    a = [torch.nn.Parameter(p.clone()) for p in ps]; b = [torch.nn.Parameter(p.clone()) for p in ps]
+    a = [torch.nn.Parameter(p.clone()) for p in ps]; b = [torch.nn.Parameter(on_device(p, DEV)) for p in ps]
     oa = torch.optim.Adam(a, lr=1.6e-4, eps=1e-15); ob = FusedAdam(b, lr=1.6e-4, eps=1e-15)
     for it in range(4):
         for x, y in zip(a, b):
             gr = torch.randn(x.shape, generator=g).to(DEV) * (10.0 ** (it - 2))
-            x.grad = gr.clone(); y.grad = gr.clone()
+            x.grad = gr.clone(); y.grad = on_device(gr, DEV)
         oa.step(); ob.step()
     for x, y in zip(a, b):
         assert float((x - y).abs().max()) < 1e-6
@@ -250,11 +251,11 @@ def test_mask_composite_with_real_mask(H, W, C):
     for mask in (syn.elliptical_mask(H, W), syn.elliptical_mask(H, W, soft=True)):
         mask = torch.tensor(mask)
         ref = sd.mask_composite(edited[..., :3].permute(2, 0, 1), unedited, mask)
-        got = sdops.mask_composite(edited.to(DEV).contiguous(), unedited.to(DEV), mask.to(DEV)).cpu()
+        got = sdops.mask_composite(on_device(edited, DEV), on_device(unedited, DEV), on_device(mask, DEV)).cpu()
         assert got.shape == (H, W, 3) and got.dtype == torch.float32
         assert float((got - ref).abs().max()) <= 1.2e-7          # fp32 mul/add vs fma contraction: <= 1 ulp of values in [0,1]
         inside = mask == 1.0
         if bool(inside.any()):
             assert torch.equal(got[inside], edited[..., :3][inside])
-    got0 = sdops.mask_composite(edited.to(DEV).contiguous()).cpu()
+    got0 = sdops.mask_composite(on_device(edited, DEV)).cpu()
     assert torch.equal(got0, edited[..., :3])

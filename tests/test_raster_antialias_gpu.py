@@ -30,6 +30,7 @@ import pytest
 import torch
 
 from _margins import within
+from _redzone import on_device
 from gaussctrl_amd import synthetic as syn
 from test_raster_gpu import _grad_close, _img_close
 
@@ -382,7 +383,7 @@ def test_antialiased_views_gradients(C):
     # grad_into: written (False) over garbage, added (True) to pre-filled buffers
     g = torch.Generator(device="cpu").manual_seed(5)
     for accumulate in (False, True):
-        into = {k: (torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max())).to(DEV).contiguous() for k in KEYS}
+        into = {k: on_device(torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max()), DEV) for k in KEYS}
         into["opacities"] = into["opacities"].reshape(-1).contiguous()
         before = {k: t.clone() for k, t in into.items()}
         tq = _leaves(P)
@@ -403,7 +404,7 @@ def test_antialiased_grad_into_single_view():
     g = torch.Generator(device="cpu").manual_seed(6)
     for accumulate in (False, True):
         tp = _leaves(P)
-        into = {k: (torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max())).to(DEV).contiguous() for k in KEYS}
+        into = {k: on_device(torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max()), DEV) for k in KEYS}
         into["opacities"] = into["opacities"].reshape(-1).contiguous()
         before = {k: t.clone() for k, t in into.items()}
         rgb, alpha, _ = _render(tp, _cam(c2w, K), _aux(grad_into=into, grad_accumulate=accumulate))

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from _margins import within
+from _redzone import on_device
 from gaussctrl_amd import synthetic as syn
 from test_raster_gpu import _grad_close, _img_close
 
@@ -221,7 +222,7 @@ def test_depth_grad_views(C):
         _grad_close(tp[k].grad.cpu().numpy(), single[k], scale1)
     # grad_into + grad_accumulate on pre-filled buffers: previous contents + gradient
     g = torch.Generator(device="cpu").manual_seed(5)
-    into = {k: (torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max())).to(DEV).contiguous() for k in KEYS}
+    into = {k: on_device(torch.randn(tp[k].shape, generator=g) * float(np.abs(ref[k]).max()), DEV) for k in KEYS}
     into["opacities"] = into["opacities"].reshape(-1).contiguous()
     before = {k: t.clone() for k, t in into.items()}
     tq = _leaves(P)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from _margins import within
+from _redzone import on_device
 from gaussctrl_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -130,6 +131,9 @@ def test_bin_and_sort_bit_exact(oracle_c, N, W, H, fx):
     (cnt, ovf), keys4, ids4, bins4, _ = ops.bin_and_sort_gaussians(*args, want_keys=True, m_cap=cap)
     assert int(cnt) == o["M"] and int(ovf) == 0
     assert torch.equal(ids4[:M], ids2) and torch.equal(keys4[:M], keys2) and torch.equal(bins4, bins2)
+    (cnt6, ovf6), keys6, ids6, bins6, _ = ops.bin_and_sort_gaussians(*args, want_keys=True, m_cap=M)       # a capacity of the count exactly: no overflow
+    assert int(cnt6) == o["M"] and int(ovf6) == 0 and ids6.shape[0] == M
+    assert torch.equal(ids6, ids2) and torch.equal(keys6, keys2) and torch.equal(bins6, bins2)
     if M > 64:                       # too small a capacity is reported, not silently truncated
         (cnt5, ovf5), _, _, _, _ = ops.bin_and_sort_gaussians(*args, m_cap=M // 2)
         assert int(cnt5) == o["M"] and int(ovf5) == 1
@@ -465,7 +469,7 @@ def test_tight_tile_boxes_same_images_and_gradients():
         P["opacities"][::13] = 8.0                              # opaque: the alpha >= 1/255 ellipse exceeds gsplat's 3-sigma box
         c2w = syn.make_cameras(2, seed=seed + 3)[1]
         cam = camera_to_gsplat(c2w, K["fx"], K["fy"], K["cx"], K["cy"], W, H)
-        v = torch.randn(H, W, 3, generator=torch.Generator().manual_seed(seed)).to(DEV)
+        v = on_device(torch.randn(H, W, 3, generator=torch.Generator().manual_seed(seed)), DEV)
         out = {}
         for tight in (True, False):
             tp = {k: _t(x).requires_grad_(True) for k, x in P.items()}

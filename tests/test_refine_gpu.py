@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from _margins import within
+from _redzone import on_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -165,7 +166,7 @@ def _plan(P, stats, densify, ns, split_by_screen, cull_by_scale, cull_by_screen,
     import ctypes as C
     L = _lib(); lib = L.lib()
     N = P["means"].shape[0]
-    d = lambda t: None if t is None else t.to(DEV).contiguous()
+    d = lambda t: None if t is None else on_device(t, DEV)
     sc, op = d(P["scales"]), d(P["opacities"])
     st = [d(t) for t in stats] if stats is not None else [None] * 3
     action = torch.full((N,), -1, dtype=torch.int32, device=DEV); ranks = torch.full((3, N), -1, dtype=torch.int32, device=DEV)
@@ -186,9 +187,9 @@ def _apply(P, mom, action, ranks, counts, ns, samples):
     N = P["means"].shape[0]
     n_out = counts[3]
     arr = lambda ts: (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in ts])
-    ins = [[P[k].to(DEV).contiguous() for k in NAMES]] + [[None if m is None or m[k] is None else m[k].to(DEV).contiguous() for k in NAMES] for m in mom]
+    ins = [[on_device(P[k], DEV) for k in NAMES]] + [[None if m is None or m[k] is None else on_device(m[k], DEV) for k in NAMES] for m in mom]
     outs = [[None if t is None else torch.full((n_out,) + tuple(t.shape[1:]), float("nan"), device=DEV) for t in ts] for ts in ins]
-    smp = None if samples is None else samples.to(DEV).contiguous()
+    smp = None if samples is None else on_device(samples, DEV)
     rest = int(P["features_rest"][0].numel()) if N else 45
     L.check(lib.gc_refine_apply(L.i64(N), L.i32(ns), L.i32(rest), L.i64(counts[0]), L.i64(counts[1]), L.i64(counts[2]), L.ptr(action), L.ptr(ranks),
                                 L.ptr(smp), arr(ins[0]), arr(ins[1]), arr(ins[2]), arr(outs[0]), arr(outs[1]), arr(outs[2]), L.stream_ptr()),
@@ -263,9 +264,9 @@ def test_accumulate(N, C):
     start = [torch.rand(N, generator=g) * 1e-3, torch.randint(0, 5, (N,), generator=g).float(), torch.rand(N, generator=g) * 0.2]
 
     def run(views):
-        st = [t.clone().to(DEV) for t in start]
+        st = [on_device(t, DEV) for t in start]
         for v in views:
-            x = xg[v].to(DEV).contiguous(); r = radii[v].to(DEV).contiguous()
+            x = on_device(xg[v], DEV); r = on_device(radii[v], DEV)
             Cv = x.shape[0]
             L.check(lib.gc_refine_accumulate_views(L.i64(N), L.i32(Cv), L.ptr(x), L.ptr(r), L.f32(1.0 / max(H, W)), L.ptr(st[0]), L.ptr(st[1]),
                                                    L.ptr(st[2]), L.stream_ptr()), "gc_refine_accumulate_views")
@@ -378,13 +379,13 @@ def test_reset_opacity(N):
     g = torch.Generator().manual_seed(N)
     op = torch.randn(N, 1, generator=g) * 3
     m, v = torch.randn(N, 1, generator=g), torch.rand(N, 1, generator=g)
-    d = [t.to(DEV) for t in (op, m, v)]
+    d = [on_device(t, DEV) for t in (op, m, v)]
     L.check(lib.gc_refine_reset_opacity(L.i64(N), L.f32(refine.reset_logit(thresh)), L.ptr(d[0]), L.ptr(d[1]), L.ptr(d[2]), L.stream_ptr()), "reset")
     got = [t.cpu() for t in d]
     over = op > want
     assert _bits(got[0][over], want.expand(int(over.sum()))) and _bits(got[0][~over], op[~over])          # clamp value exact, the rest untouched
     assert _bits(got[1], torch.zeros_like(m)) and _bits(got[2], torch.zeros_like(v))
-    d = op.to(DEV)                                                         # without moments
+    d = on_device(op, DEV)                                                  # without moments
     L.check(lib.gc_refine_reset_opacity(L.i64(N), L.f32(refine.reset_logit(thresh)), L.ptr(d), None, None, L.stream_ptr()), "reset")
     assert _bits(d.cpu(), got[0])
 

@@ -5,6 +5,7 @@ import math
 
 import pytest
 from _margins import within
+from _redzone import on_device
 import torch
 
 pytestmark = pytest.mark.gpu
@@ -61,8 +62,8 @@ def test_tail_matches_torch_and_the_per_op_path(dtype, B, HW, f, Lt, gate_shift)
     sd = _sd(gate_shift=gate_shift)
     w = weights.prepare(sd, dtype, dev, heads=H)
     g = torch.Generator().manual_seed(1)
-    o1, h, x = (torch.randn(B, HW, C, generator=g).to(dtype).to(dev) for _ in range(3))
-    ctx = torch.randn(B // f, Lt, CTX, generator=g).to(dtype).to(dev)
+    o1, h, x = (on_device(torch.randn(B, HW, C, generator=g).to(dtype), dev) for _ in range(3))
+    ctx = on_device(torch.randn(B // f, Lt, CTX, generator=g).to(dtype), dev)
     Lp = (Lt + 7) // 8 * 8
     k = ops.linear(ctx, w[T + ".attn2.to_k.weight"])
     vt = torch.zeros(B // f, C, Lp, dtype=dtype, device=dev)
@@ -121,7 +122,7 @@ def test_head_matches_torch_and_the_per_op_path(dtype, B, HW):
     w = weights.prepare(sd, dtype, dev, heads=H)
     assert P + ".head.w" in w
     g = torch.Generator().manual_seed(2)
-    x = (torch.randn(B, HW, C, generator=g) * 1.5 + 0.3).to(dtype).to(dev)
+    x = on_device((torch.randn(B, HW, C, generator=g) * 1.5 + 0.3).to(dtype), dev)
     coef = ops.groupnorm_coef(x, w[P + ".norm.weight"], w[P + ".norm.bias"], 32, 1e-6)
     h, qk, vt = ops.transformer_head(x, coef, w[P + ".head.w"], w[P + ".head.params"])
     # per-op path
