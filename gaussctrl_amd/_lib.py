@@ -39,6 +39,8 @@ SYMBOLS = [
     "gc_rasterize_bwd_abs_views",
     # MCMC densification (relocate, grow to a cap, perturb the means): include/gaussctrl_mcmc.h
     "gc_mcmc_dead_workspace_bytes", "gc_mcmc_dead", "gc_mcmc_relocate", "gc_mcmc_inject_noise",
+    # edit-region tracing (masks lifted onto the Gaussians, row-masked Adam): include/gaussctrl_trace.h
+    "gc_trace_mask_views", "gc_trace_select", "gc_adam_step_rows",
     "gc_dn_gemm", "gc_dn_gemm_workspace_bytes", "gc_dn_gemm_row_stat_slots", "gc_dn_gemm_chan_parts_layout", "gc_dn_gemm_selection", "gc_dn_groupnorm_apply_parts", "gc_dn_groupnorm_apply_parts_fp8", "gc_dn_groupnorm_coef_parts", "gc_dn_concat_parts_layout", "gc_dn_concat_add_parts", "gc_dn_attention", "gc_dn_groupnorm", "gc_dn_groupnorm_workspace_bytes", "gc_dn_groupnorm_apply", "gc_dn_groupnorm_apply_fp8", "gc_dn_group_stats", "gc_dn_layernorm", "gc_dn_layernorm_fp8", "gc_dn_concat_add", "gc_dn_axpby",
     "gc_dn_cast_f32", "gc_dn_softmax_rows", "gc_dn_attention_workspace_bytes", "gc_dn_attention_selection", "gc_dn_transformer_tail", "gc_dn_transformer_tail_layout", "gc_dn_transformer_head", "gc_dn_groupnorm_coef", "gc_dn_cfg_ddim_step", "gc_dn_depth_to_disparity", "gc_dn_mask_composite",
 ]

@@ -10,6 +10,7 @@
 // Everything is HBM-bound: the SSIM windows are separable (2 x 11 taps) and run on LDS tiles; Adam is one fused
 // read-modify-write of (param, grad, m, v) with 16-byte accesses and the bias correction folded into two scalars.
 #include "common.h"
+#include "../../include/gaussctrl_trace.h"
 
 namespace {
 
@@ -178,6 +179,44 @@ __global__ __launch_bounds__(256) void k_adam(float *__restrict__ p, const float
     }
 }
 
+// k_adam on the rows with sel[row] != 0 (gc_adam_step_rows, include/gaussctrl_trace.h): the tensor is [rows][rf] floats, a 16-byte chunk
+// may straddle rows (rf = 1, 3, 4, 45 in use).  The select bytes of a chunk's four elements are read FIRST: a chunk without a selected
+// element issues no load of p / g / m / v and no store -- with a tenth of the scene selected nine tenths of the traffic go.  A chunk with
+// one is updated whole by the GC_ADAM1 expression of k_adam (the same bits) and blended with what was loaded, so unselected elements are
+// stored back with the bits they had.
+__global__ __launch_bounds__(256) void k_adam_rows(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, const uint8_t *__restrict__ sel, uint32_t rf, uint32_t n4,
+                                                   uint32_t n, float beta1, float beta2, float eps, float step_size, float inv_sqrt_bc2)
+{
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        uint32_t row = (4 * i) / rf, rem = 4 * i - row * rf;             // element 4 i .. 4 i + 3: row and offset inside it
+        bool s[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s[k] = sel[row] != 0;
+            if (++rem == rf) { rem = 0; ++row; }
+        }
+        if (!(s[0] | s[1] | s[2] | s[3])) continue;
+        float4 pp = reinterpret_cast<float4 *>(p)[i], gg = reinterpret_cast<const float4 *>(g)[i];
+        float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
+        const float4 p0 = pp, m0 = mm, v0 = vv;
+        GC_ADAM1(x) GC_ADAM1(y) GC_ADAM1(z) GC_ADAM1(w)
+#define GC_ADAM_KEEP(c, k) pp.c = s[k] ? pp.c : p0.c; mm.c = s[k] ? mm.c : m0.c; vv.c = s[k] ? vv.c : v0.c;
+        GC_ADAM_KEEP(x, 0) GC_ADAM_KEEP(y, 1) GC_ADAM_KEEP(z, 2) GC_ADAM_KEEP(w, 3)
+#undef GC_ADAM_KEEP
+        reinterpret_cast<float4 *>(p)[i] = pp; reinterpret_cast<float4 *>(m)[i] = mm; reinterpret_cast<float4 *>(v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail (n not a multiple of 4), k_adam's
+        const uint32_t i = n4 * 4 + threadIdx.x;
+        if (sel[i / rf]) {
+            const float gi = g[i];
+            const float mi = beta1 * m[i] + (1.f - beta1) * gi, vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+            m[i] = mi; v[i] = vi;
+            p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+        }
+    }
+}
+
 // Depth L1 (gc_depth_l1_fwd_bwd_views): mean |pred - target| over the pixels where both depths are real -- neither is the 1000 sentinel
 // gc_raster_finalize writes where alpha == 0, both are finite.  Two small streaming kernels; the valid count never leaves the device:
 // k_depth_l1_reduce leaves (sum, count) per workgroup, k_depth_l1_grad folds a view's partials (<= DL1_MAXB, one wave, fixed order:
@@ -342,6 +381,23 @@ int gc_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg
     hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, gc::S(stream), param, grad, exp_avg, exp_avg_sq, n4, n, beta1, beta2, eps,
                        step_size, inv_sqrt_bc2);
     return gc::check_launch("gc_adam_step");
+}
+
+/* gc_adam_step on the rows with row_select != 0 (include/gaussctrl_trace.h): same step_size / inv_sqrt_bc2, same grid. */
+int gc_adam_step_rows(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t rows, int row_floats,
+                      const uint8_t *row_select, float lr, float beta1, float beta2, float eps, int step, void *stream)
+{
+    GC_REQUIRE(param && grad && exp_avg && exp_avg_sq && row_select && rows >= 0 && row_floats >= 1 && step >= 1, "bad arguments");
+    GC_REQUIRE(rows < (1ll << 31) && rows * row_floats < (1ll << 31), "rows * row_floats must be < 2^31 elements");
+    const int64_t n = rows * row_floats;
+    if (n == 0) return GC_OK;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const int64_t n4 = n / 4;
+    const unsigned grid = (unsigned)std::min<int64_t>((n4 + 255) / 256 + 1, 256 * 8);
+    hipLaunchKernelGGL(k_adam_rows, dim3(grid), dim3(256), 0, gc::S(stream), param, grad, exp_avg, exp_avg_sq, row_select, (uint32_t)row_floats,
+                       (uint32_t)n4, (uint32_t)n, beta1, beta2, eps, step_size, inv_sqrt_bc2);
+    return gc::check_launch("gc_adam_step_rows");
 }
 
 }  // extern "C"

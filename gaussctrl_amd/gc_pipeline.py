@@ -97,6 +97,20 @@ class GaussCtrlPipelineConfig(_PipelineConfigBase):
                                        # hold a surface; 0: the loss dict of the reference (rgb only)
     synthetic_weights: bool = False    # True: seeded random SD1.5-shaped weights + hashed prompt embeddings (bench / tests; there
                                        # are no checkpoints on the build machines).  False: checkpoints are REQUIRED -- no silent fallback.
+    edit_region: str = "image"         # what a masked edit (langsam_obj) protects: "image" = the reference's behaviour, the unedited pixels are
+                                       # pasted back into every edited view (gc_pipeline.py:226-234) and training moves every Gaussian; "traced" =
+                                       # also lift the masks onto the Gaussians by their compositing weights over all training views
+                                       # (gaussctrl_amd/edit_region.py, include/gaussctrl_trace.h) and let the optimizers step the traced rows only:
+                                       # every other Gaussian keeps its bits.  Stand-alone trainer, one GPU, no row-adding densification.
+    trace_ratio_thresh: float = 0.5    # "traced": a Gaussian is in the edit region when more than this share of its compositing weight ...
+    trace_min_weight: float = 0.0      # ... comes from masked pixels, and its total weight over all views exceeds this
+
+    def __post_init__(self):
+        parent = getattr(super(), "__post_init__", None)
+        if parent is not None:
+            parent()
+        from .edit_region import check_mode
+        check_mode(self.edit_region)
 
 
 class GaussCtrlPipeline(_PipelineBase):
@@ -116,6 +130,8 @@ class GaussCtrlPipeline(_PipelineBase):
         self._dev = torch.device(device)
         self.test_mode = test_mode
         self.world_size, self.local_rank = world_size, local_rank
+        self.mask_fn = mask_fn
+        self._edit_region_traced()          # refuses the combinations "traced" does not cover before anything is loaded
         self.edit_prompt, self.reverse_prompt = config.edit_prompt, config.reverse_prompt
         added_prompt = "best quality, extremely detailed"                                        # :104-107
         self.positive_prompt = self.edit_prompt + ", " + added_prompt
@@ -179,7 +195,7 @@ class GaussCtrlPipeline(_PipelineBase):
             text_encoder = _hash_text_encoder
             self.weights_source["text_encoder"] = "synthetic(hash of the prompt)"
         self.text_encoder = text_encoder                           # CLIP text tower: outside the hot path
-        self.mask_fn = mask_fn                                     # LangSAM stand-in: image[H,W,3] -> mask[H,W] (out of scope)
+        # (self.mask_fn, the LangSAM stand-in image[H,W,3] -> mask[H,W], was set above: LangSAM itself is out of scope)
         self.bank_hook = None                                      # optional callable(RefBank | None), called once inside edit_images (tests)
         self._spread_calls = 0                                     # training steps taken in train_mode "throughput" / "sharded" (view schedule)
         print("[gaussctrl_amd] diffusion weights: " + ", ".join(f"{k} <- {v}" for k, v in sorted(self.weights_source.items())))
@@ -203,6 +219,52 @@ class GaussCtrlPipeline(_PipelineBase):
     def _encode(self, prompt):
         return self.text_encoder(prompt).to(self._dev)
 
+    # ------------------------------------------------------------------------------------ edit_region "traced"
+    def _edit_region_traced(self) -> bool:
+        """config.edit_region == "traced", checked where it is read (the field may have been assigned): a wrong name and every combination
+        the traced region does not cover raise here"""
+        from . import edit_region as er
+        if not er.check_mode(getattr(self.config, "edit_region", "image")):
+            return False
+        er.refuse_unsupported(self.config, self.model, self.world_size, self.config.langsam_obj != "" and self.mask_fn is not None, HAVE_NERFSTUDIO)
+        return True
+
+    @torch.no_grad()
+    def trace_edit_region(self):
+        """edit_region "traced": lift the stored masks of ALL training views onto the Gaussians and keep the selection as model.edit_select
+        (uint8 [N]; gc_trainer.CullCallback prunes it with the rows).  render_reverse calls this once the masks are stored; a run that fills
+        train_data from a mid-result cache calls it itself.  Returns the number of selected Gaussians."""
+        from . import edit_region as er
+        if not self._edit_region_traced():
+            raise ValueError("trace_edit_region: config.edit_region is not 'traced'")
+        td = self.datamanager.train_data
+        missing = [i for i in range(len(td)) if td[i].get("mask_image") is None]
+        if missing:
+            raise RuntimeError(f"edit_region 'traced': views {missing[:8]} have no mask_image (render_reverse or load_mid_results stores them)")
+        m = self.model
+        w_in, w_all = er.trace(m, [self.datamanager.cameras[i] for i in range(len(td))], [td[i]["mask_image"] for i in range(len(td))],
+                               views_per_launch=max(1, int(self.config.render_batch)))
+        m.edit_select, n = er.select(w_in, w_all, float(self.config.trace_ratio_thresh), float(self.config.trace_min_weight))
+        return n
+
+    def apply_edit_select(self, optimizers: dict) -> None:
+        """edit_region "traced": the optimizers of the six leaf groups step the traced rows only (train_ops.FusedAdam.row_select), from this
+        step's model.edit_select.  "image": nothing is touched."""
+        if not self._edit_region_traced():
+            return
+        sel = getattr(self.model, "edit_select", None)
+        if sel is None or sel.numel() != self.model.means.shape[0]:
+            raise RuntimeError("edit_region 'traced': no selection for the current Gaussians (render_reverse / trace_edit_region makes it, "
+                               "CullCallback prunes it)")
+        from .train_ops import FusedAdam
+        for g in self._GROUP_OF:
+            opt = optimizers.get(g)
+            if opt is None:
+                continue
+            if not isinstance(opt, FusedAdam):
+                raise ValueError(f"edit_region 'traced' needs train_ops.FusedAdam for group {g!r}, not {type(opt).__name__}")
+            opt.row_select = sel
+
     def _my_views(self):
         from .dist import shard_views
         return shard_views(len(self.datamanager.cameras), self.world_size, self.local_rank)
@@ -211,7 +273,6 @@ class GaussCtrlPipeline(_PipelineBase):
     @torch.no_grad()
     def render_reverse(self, views=None):
         """Render rgb + depth of every (local) view and DDIM-invert the renders to z_0 (batched)."""
-        views = self._my_views() if views is None else list(views)
         td = self.datamanager.train_data
         rb = max(1, int(self.config.render_batch))
         batched = rb > 1 and hasattr(self.model, "get_outputs_for_cameras")
@@ -226,6 +287,9 @@ class GaussCtrlPipeline(_PipelineBase):
             td[cam_idx]["depth_image"] = depth.clone() if batched else depth  # [H,W]
             if self.config.langsam_obj != "" and self.mask_fn is not None:
                 td[cam_idx]["mask_image"] = self.mask_fn(rgb, self.config.langsam_obj)
+        traced = self._edit_region_traced()
+        all_views = views is None
+        views = self._my_views() if all_views else list(views)
         if batched:                       # each group is consumed right after its launch set: only one batch of outputs is alive at a time
             for s0 in range(0, len(views), rb):
                 grp = views[s0:s0 + rb]
@@ -234,6 +298,8 @@ class GaussCtrlPipeline(_PipelineBase):
         else:
             for cam_idx in views:         # (views may repeat: ref_indices)
                 keep(cam_idx, self._model.get_outputs_for_camera(self.datamanager.cameras[cam_idx]))
+        if traced and all_views:          # the masks of every training view are stored: lift them onto the Gaussians
+            self.trace_edit_region()
         ctx = self._encode(self.positive_reverse_prompt)
         for s in range(0, len(views), max(self.chunk_size, 1)):
             chunk = views[s:s + max(self.chunk_size, 1)]
@@ -518,6 +584,7 @@ class GaussCtrlPipeline(_PipelineBase):
                 if g not in self._GROUP_OF:
                     opt.step()
             return loss, loss_dict, metrics_dict
+        self.apply_edit_select(optimizers)
         for opt in optimizers.values():
             opt.step()
         return loss, loss_dict, metrics_dict

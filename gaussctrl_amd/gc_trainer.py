@@ -150,6 +150,8 @@ else:
                 self.pipeline.reduce_gradients()
                 loss = loss.detach()
             sharded = getattr(self.pipeline, "world_size", 1) > 1 and getattr(getattr(self.pipeline, "config", None), "train_mode", "") == "sharded"
+            if hasattr(self.pipeline, "apply_edit_select"):              # edit_region "traced": the leaf groups step the traced rows only
+                self.pipeline.apply_edit_select(self.optimizers)
             for g, opt in self.optimizers.items():                       # optimizer_scaler_step_some
                 if step % acc(g) == acc(g) - 1:
                     for pg in opt.param_groups:
@@ -209,6 +211,9 @@ class CullCallback(_Callback):
         from .scene_rows import MOMENTS, swap_rows
         keep = ~culls
         self.n_culled += int(culls.sum())
+        if getattr(m, "edit_select", None) is not None:          # edit_region "traced": the selection follows its rows
+            from .edit_region import follow_cull
+            m.edit_select = follow_cull(m.edit_select, keep)
         for gname, params in m.get_param_groups().items():      # parameter by parameter: each old tensor goes before the next is pruned
             opt = self.optimizers.get(gname)
             for p in params:

@@ -579,6 +579,83 @@ def render_view(means, log_scales, quats, opacities, features_dc, features_rest,
 
 
 # --------------------------------------------------------------------------------------------- batched views
+# what the front half of a batched launch set leaves for its compositing stage (render_views: the forward; trace_masks_views: the trace)
+_ViewsFront = collections.namedtuple("_ViewsFront", "N C H W tb leaves sh_degree CH xys depths radii conics nth rgbs boxes opac comp shared_op "
+                                                    "cnt ovf M_cap ids_s bins")
+
+
+def _views_front(means, log_scales, quats, opacities, features_dc, features_rest, cams, sh_degree_to_use, aux):
+    """Projection / SH, depth order and binning of C cameras of one scene: tight boxes, the sorted-boxes chain (or the pair chain with
+    aux.sorted_boxes = False), the antialiased per-view opacities when aux.antialiased."""
+    _need_gpu(means)
+    lib = L.lib()
+    st = L.stream_ptr()
+    N = means.shape[0]
+    dev = means.device
+    C = len(cams)
+    H, W = cams[0]["H"], cams[0]["W"]
+    assert all(c["H"] == H and c["W"] == W for c in cams), "the views of a batch share one image size"
+    tb = ((W + TILE - 1) // TILE, (H + TILE - 1) // TILE, 1)
+    T = tb[0] * tb[1]
+    if tb[0] > 255 or tb[1] > 255:
+        raise ValueError("render_views: at most 255 x 255 tiles (packed tile boxes)")
+    (m, ls, q, op, dc, rest), sh_degree = _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest)
+    CH = _cams_host(cams)
+    f32 = dict(device=dev, dtype=torch.float32); i32 = dict(device=dev, dtype=torch.int32)
+    xys = torch.empty(C, N, 2, **f32); depths = torch.empty(C, N, **f32); radii = torch.empty(C, N, **i32)
+    conics = torch.empty(C, N, 3, **f32); nth = torch.empty(C, N, **i32); rgbs = torch.empty(C, N, 3, **f32)
+    boxes = torch.empty(C, N, **i32); pairs = torch.empty(C, N, 2, **i32)
+    aa = bool(aux is not None and aux.antialiased)
+    shared_op = 0 if aa else 1          # antialiased: per-view effective opacities [C][N], the compositing kernels' shared_opacities = 0
+    if aa:
+        opac = torch.empty(C, N, **f32); comp = torch.empty(C, N, **f32)
+        L.check(lib.gc_project_sh_fwd_aa_views(
+            L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
+            CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
+            L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_aa_views")
+    else:
+        opac = torch.empty(N, **f32); comp = None
+        L.check(lib.gc_project_sh_fwd_views(
+            L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
+            CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
+            L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_views")
+    order = torch.empty(C, N, **i32); cum = torch.empty(C, N, **i32); cnt = torch.empty(C, **i32)
+    sorted_boxes = bool(getattr(aux, "sorted_boxes", True)) if aux is not None else True
+    if sorted_boxes:      # round 6: the boxes ride through the depth sort, culled Gaussians drop out in its first pass -- no per-Gaussian gathers
+        bxs = torch.empty(C, N, **i32); nvis = torch.empty(C, **i32)
+        wb = int(lib.gc_raster_order_boxes_views_workspace_bytes(L.i64(N), L.i32(C)))
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+        L.check(lib.gc_raster_order_boxes_views(L.i64(N), L.i32(C), L.ptr(pairs), L.ptr(boxes), L.ptr(order), L.ptr(bxs), L.ptr(cum), L.ptr(cnt),
+                                                L.ptr(nvis), L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_order_boxes_views")
+    else:                 # the round-5 chain (A/B, cross-check tests)
+        wb = int(lib.gc_raster_depth_order_views_workspace_bytes(L.i64(N), L.i32(C)))
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+        L.check(lib.gc_raster_depth_order_views(L.i64(N), L.i32(C), None, None, L.ptr(pairs), L.ptr(nth), L.ptr(order), L.ptr(cum), L.ptr(cnt),
+                                                L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_depth_order_views")
+    del pairs
+    m_cap = None if aux is None else aux.m_cap
+    if m_cap is None:                     # one readback of the C counts sizes the lists exactly (the sync-free form passes a capacity)
+        M_cap = max(int(cnt.max().item()), 1)
+    else:
+        M_cap = int(m_cap)
+    ids_s = torch.empty(C, M_cap, **i32); bins = torch.empty(C, T, 2, **i32); ovf = torch.empty(C, **i32)
+    bb = int(lib.gc_raster_bin_views_workspace_bytes(L.i64(M_cap), L.i32(C)))
+    del ws
+    bws = torch.empty(bb, dtype=torch.uint8, device=dev)
+    if sorted_boxes:
+        L.check(lib.gc_raster_bin_sorted_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(nvis), L.ptr(order), L.ptr(bxs),
+                                               L.ptr(cum), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(bws), L.C.c_size_t(bb), st),
+                "gc_raster_bin_sorted_views")
+        del bxs
+    else:
+        L.check(lib.gc_raster_bin_tiles_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(order), L.ptr(cum), L.ptr(boxes),
+                                              L.ptr(depths), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), None, L.ptr(bws),
+                                              L.C.c_size_t(bb), st), "gc_raster_bin_tiles_views")
+    del bws
+    return _ViewsFront(N, C, H, W, tb, (m, ls, q, op, dc, rest), sh_degree, CH, xys, depths, radii, conics, nth, rgbs, boxes, opac, comp, shared_op,
+                       cnt, ovf, M_cap, ids_s, bins)
+
+
 class _RenderViews(torch.autograd.Function):
     """C cameras of one scene through ONE set of launches (include/gaussctrl_hip.h "Batched views"): the parameter record is read once
     per batch by the projection / SH kernel and once by its backward, the sort / binning / compositing kernels run with the view as a
@@ -587,71 +664,13 @@ class _RenderViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, log_scales, quats, opacities, features_dc, features_rest, cams, backgrounds, want_depth, sh_degree_to_use, aux):
-        _need_gpu(means)
+        fr = _views_front(means, log_scales, quats, opacities, features_dc, features_rest, cams, sh_degree_to_use, aux)
+        N, C, H, W, tb, (m, ls, q, op, dc, rest), sh_degree, CH = fr[:8]
+        xys, depths, radii, conics, nth, rgbs, boxes, opac, comp, shared_op, cnt, ovf, M_cap, ids_s, bins = fr[8:]
+        del fr
         lib = L.lib()
         st = L.stream_ptr()
-        N = means.shape[0]
-        dev = means.device
-        C = len(cams)
-        H, W = cams[0]["H"], cams[0]["W"]
-        assert all(c["H"] == H and c["W"] == W for c in cams), "the views of a batch share one image size"
-        tb = ((W + TILE - 1) // TILE, (H + TILE - 1) // TILE, 1)
-        T = tb[0] * tb[1]
-        if tb[0] > 255 or tb[1] > 255:
-            raise ValueError("render_views: at most 255 x 255 tiles (packed tile boxes)")
-        (m, ls, q, op, dc, rest), sh_degree = _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest)
-        CH = _cams_host(cams)
-        f32 = dict(device=dev, dtype=torch.float32); i32 = dict(device=dev, dtype=torch.int32)
-        xys = torch.empty(C, N, 2, **f32); depths = torch.empty(C, N, **f32); radii = torch.empty(C, N, **i32)
-        conics = torch.empty(C, N, 3, **f32); nth = torch.empty(C, N, **i32); rgbs = torch.empty(C, N, 3, **f32)
-        boxes = torch.empty(C, N, **i32); pairs = torch.empty(C, N, 2, **i32)
-        aa = bool(aux is not None and aux.antialiased)
-        shared_op = 0 if aa else 1          # antialiased: per-view effective opacities [C][N], the compositing kernels' shared_opacities = 0
-        if aa:
-            opac = torch.empty(C, N, **f32); comp = torch.empty(C, N, **f32)
-            L.check(lib.gc_project_sh_fwd_aa_views(
-                L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
-                CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
-                L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_aa_views")
-        else:
-            opac = torch.empty(N, **f32); comp = None
-            L.check(lib.gc_project_sh_fwd_views(
-                L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
-                CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
-                L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_views")
-        order = torch.empty(C, N, **i32); cum = torch.empty(C, N, **i32); cnt = torch.empty(C, **i32)
-        sorted_boxes = bool(getattr(aux, "sorted_boxes", True)) if aux is not None else True
-        if sorted_boxes:      # round 6: the boxes ride through the depth sort, culled Gaussians drop out in its first pass -- no per-Gaussian gathers
-            bxs = torch.empty(C, N, **i32); nvis = torch.empty(C, **i32)
-            wb = int(lib.gc_raster_order_boxes_views_workspace_bytes(L.i64(N), L.i32(C)))
-            ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-            L.check(lib.gc_raster_order_boxes_views(L.i64(N), L.i32(C), L.ptr(pairs), L.ptr(boxes), L.ptr(order), L.ptr(bxs), L.ptr(cum), L.ptr(cnt),
-                                                    L.ptr(nvis), L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_order_boxes_views")
-        else:                 # the round-5 chain (A/B, cross-check tests)
-            wb = int(lib.gc_raster_depth_order_views_workspace_bytes(L.i64(N), L.i32(C)))
-            ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-            L.check(lib.gc_raster_depth_order_views(L.i64(N), L.i32(C), None, None, L.ptr(pairs), L.ptr(nth), L.ptr(order), L.ptr(cum), L.ptr(cnt),
-                                                    L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_depth_order_views")
-        del pairs
-        m_cap = None if aux is None else aux.m_cap
-        if m_cap is None:                     # one readback of the C counts sizes the lists exactly (the sync-free form passes a capacity)
-            M_cap = max(int(cnt.max().item()), 1)
-        else:
-            M_cap = int(m_cap)
-        ids_s = torch.empty(C, M_cap, **i32); bins = torch.empty(C, T, 2, **i32); ovf = torch.empty(C, **i32)
-        bb = int(lib.gc_raster_bin_views_workspace_bytes(L.i64(M_cap), L.i32(C)))
-        del ws
-        bws = torch.empty(bb, dtype=torch.uint8, device=dev)
-        if sorted_boxes:
-            L.check(lib.gc_raster_bin_sorted_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(nvis), L.ptr(order), L.ptr(bxs),
-                                                   L.ptr(cum), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(bws), L.C.c_size_t(bb), st),
-                    "gc_raster_bin_sorted_views")
-            del bxs
-        else:
-            L.check(lib.gc_raster_bin_tiles_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(order), L.ptr(cum), L.ptr(boxes),
-                                                  L.ptr(depths), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), None, L.ptr(bws),
-                                                  L.C.c_size_t(bb), st), "gc_raster_bin_tiles_views")
-        del bws
+        f32 = dict(device=means.device, dtype=torch.float32); i32 = dict(device=means.device, dtype=torch.int32)
         bg = _c(backgrounds)
         shared_bg = 1 if bg.dim() == 1 else 0
         assert bg.numel() == (3 if shared_bg else 3 * C)
@@ -678,3 +697,30 @@ def render_views(means, log_scales, quats, opacities, features_dc, features_rest
     aux.m_cap = per-view intersection capacity for the sync-free form (else the C counts are read back once to size the lists)."""
     return _RenderViews.apply(means, log_scales, quats, opacities, features_dc, features_rest, list(cams), backgrounds, want_depth,
                               sh_degree_to_use, aux)
+
+
+# --------------------------------------------------------------------------------------------- edit-region tracing
+@torch.no_grad()
+def trace_masks_views(means, log_scales, quats, opacities, features_dc, features_rest, cams: list, masks, w_in, w_all, aux: RenderAux | None = None):
+    """Lift the 2D masks of a LIST of cameras onto the Gaussians (include/gaussctrl_trace.h): the front half of render_views (projection,
+    depth order, binning -- the same lists, bit for bit), then gc_trace_mask_views in place of the compositing forward.  masks [C,H,W]
+    float32; w_in / w_all: float32 [N], ADDED into (w_in += sum vis * mask, w_all += sum vis over the views' pixels): zero them once, then
+    call per batch of views.  aux: tight_boxes is not read (batched views always bin tight boxes); sorted_boxes, antialiased and m_cap act
+    as in render_views; aux.M = (count [C], overflow [C]) afterwards.  No gradient."""
+    _need_gpu(means, masks, w_in, w_all)
+    N, C = means.shape[0], len(cams)
+    for t, name in ((w_in, "w_in"), (w_all, "w_all")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != N:
+            raise ValueError(f"trace_masks_views: {name} must be a contiguous float32 tensor of N = {N} elements")
+    if C == 0 or N == 0:
+        return
+    H, W = cams[0]["H"], cams[0]["W"]
+    if tuple(masks.shape) != (C, H, W):
+        raise ValueError(f"trace_masks_views: masks must be [C, H, W] = {(C, H, W)}, got {tuple(masks.shape)}")
+    mk = _c(masks)
+    fr = _views_front(means, log_scales, quats, opacities, features_dc, features_rest, list(cams), 0, aux)
+    if aux is not None:
+        aux.M = (fr.cnt, fr.ovf)
+    L.check(L.lib().gc_trace_mask_views(L.i32(C), L.i64(N), L.i64(fr.M_cap), L.i32(fr.shared_op), L.i32(H), L.i32(W), L.i32(fr.tb[0]),
+                                        L.i32(fr.tb[1]), L.ptr(fr.ids_s), L.ptr(fr.bins), L.ptr(fr.xys), L.ptr(fr.conics), L.ptr(fr.opac),
+                                        L.ptr(mk), L.ptr(w_in), L.ptr(w_all), L.stream_ptr()), "gc_trace_mask_views")

@@ -113,8 +113,13 @@ def depth_l1_loss(pred, target):
 
 
 class FusedAdam(torch.optim.Optimizer):
+    """row_select: None (every element steps: gc_adam_step), or a uint8 [rows] GPU tensor -- then a parameter whose first dimension has
+    that many rows steps only in the rows with a non-zero byte (gc_adam_step_rows, include/gaussctrl_trace.h: every other row of the
+    parameter and of both moments keeps its bits); parameters of another row count step whole."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-15):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self.row_select = None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -134,6 +139,15 @@ class FusedAdam(torch.optim.Optimizer):
                     state["exp_avg_sq"] = torch.zeros_like(p)
                 state["step"] += 1
                 g = p.grad.contiguous()
+                sel = getattr(self, "row_select", None)
+                if sel is not None and p.dim() >= 1 and p.shape[0] == sel.numel():
+                    if not sel.is_cuda or sel.dtype != torch.uint8 or not sel.is_contiguous():
+                        raise L.GaussCtrlHipError("FusedAdam.row_select must be a contiguous uint8 GPU tensor")
+                    rows = p.shape[0]
+                    L.check(lib.gc_adam_step_rows(L.ptr(p), L.ptr(g), L.ptr(state["exp_avg"]), L.ptr(state["exp_avg_sq"]), L.i64(rows),
+                                                  L.i32(p.numel() // rows if rows else 1), L.ptr(sel), L.f32(group["lr"]), L.f32(b1), L.f32(b2),
+                                                  L.f32(group["eps"]), L.i32(state["step"]), st), "gc_adam_step_rows")
+                    continue
                 L.check(lib.gc_adam_step(L.ptr(p), L.ptr(g), L.ptr(state["exp_avg"]), L.ptr(state["exp_avg_sq"]), L.i64(p.numel()),
                                          L.f32(group["lr"]), L.f32(b1), L.f32(b2), L.f32(group["eps"]), L.i32(state["step"]), st),
                         "gc_adam_step")
