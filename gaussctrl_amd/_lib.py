@@ -45,6 +45,13 @@ SYMBOLS = [
     "gc_dn_cast_f32", "gc_dn_softmax_rows", "gc_dn_attention_workspace_bytes", "gc_dn_attention_selection", "gc_dn_transformer_tail", "gc_dn_transformer_tail_layout", "gc_dn_transformer_head", "gc_dn_groupnorm_coef", "gc_dn_cfg_ddim_step", "gc_dn_depth_to_disparity", "gc_dn_mask_composite",
 ]
 
+# the extension set: entry points with the prefix gcx_, declared in headers of their own beside the counted ones above and resolved in the
+# same way (tests/test_bilagrid_abi_cpu.py checks include/gaussctrl_bilagrid.h against this list)
+EXT_SYMBOLS = [
+    # bilateral-grid colour compensation (slice forward / backward, total variation): include/gaussctrl_bilagrid.h
+    "gcx_bilagrid_slice_fwd_views", "gcx_bilagrid_slice_bwd_views", "gcx_bilagrid_tv_workspace_bytes", "gcx_bilagrid_tv_fwd_bwd",
+]
+
 _lib = None
 
 
@@ -60,11 +67,11 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
         l = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
+        for s in SYMBOLS + EXT_SYMBOLS:
             if not hasattr(l, s):
                 raise GaussCtrlHipError(f"libgaussctrl_hip.so does not export {s}")
         l.gc_last_error_string.restype = C.c_char_p
-        for s in SYMBOLS:
+        for s in SYMBOLS + EXT_SYMBOLS:
             if s.endswith("_bytes"):
                 getattr(l, s).restype = C.c_size_t
                 continue

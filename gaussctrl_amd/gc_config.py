@@ -78,9 +78,14 @@ def scheduled_lr(group: str, step: int, table: dict | None = None) -> float:
 
 
 def build_optimizers(model, table: dict | None = None, step: int = 30000):
-    """Adam per parameter group with the reference's learning rates / eps / schedules (gc_config.py:58-87) on the fused HIP Adam."""
+    """Adam per parameter group with the reference's learning rates / eps / schedules (gc_config.py:58-87) on the fused HIP Adam; a model
+    with use_bilateral_grid also gets the group "bilateral_grid" at config.bilagrid_lr, eps 1e-15, constant."""
     from .train_ops import FusedAdam
     table = table or optimizer_table()
     groups = model.get_param_groups()
-    return {name: FusedAdam(params, lr=scheduled_lr(name, step, table), eps=table[name]["optimizer"]["eps"])
+    opts = {name: FusedAdam(params, lr=scheduled_lr(name, step, table), eps=table[name]["optimizer"]["eps"])
             for name, params in groups.items() if name in table}
+    if "bilateral_grid" in groups and "bilateral_grid" not in table:
+        # use_bilateral_grid: a group of this implementation, outside the reference's table (optimizer_table() stays the reference's)
+        opts["bilateral_grid"] = FusedAdam(groups["bilateral_grid"], lr=model.config.bilagrid_lr, eps=1e-15)
+    return opts

@@ -93,6 +93,18 @@ class GaussCtrlModelConfig(_ModelConfigBase):
     mcmc_refine_every: int = 100
     mcmc_opacity_reg: float = 0.01                # loss += mcmc_opacity_reg * mean(sigmoid(opacities))
     mcmc_scale_reg: float = 0.01                  # loss += mcmc_scale_reg * mean(exp(scales))
+    use_bilateral_grid: bool = False              # True (stand-alone model, one GPU): every training view owns a learnable 3D grid of 3x4 colour
+                                                  # transforms (later splatfacto's switch of that name; gaussctrl_amd/bilagrid.py on the kernels of
+                                                  # csrc/train_bilagrid.hip).  In training mode the loss is taken on the render sliced through the
+                                                  # view's grid at (x, y, luma), so exposure / white-balance drift between the edited views lands in
+                                                  # the grids, not in the Gaussians; outputs, metrics and evaluation never see the grid.  The model
+                                                  # then needs num_train_data, owns the parameter `bilateral_grid` and the group "bilateral_grid".
+                                                  # The formulas are recalled from the paper and gsplat 1.x, not checked against their source
+                                                  # (include/gaussctrl_bilagrid.h is the contract).  Under nerfstudio the fields exist and are
+                                                  # validated; the inherited loss stays
+    bilateral_grid_shape: tuple = (16, 16, 8)     # (GW, GH, L): vertices along x, y and luma; each at least 2
+    bilagrid_tv_mult: float = 10.0                # loss += bilagrid_tv_mult * (total variation of all grids)   [gsplat's value, as recalled]
+    bilagrid_lr: float = 2e-3                     # Adam learning rate of the group "bilateral_grid" (eps 1e-15)   [gsplat's value, as recalled]
 
     def __post_init__(self):
         parent = getattr(super(), "__post_init__", None)
@@ -100,6 +112,7 @@ class GaussCtrlModelConfig(_ModelConfigBase):
             parent()
         _antialiased(self.rasterize_mode)
         _mcmc(self.densify_strategy)
+        _bilagrid(self)
 
 
 RASTERIZE_MODES = ("classic", "antialiased")
@@ -120,6 +133,19 @@ def _mcmc(strategy) -> bool:
     if strategy not in DENSIFY_STRATEGIES:
         raise ValueError(f"densify_strategy must be one of {DENSIFY_STRATEGIES}, got {strategy!r}")
     return strategy == "mcmc"
+
+
+def _bilagrid(config) -> bool:
+    """use_bilateral_grid with its three fields checked; a wrong type or range is a ValueError"""
+    from .bilagrid import check_shape
+    if not isinstance(getattr(config, "use_bilateral_grid", False), bool):
+        raise ValueError(f"use_bilateral_grid must be a bool, got {config.use_bilateral_grid!r}")
+    check_shape(getattr(config, "bilateral_grid_shape", (16, 16, 8)))
+    for name in ("bilagrid_tv_mult", "bilagrid_lr"):
+        v = getattr(config, name, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0 or v == float("inf") or (name == "bilagrid_lr" and v == 0):
+            raise ValueError(f"{name} must be a finite {'positive' if name == 'bilagrid_lr' else 'non-negative'} number, got {v!r}")
+    return bool(getattr(config, "use_bilateral_grid", False))
 
 
 class GaussCtrlModel(_ModelBase):
@@ -150,6 +176,13 @@ class GaussCtrlModel(_ModelBase):
         self.radii = None
         self.last_size = None
         self._aux = ops.RenderAux()
+        if _bilagrid(config):
+            # one grid per training view, identity at the start: a parameter, so it is in state_dict and in its own group
+            from .bilagrid import identity_grids
+            n = kwargs.get("num_train_data")
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"use_bilateral_grid needs num_train_data, the number of training views (a positive integer), got {n!r}")
+            self.bilateral_grid = nn.Parameter(identity_grids(n, *config.bilateral_grid_shape, device=device))
 
     @property
     def device(self):
@@ -165,8 +198,11 @@ class GaussCtrlModel(_ModelBase):
     def get_param_groups(self) -> Dict[str, List[nn.Parameter]]:
         if HAVE_NERFSTUDIO:
             return super().get_param_groups()
-        return {"xyz": [self.means], "features_dc": [self.features_dc], "features_rest": [self.features_rest],
-                "opacity": [self.opacities], "scaling": [self.scales], "rotation": [self.quats]}
+        groups = {"xyz": [self.means], "features_dc": [self.features_dc], "features_rest": [self.features_rest],
+                  "opacity": [self.opacities], "scaling": [self.scales], "rotation": [self.quats]}
+        if getattr(self, "bilateral_grid", None) is not None:
+            groups["bilateral_grid"] = [self.bilateral_grid]
+        return groups
 
     def get_training_callbacks(self, training_callback_attributes):
         """SplatfactoModel's callbacks (step bookkeeping, after_train, refinement_after) under nerfstudio; stand-alone: the
@@ -299,10 +335,20 @@ class GaussCtrlModel(_ModelBase):
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, torch.Tensor]:
         """SplatfactoModel.get_loss_dict [recall, SURVEY 8a/A8]: (1-l)*L1 + l*(1-SSIM), l = 0.2.  The stand-alone model with
-        config.densify_strategy = "mcmc" adds the strategy's two regularisers (plain torch: two reductions over N, not the hot path)."""
+        config.densify_strategy = "mcmc" adds the strategy's two regularisers (plain torch: two reductions over N, not the hot path).
+        The stand-alone model with config.use_bilateral_grid, in training mode, takes the main loss on the render sliced through the grid
+        of batch["image_idx"] and adds "tv_loss"; outputs["rgb"] itself, the metrics and everything at evaluation stay un-gridded."""
         from .train_ops import l1_ssim_loss
         gt = batch["image"].to(self.device)
-        loss = {"main_loss": l1_ssim_loss(outputs["rgb"], gt, self.config.ssim_lambda)}
+        grid = getattr(self, "bilateral_grid", None) if (not HAVE_NERFSTUDIO and self.training) else None
+        if grid is not None:
+            from .bilagrid import bilagrid_apply, bilagrid_tv_loss, check_view
+            view = check_view(batch["image_idx"], grid.shape[0])
+            pred = bilagrid_apply(grid, outputs["rgb"][None], [view])[0]
+            loss = {"main_loss": l1_ssim_loss(pred, gt, self.config.ssim_lambda),
+                    "tv_loss": self.config.bilagrid_tv_mult * bilagrid_tv_loss(grid)}
+        else:
+            loss = {"main_loss": l1_ssim_loss(outputs["rgb"], gt, self.config.ssim_lambda)}
         if not HAVE_NERFSTUDIO and _mcmc(getattr(self.config, "densify_strategy", "default")):
             loss["opacity_reg"] = self.config.mcmc_opacity_reg * torch.sigmoid(self.opacities).mean()
             loss["scale_reg"] = self.config.mcmc_scale_reg * torch.exp(self.scales).mean()

@@ -132,6 +132,7 @@ class GaussCtrlPipeline(_PipelineBase):
         self.world_size, self.local_rank = world_size, local_rank
         self.mask_fn = mask_fn
         self._edit_region_traced()          # refuses the combinations "traced" does not cover before anything is loaded
+        self._bilagrid_check()              # likewise use_bilateral_grid
         self.edit_prompt, self.reverse_prompt = config.edit_prompt, config.reverse_prompt
         added_prompt = "best quality, extremely detailed"                                        # :104-107
         self.positive_prompt = self.edit_prompt + ", " + added_prompt
@@ -228,6 +229,19 @@ class GaussCtrlPipeline(_PipelineBase):
             return False
         er.refuse_unsupported(self.config, self.model, self.world_size, self.config.langsam_obj != "" and self.mask_fn is not None, HAVE_NERFSTUDIO)
         return True
+
+    def _bilagrid_check(self) -> None:
+        """use_bilateral_grid of the model's config, checked where it is read: more than one GPU, and a model whose grids do not match the
+        training views, raise here"""
+        from . import bilagrid
+        m = self.model
+        mcfg = getattr(m, "config", None)
+        bilagrid.refuse_unsupported(mcfg, self.world_size)
+        grid = getattr(m, "bilateral_grid", None)
+        td = getattr(self.datamanager, "train_data", None)
+        if grid is not None and td is not None and grid.shape[0] != len(td):
+            raise ValueError(f"use_bilateral_grid: the model holds {grid.shape[0]} grids, the datamanager {len(td)} training views "
+                             "(build the model with num_train_data=len(train_data))")
 
     @torch.no_grad()
     def trace_edit_region(self):
@@ -598,6 +612,8 @@ class GaussCtrlPipeline(_PipelineBase):
             # "throughput" / "sharded": the fused backward owns the leaf gradients (grad_into) and the regularisers' autograd gradients would
             # not reach them; no multi-GPU mode relocates or grows its replicas together
             raise ValueError("densify_strategy 'mcmc' trains on one GPU only (world_size > 1 is out of its scope)")
+        from .bilagrid import refuse_unsupported as _refuse_bilagrid
+        _refuse_bilagrid(getattr(self.model, "config", None), self.world_size)      # whatever train_mode says
         mode = self.config.train_mode if multi else "single"
         if mode not in ("single", "parity", "throughput", "sharded"):
             raise ValueError(f"train_mode must be 'parity', 'throughput' or 'sharded', not {mode!r}")

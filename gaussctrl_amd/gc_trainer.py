@@ -116,8 +116,11 @@ else:
             return build_optimizers(self.pipeline.model, self.config.optimizers or None)
 
         def lr_at(self, group: str, step: int) -> float:
-            from .gc_config import scheduled_lr
-            return scheduled_lr(group, step, self.config.optimizers or None)
+            from .gc_config import optimizer_table, scheduled_lr
+            table = self.config.optimizers or optimizer_table()
+            if group == "bilateral_grid" and group not in table:       # use_bilateral_grid: outside the reference's table, constant (build_optimizers)
+                return float(self.pipeline.model.config.bilagrid_lr)
+            return scheduled_lr(group, step, table)
 
         # -- gc_trainer.py:176-207 (no viewer lock / writers)
         def train(self) -> List[float]:
@@ -208,7 +211,8 @@ class CullCallback(_Callback):
             culls = culls | (torch.exp(m.scales).max(dim=-1).values > c.cull_scale_thresh)
         if not bool(culls.any()):
             return
-        from .scene_rows import MOMENTS, swap_rows
+        from .scene_rows import MOMENTS, NAMES, swap_rows
+        rows = {id(getattr(m, n)) for n in NAMES}                # the per-Gaussian tensors: a group such as "bilateral_grid" has no rows to cull
         keep = ~culls
         self.n_culled += int(culls.sum())
         if getattr(m, "edit_select", None) is not None:          # edit_region "traced": the selection follows its rows
@@ -217,6 +221,8 @@ class CullCallback(_Callback):
         for gname, params in m.get_param_groups().items():      # parameter by parameter: each old tensor goes before the next is pruned
             opt = self.optimizers.get(gname)
             for p in params:
+                if id(p) not in rows:
+                    continue
                 st = opt.state.get(p) if opt is not None else None
                 swap_rows(m, [(opt, p, st)], [p.data[keep].contiguous()],          # whichever of the moments exist are pruned
                           [{k: st[k][keep].contiguous() for k in MOMENTS if k in st} if st else None], keep)
