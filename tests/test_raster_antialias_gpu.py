@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 import torch
 
+from _inside_scene import _rho
 from _margins import within
 from _redzone import on_device
 from gaussctrl_amd import synthetic as syn
@@ -79,28 +80,6 @@ def _scene(name):
 def _cotangents(H, W, seed):
     g = np.random.default_rng(seed)
     return (g.normal(size=(H, W, 3)).astype(np.float32), g.normal(size=(H, W)).astype(np.float32), g.normal(size=(H, W)).astype(np.float32))
-
-
-def _rho(rt, means, scales, quats, viewmat, K, radii):
-    """The compensation, from a restatement of the 2 x 2 covariance of rt.project_gaussians (its lines between `W3 = ...` and `cov = ...`,
-    before the + 0.3); 0 where the projection culls (radii == 0).  The square root is only taken where its argument is positive (autograd)."""
-    W3 = viewmat[:3, :3]
-    t = means @ W3.T + viewmat[:3, 3]
-    keep = t[:, 2] > 0.01
-    tz = torch.where(keep, t[:, 2], torch.ones_like(t[:, 2]))
-    M = rt.quat_to_rotmat(quats) * scales[:, None, :]
-    Sigma = M @ M.transpose(1, 2)
-    txc = tz * torch.clamp(t[:, 0] / tz, -1.3 * (0.5 * K["W"] / K["fx"]), 1.3 * (0.5 * K["W"] / K["fx"]))
-    tyc = tz * torch.clamp(t[:, 1] / tz, -1.3 * (0.5 * K["H"] / K["fy"]), 1.3 * (0.5 * K["H"] / K["fy"]))
-    rz = 1.0 / tz
-    zero = torch.zeros_like(rz)
-    J = torch.stack([K["fx"] * rz, zero, -K["fx"] * txc * rz * rz, zero, K["fy"] * rz, -K["fy"] * tyc * rz * rz], -1).reshape(-1, 2, 3)
-    Tm = J @ W3
-    cov = Tm @ Sigma @ Tm.transpose(1, 2)
-    a0, b, d0 = cov[:, 0, 0], cov[:, 0, 1], cov[:, 1, 1]
-    ratio = (a0 * d0 - b * b) / ((a0 + 0.3) * (d0 + 0.3) - b * b)
-    ok = keep & (radii > 0) & (ratio > 0)
-    return torch.where(ok, torch.sqrt(torch.where(ok, ratio, torch.ones_like(ratio))), torch.zeros_like(ratio))
 
 
 def _aa_forward(P, c2w, K, dtype, detach_rho=False, antialiased=True):

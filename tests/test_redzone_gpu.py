@@ -70,6 +70,9 @@ CASES = [
     _c(AA, "test_antialiased_single_view", name="b"),
     _c(AA, "test_antialiased_views_gradients", C=9),
     _c("test_absgrad_gpu", "test_absgrad_views"),
+    # projection / SH kernels alone, camera inside the cloud (N = 299: the staging tails; C = 9 crosses the 8-views-per-launch split)
+    _c("test_project_vjp_gpu", "test_fused_single_view", name="tiny", deg=3, n_use=3),
+    _c("test_project_vjp_gpu", "test_views_backward", C=9),
     # training step
     _c("test_plugin_gpu", "test_l1_ssim_loss_and_fused_adam"),
     _c(V, "test_l1_ssim_loss_views_matches_per_image"),
