@@ -73,6 +73,9 @@ CASES = [
     # projection / SH kernels alone, camera inside the cloud (N = 299: the staging tails; C = 9 crosses the 8-views-per-launch split)
     _c("test_project_vjp_gpu", "test_fused_single_view", name="tiny", deg=3, n_use=3),
     _c("test_project_vjp_gpu", "test_views_backward", C=9),
+    # compositing backward alone on crafted tile lists (tiny: the staging tails; deep: one to three backward batches)
+    *[_c("test_composite_vjp_gpu", "test_bwd_clamped", name=n, cset="a") for n in ("tiny", "deep")],
+    *[_c("test_composite_vjp_gpu", "test_bwd_views", name=n, shared=False) for n in ("tiny", "deep")],
     # training step
     _c("test_plugin_gpu", "test_l1_ssim_loss_and_fused_adam"),
     _c(V, "test_l1_ssim_loss_views_matches_per_image"),
@@ -167,7 +170,7 @@ _ran = set()
 NOT_REACHED = ["gc_abi_version", "gc_last_error_string",                       # (no device buffers)
                "gc_dn_attention_selection", "gc_dn_gemm_selection", "gc_dn_gemm_row_stat_slots", "gc_dn_transformer_tail_layout",      # (host-side queries)
                "gc_dn_depth_to_disparity", "gc_dn_group_stats", "gc_dn_groupnorm_apply", "gc_dn_groupnorm_apply_parts_fp8",
-               "gc_raster_pad_intersects", "gc_raster_scan_tiles_views", "gc_rasterize_bwd_clamped"]
+               "gc_raster_pad_intersects", "gc_raster_scan_tiles_views"]
 
 
 def test_entry_points_no_guarded_case_reaches():
