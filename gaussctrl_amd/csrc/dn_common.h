@@ -98,6 +98,34 @@ __device__ __forceinline__ uint4 pack8(const float *f)
 }
 
 __device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
+
+// f[j] = f[j] * a[j] + d[j] [SiLU]: the apply step of every normalisation kernel
+__device__ __forceinline__ void affine8(float *f, const float *a, const float *d, int act)
+{
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float v = f[j] * a[j] + d[j];
+        f[j] = act ? silu(v) : v;
+    }
+}
+
+// 8 values to memory.  Q8 = false: 16 bytes of T.  Q8 = true: 8 bytes of OCP fp8 (e4m3), stored = value * qscale (a power of two: the
+// tensor-wide E8M0 activation scale of the fp8 GEMM that consumes them) saturated to +-448.
+template <class T, bool Q8>
+__device__ __forceinline__ void store8(void *dst, const float *f, float qscale)
+{
+    if constexpr (Q8) {
+        float q[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = fminf(fmaxf(f[j] * qscale, -448.f), 448.f);
+        int w0 = 0, w1 = 0;
+        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w0, true);
+        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], w1, true);
+        *reinterpret_cast<uint2 *>(dst) = make_uint2((unsigned)w0, (unsigned)w1);
+    } else {
+        *reinterpret_cast<uint4 *>(dst) = pack8<T>(f);
+    }
+}
 // exact (erf) GELU of torch.nn.functional.gelu; erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 round-off
 // level) in ~12 VALU ops instead of the ~35 of the device-library erff -- this sits in the epilogue of the largest GEMMs
 __device__ __forceinline__ float erf_as(float x)

@@ -1,13 +1,101 @@
 // dn_norm.hip -- HBM-bound normalisation / elementwise kernels of the SD1.5 UNet / ControlNet / VAE on
 // NHWC ("tokens x channels") bf16/f16 tensors (gfx950).  Replaces torch.nn.GroupNorm / LayerNorm / SiLU /
 // cat / add and the scheduler + CFG arithmetic diffusers runs for
-// /root/reference/gaussctrl/gc_pipeline.py:142-145,209-219.
+// gaussctrl/gc_pipeline.py:142-145,209-219 of the reference.
 //
 // All kernels move 16 bytes per lane per access, statistics in fp32.
+//
+// GroupNorm    k_gn_partial + k_gn_finalize + k_gn_apply (stand-alone, three launches), k_gn_small (one launch, small maps),
+//              k_gn_apply_stats<T, Q8> (from the producer's per-group sums), k_gn_apply_parts<T, Q8> / k_gn_coef_parts (from the
+//              producer's slab partials); Q8 = e4m3 output
+// LayerNorm    k_layernorm<T, Q8>
+// concat       k_concat_add, k_concat_add_stats (+ group sums, atomics), k_concat_add_parts (+ slab partials, plain stores)
+// elementwise  k_axpby, k_cast_f32, k_softmax_rows, k_cfg_ddim, k_disp_max / k_disp_write, k_mask_composite
+// Written once, used by the kernels above: affine8 / store8 (dn_common.h), gn_coef, SlabThread + slab_reduce16, concat_chunk.
 #include "dn_common.h"
 
 namespace {
 using namespace dn;
+
+// ------------------------------------------------------------------------------------------ shared pieces
+// per-channel GroupNorm coefficients from a group's moments: y = x * a + d
+__device__ __forceinline__ void gn_coef(float mean, float rstd, float gamma, float beta, float &a, float &d)
+{
+    a = rstd * gamma;
+    d = beta - mean * a;
+}
+
+// 8 (a, d) pairs as stored ([c][2] floats, global or LDS) -> a[8], d[8]
+__device__ __forceinline__ void load_coef8(const float *coef, float *a, float *d)
+{
+    const float4 *cf = reinterpret_cast<const float4 *>(coef);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 ab = cf[j];
+        a[2 * j] = ab.x; d[2 * j] = ab.y; a[2 * j + 1] = ab.z; d[2 * j + 1] = ab.w;
+    }
+}
+
+// Thread coordinates of the slab kernels: grid = (pixel slab, channel slice, batch), a workgroup covers `nchb` 16-byte channel chunks x
+// `lanes` pixel lanes; a thread owns chunk `cch` (channels c0 .. c0 + 7) and walks the pixels p0 + pl, + lanes, ... < p1 of its slab.
+// Threads with pl >= lanes (256 % nchb of them) are idle.
+struct SlabThread {
+    int nchb, lanes, cch, pl, c0, p0, p1;
+    __device__ __forceinline__ SlabThread(int nchb_, int pix_per_block, int HW)
+        : nchb(nchb_), lanes(256 / nchb_), cch((int)threadIdx.x % nchb_), pl((int)threadIdx.x / nchb_), c0((blockIdx.y * nchb_ + cch) * 8),
+          p0(blockIdx.x * pix_per_block), p1(min(p0 + pix_per_block, HW)) {}
+    __device__ __forceinline__ bool live() const { return pl < lanes; }
+};
+
+// per-channel (s1, s2) of every live thread -> sp[pl][cch][16] (interleaved), barrier, then pixel lane 0 adds up its column in the order
+// l = 0 .. lanes - 1: acc[2 j] = sum s1[j], acc[2 j + 1] = sum s2[j] (acc is left untouched on the other lanes).  sp: [lanes][nchb][16] floats.
+__device__ __forceinline__ void slab_reduce16(float *sp, const SlabThread &st, const float *s1, const float *s2, float *acc)
+{
+    if (st.live()) {
+        float *o = sp + ((size_t)st.pl * st.nchb + st.cch) * 16;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { o[2 * j] = s1[j]; o[2 * j + 1] = s2[j]; }
+    }
+    __syncthreads();
+    if (st.pl == 0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+        for (int l = 0; l < st.lanes; ++l) {
+            const float *o = sp + ((size_t)l * st.nchb + st.cch) * 16;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] += o[j];
+        }
+    }
+}
+
+// One 16-byte chunk of [a | b (+ c)]: v (and w = the chunk of c when `add`) -> the chunk as stored, f = its 8 values (after the
+// rounding of b + c to T: statistics are taken of the values as stored)
+template <class T>
+__device__ __forceinline__ uint4 concat_combine(uint4 v, uint4 w, bool add, float *f)
+{
+    unpack8<T>(v, f);
+    if (add) {
+        float fc[8];
+        unpack8<T>(w, fc);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] += fc[j];
+        v = pack8<T>(f);
+        unpack8<T>(v, f);
+    }
+    return v;
+}
+
+// the chunk at row m, channels c0 .. c0 + 7 of the concatenation (c may be null)
+template <class T>
+__device__ __forceinline__ uint4 concat_chunk(const unsigned short *__restrict__ a, int C1, const unsigned short *__restrict__ b,
+                                              const unsigned short *__restrict__ c, int C2, size_t m, int c0, float *f)
+{
+    const uint4 none = make_uint4(0u, 0u, 0u, 0u);
+    if (c0 < C1) return concat_combine<T>(*reinterpret_cast<const uint4 *>(a + m * C1 + c0), none, false, f);
+    const uint4 v = *reinterpret_cast<const uint4 *>(b + m * C2 + (c0 - C1));
+    if (!c) return concat_combine<T>(v, none, false, f);
+    return concat_combine<T>(v, *reinterpret_cast<const uint4 *>(c + m * C2 + (c0 - C1)), true, f);
+}
 
 // ------------------------------------------------------------------------------------------ GroupNorm
 // Three streaming kernels, no atomics, 32-bit index arithmetic:
@@ -21,38 +109,25 @@ __global__ __launch_bounds__(256) void k_gn_partial(const unsigned short *__rest
 {
     extern __shared__ float sp[];   // [lanes][nchb][16]
     const int b = blockIdx.z;
-    const int lanes = 256 / nchb;
-    const int tid = threadIdx.x;
-    const int cch = tid % nchb, pl = tid / nchb;
-    const int c0 = (blockIdx.y * nchb + cch) * 8;
+    const SlabThread st(nchb, pix_per_block, HW);
+    const int c0 = st.c0;
     const unsigned short *xb = x + (size_t)b * HW * C;
-    if (pl < lanes) {
-        float sh[8], s1[8], s2[8];
-        unpack8<T>(*reinterpret_cast<const uint4 *>(xb + c0), sh);
+    float s1[8], s2[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-        const int p0 = blockIdx.x * pix_per_block;
-        const int p1 = min(p0 + pix_per_block, HW);
-        for (int p = p0 + pl; p < p1; p += lanes) {
+    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    if (st.live()) {
+        float sh[8];
+        unpack8<T>(*reinterpret_cast<const uint4 *>(xb + c0), sh);
+        for (int p = st.p0 + st.pl; p < st.p1; p += st.lanes) {
             float f[8];
             unpack8<T>(*reinterpret_cast<const uint4 *>(xb + (size_t)p * C + c0), f);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float d = f[j] - sh[j]; s1[j] += d; s2[j] += d * d; }
         }
-        float *o = sp + ((size_t)pl * nchb + cch) * 16;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { o[2 * j] = s1[j]; o[2 * j + 1] = s2[j]; }
     }
-    __syncthreads();
-    if (pl == 0) {
-        float acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-        for (int l = 0; l < lanes; ++l) {
-            const float *o = sp + ((size_t)l * nchb + cch) * 16;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] += o[j];
-        }
+    float acc[16];
+    slab_reduce16(sp, st, s1, s2, acc);
+    if (st.pl == 0) {
         float *dst = part + (((size_t)b * gridDim.x + blockIdx.x) * C + c0) * 2;
 #pragma unroll
         for (int j = 0; j < 16; j += 4) *reinterpret_cast<float4 *>(dst + j) = make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]);
@@ -116,17 +191,11 @@ __global__ __launch_bounds__(256) void k_gn_apply(const unsigned short *__restri
     for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < total_chunks; q += gridDim.x * 256u) {
         const unsigned b = q / per_img;
         const unsigned c0 = (q % nch) * 8;
-        float f[8];
+        float f[8], ca[8], cd[8];
         unpack8<T>(*reinterpret_cast<const uint4 *>(x + (size_t)q * 8), f);
-        const float4 *cf = reinterpret_cast<const float4 *>(coef + ((size_t)b * C + c0) * 2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float4 ab = cf[j];
-            float v0 = f[2 * j] * ab.x + ab.y, v1 = f[2 * j + 1] * ab.z + ab.w;
-            if (act) { v0 = silu(v0); v1 = silu(v1); }
-            f[2 * j] = v0; f[2 * j + 1] = v1;
-        }
-        *reinterpret_cast<uint4 *>(y + (size_t)q * 8) = pack8<T>(f);
+        load_coef8(coef + ((size_t)b * C + c0) * 2, ca, cd);
+        affine8(f, ca, cd, act);
+        store8<T, false>(y + (size_t)q * 8, f, 1.f);
     }
 }
 
@@ -174,39 +243,63 @@ __global__ __launch_bounds__(256) void k_gn_small(const unsigned short *__restri
 // stats[b][g] = (sum x, sum x^2) over the HW pixels and the C/G channels of group g.  ONE launch: every workgroup (blockIdx.y =
 // batch) first turns the batch's G x 2 sums into per-channel coefficients a = rstd_g * gamma_c, d = beta_c - mean_g * a in LDS, then
 // streams its share of the image: y = x * a + d [SiLU], 16 bytes per lane.  Replaces k_gn_partial + k_gn_finalize + k_gn_apply.
-template <class T>
-__global__ __launch_bounds__(256) void k_gn_apply_stats(const unsigned short *__restrict__ x, unsigned short *__restrict__ y, unsigned HW,
-                                                        unsigned C, int G, const float *__restrict__ stats, const float *__restrict__ gamma,
-                                                        const float *__restrict__ beta, float eps, int act)
+//
+// Q8: the same GroupNorm(+SiLU) with an OCP fp8 (e4m3) OUTPUT for the fp8 convolution path (k_gemm8q): y8[b][p][Cp] bytes, Cp = C rounded
+// up to a multiple of 128 (one 3x3 tap per 128-byte k-tile), padding channels written as zero; stored value = y * qscale (a power of
+// two: the tensor-wide E8M0 activation scale), saturated to +-448.
+
+// the batch's [G][2] sums -> coef[c] = (a, d) for all C channels, in LDS (ends with a barrier)
+__device__ __forceinline__ void gstats_to_coef(float *coef, const float *__restrict__ sb, unsigned HW, unsigned C, unsigned cpg,
+                                               const float *__restrict__ gamma, const float *__restrict__ beta, float eps)
 {
-    extern __shared__ float coef[];          // [C][2]
-    const unsigned b = blockIdx.y, tid = threadIdx.x, cpg = C / G;
-    const float *sb = stats + (size_t)b * G * 2;
     const float n = (float)HW * (float)cpg;
-    for (unsigned c = tid; c < C; c += 256) {
+    for (unsigned c = threadIdx.x; c < C; c += 256) {
         const unsigned g = c / cpg;
         const float mu = sb[2 * g] / n;
         const float rstd = rsqrtf(fmaxf(sb[2 * g + 1] / n - mu * mu, 0.f) + eps);
-        const float a = rstd * gamma[c];
-        coef[2 * c] = a; coef[2 * c + 1] = beta[c] - mu * a;
+        gn_coef(mu, rstd, gamma[c], beta[c], coef[2 * c], coef[2 * c + 1]);
     }
     __syncthreads();
-    const unsigned nch = C / 8, per_img = HW * nch;
-    const unsigned short *xb = x + (size_t)b * per_img * 8;
-    unsigned short *yb = y + (size_t)b * per_img * 8;
-    for (unsigned q = blockIdx.x * 256u + tid; q < per_img; q += gridDim.x * 256u) {
-        const unsigned c0 = (q % nch) * 8;
-        float f[8];
-        unpack8<T>(*reinterpret_cast<const uint4 *>(xb + (size_t)q * 8), f);
-        const float4 *cf = reinterpret_cast<const float4 *>(coef + 2 * c0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float4 ab = cf[j];
-            float v0 = f[2 * j] * ab.x + ab.y, v1 = f[2 * j + 1] * ab.z + ab.w;
-            if (act) { v0 = silu(v0); v1 = silu(v1); }
-            f[2 * j] = v0; f[2 * j + 1] = v1;
+}
+
+template <class T, bool Q8>
+__global__ __launch_bounds__(256) void k_gn_apply_stats(const unsigned short *__restrict__ x, void *__restrict__ y, unsigned HW,
+                                                        unsigned C, unsigned Cp, int G, const float *__restrict__ stats,
+                                                        const float *__restrict__ gamma, const float *__restrict__ beta, float eps, int act,
+                                                        float qscale)
+{
+    extern __shared__ float coef[];          // [C][2]
+    const unsigned b = blockIdx.y, tid = threadIdx.x;
+    gstats_to_coef(coef, stats + (size_t)b * G * 2, HW, C, C / G, gamma, beta, eps);
+    const unsigned nch = C / 8;
+    float f[8], ca[8], cd[8];
+    if constexpr (Q8) {                      // 8-byte chunks of the Cp output channels, zeros beyond C
+        const unsigned nchp = Cp / 8, per_img = HW * nchp;
+        const unsigned short *xb = x + (size_t)b * HW * C;
+        unsigned char *yb = reinterpret_cast<unsigned char *>(y) + (size_t)b * HW * Cp;
+        for (unsigned q = blockIdx.x * 256u + tid; q < per_img; q += gridDim.x * 256u) {
+            const unsigned p = q / nchp, ch = q - p * nchp;
+            if (ch < nch) {
+                const unsigned c0 = ch * 8;
+                unpack8<T>(*reinterpret_cast<const uint4 *>(xb + (size_t)p * C + c0), f);
+                load_coef8(coef + 2 * c0, ca, cd);
+                affine8(f, ca, cd, act);
+                store8<T, true>(yb + (size_t)q * 8, f, qscale);
+            } else {
+                *reinterpret_cast<uint2 *>(yb + (size_t)q * 8) = make_uint2(0u, 0u);
+            }
         }
-        *reinterpret_cast<uint4 *>(yb + (size_t)q * 8) = pack8<T>(f);
+    } else {                                 // 16-byte chunks of the C channels
+        const unsigned per_img = HW * nch;
+        const unsigned short *xb = x + (size_t)b * per_img * 8;
+        unsigned short *yb = reinterpret_cast<unsigned short *>(y) + (size_t)b * per_img * 8;
+        for (unsigned q = blockIdx.x * 256u + tid; q < per_img; q += gridDim.x * 256u) {
+            const unsigned c0 = (q % nch) * 8;
+            unpack8<T>(*reinterpret_cast<const uint4 *>(xb + (size_t)q * 8), f);
+            load_coef8(coef + 2 * c0, ca, cd);
+            affine8(f, ca, cd, act);
+            store8<T, false>(yb + (size_t)q * 8, f, 1.f);
+        }
     }
 }
 
@@ -268,22 +361,21 @@ __device__ __forceinline__ void gparts_to_moments(float *gs, float2 *red /* [256
 // statistics kernels): its 16 coefficients live in registers -- no coefficient table in the loop (the first version read a [C][2] LDS
 // table per chunk: 64-byte lane stride = 16-way bank conflicts, 43 us against 12 us for the plain apply kernel at 64 x 64 x 320 / 640) --
 // and gamma / beta and the first pixels of x are requested before the partials (nothing of that depends on the statistics).
-template <class T, bool Q8 = false>
+template <class T, bool Q8>
 __global__ __launch_bounds__(256) void k_gn_apply_parts(const unsigned short *__restrict__ x, unsigned short *__restrict__ y, unsigned HW,
                                                         unsigned C, unsigned G, const float *__restrict__ parts, int nslab, unsigned R, int mode,
                                                         unsigned col_tile, const float *__restrict__ gamma, const float *__restrict__ beta, float eps, int act,
-                                                        int nchb, int pix_per_block, unsigned Cp = 0, float qscale = 1.f)
+                                                        int nchb, int pix_per_block, unsigned Cp, float qscale)
 {
     // Q8: e4m3 output y8[b][p][Cp] bytes (Cp = C rounded up to 128, padding channels written as zero by the thread of the last chunk),
-    // stored = value * qscale saturated to +-448: the input of an fp8 convolution / linear (k_gn_apply_stats_fp8 with the producer's partials)
+    // stored = value * qscale saturated to +-448: the input of an fp8 convolution / linear (k_gn_apply_stats<T, true> with the producer's partials)
     __shared__ float gs[256];                // [G][2], G <= 128
     __shared__ float2 red[256];
-    const unsigned b = blockIdx.z, tid = threadIdx.x, cpg = C / G;
-    const int lanes = 256 / nchb;
-    const int cch = tid % nchb, pl = tid / nchb;
-    const unsigned c0 = (blockIdx.y * nchb + cch) * 8;
-    const bool live = pl < lanes;
-    const int p0 = blockIdx.x * pix_per_block, p1 = min(p0 + pix_per_block, (int)HW);
+    const unsigned b = blockIdx.z, cpg = C / G;
+    const SlabThread st(nchb, pix_per_block, (int)HW);
+    const int lanes = st.lanes, pl = st.pl, p0 = st.p0, p1 = st.p1;
+    const unsigned c0 = (unsigned)st.c0;
+    const bool live = st.live();
     const unsigned short *xb = x + (size_t)b * HW * C + c0;
     unsigned short *yb = y + (size_t)b * HW * C + c0;
     float4 gm[2], bt[2];
@@ -306,29 +398,19 @@ __global__ __launch_bounds__(256) void k_gn_apply_parts(const unsigned short *__
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const unsigned g = (c0 + j) / cpg;
-        ca[j] = gs[2 * g + 1] * gmv[j];
-        cd[j] = btv[j] - gs[2 * g] * ca[j];
+        gn_coef(gs[2 * g], gs[2 * g + 1], gmv[j], btv[j], ca[j], cd[j]);
     }
     auto one = [&](int p, const uint4 &raw) __attribute__((always_inline)) {
         float f[8];
         unpack8<T>(raw, f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = f[j] * ca[j] + cd[j];
-            f[j] = act ? silu(v) : v;
-        }
+        affine8(f, ca, cd, act);
         if constexpr (Q8) {
             unsigned char *o8 = reinterpret_cast<unsigned char *>(y) + ((size_t)b * HW + p) * Cp + c0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] * qscale, -448.f), 448.f);
-            int w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-            *reinterpret_cast<uint2 *>(o8) = make_uint2((unsigned)w0, (unsigned)w1);
+            store8<T, true>(o8, f, qscale);
             if (c0 + 8 == C)
                 for (unsigned c = C; c < Cp; c += 8) *reinterpret_cast<uint2 *>(o8 + (c - c0)) = make_uint2(0u, 0u);
         } else {
-            *reinterpret_cast<uint4 *>(yb + (size_t)p * C) = pack8<T>(f);
+            store8<T, false>(yb + (size_t)p * C, f, 1.f);
         }
     };
 #pragma unroll
@@ -356,56 +438,9 @@ __global__ __launch_bounds__(256) void k_gn_coef_parts(unsigned HW, unsigned C, 
     gparts_to_moments(gs, red, b, HW, C, G, parts, nslab, R, mode, col_tile, eps);
     for (unsigned c = threadIdx.x; c < C; c += 256) {
         const unsigned g = c / cpg;
-        const float a = gs[2 * g + 1] * gamma[c];
-        *reinterpret_cast<float2 *>(out + ((size_t)b * C + c) * 2) = make_float2(a, beta[c] - gs[2 * g] * a);
-    }
-}
-
-// The same GroupNorm(+SiLU) with an OCP fp8 (e4m3) OUTPUT for the fp8 convolution path (k_gemm8q): y8[b][p][Cp] bytes, Cp = C rounded
-// up to a multiple of 128 (one 3x3 tap per 128-byte k-tile), padding channels written as zero; stored value = y * qscale (a power of
-// two: the tensor-wide E8M0 activation scale), saturated to +-448.
-template <class T>
-__global__ __launch_bounds__(256) void k_gn_apply_stats_fp8(const unsigned short *__restrict__ x, unsigned char *__restrict__ y8, unsigned HW,
-                                                            unsigned C, unsigned Cp, int G, const float *__restrict__ stats,
-                                                            const float *__restrict__ gamma, const float *__restrict__ beta, float eps, int act,
-                                                            float qscale)
-{
-    extern __shared__ float coef[];          // [C][2]
-    const unsigned b = blockIdx.y, tid = threadIdx.x, cpg = C / G;
-    const float *sb = stats + (size_t)b * G * 2;
-    const float n = (float)HW * (float)cpg;
-    for (unsigned c = tid; c < C; c += 256) {
-        const unsigned g = c / cpg;
-        const float mu = sb[2 * g] / n;
-        const float rstd = rsqrtf(fmaxf(sb[2 * g + 1] / n - mu * mu, 0.f) + eps);
-        const float a = rstd * gamma[c];
-        coef[2 * c] = a; coef[2 * c + 1] = beta[c] - mu * a;
-    }
-    __syncthreads();
-    const unsigned nch = C / 8, nchp = Cp / 8, per_img = HW * nchp;
-    const unsigned short *xb = x + (size_t)b * HW * C;
-    unsigned char *yb = y8 + (size_t)b * HW * Cp;
-    for (unsigned q = blockIdx.x * 256u + tid; q < per_img; q += gridDim.x * 256u) {
-        const unsigned p = q / nchp, ch = q - p * nchp;
-        uint2 o = make_uint2(0u, 0u);
-        if (ch < nch) {
-            const unsigned c0 = ch * 8;
-            float f[8];
-            unpack8<T>(*reinterpret_cast<const uint4 *>(xb + (size_t)p * C + c0), f);
-            const float4 *cf = reinterpret_cast<const float4 *>(coef + 2 * c0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 ab = cf[j];
-                float v0 = f[2 * j] * ab.x + ab.y, v1 = f[2 * j + 1] * ab.z + ab.w;
-                if (act) { v0 = silu(v0); v1 = silu(v1); }
-                f[2 * j] = fminf(fmaxf(v0 * qscale, -448.f), 448.f); f[2 * j + 1] = fminf(fmaxf(v1 * qscale, -448.f), 448.f);
-            }
-            int w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-            o = make_uint2((unsigned)w0, (unsigned)w1);
-        }
-        *reinterpret_cast<uint2 *>(yb + (size_t)q * 8) = o;
+        float a, d;
+        gn_coef(gs[2 * g], gs[2 * g + 1], gamma[c], beta[c], a, d);
+        *reinterpret_cast<float2 *>(out + ((size_t)b * C + c) * 2) = make_float2(a, d);
     }
 }
 
@@ -418,59 +453,30 @@ __global__ __launch_bounds__(256) void k_concat_add_stats(const unsigned short *
                                                           int HW, int nchb, int pix_per_block, int G, float *__restrict__ stats)
 {
     extern __shared__ float sp[];   // [lanes][nchb][16], then [G][2]
-    const int b = blockIdx.z, C = C1 + C2;
-    const int lanes = 256 / nchb;
-    const int tid = threadIdx.x;
-    const int cch = tid % nchb, pl = tid / nchb;
-    const int c0 = (blockIdx.y * nchb + cch) * 8;
+    const int b = blockIdx.z, C = C1 + C2, tid = threadIdx.x;
+    const SlabThread st(nchb, pix_per_block, HW);
+    const int c0 = st.c0;
     const size_t row0 = (size_t)b * HW;
     float s1[8], s2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    if (pl < lanes) {
-        const int p0 = blockIdx.x * pix_per_block;
-        const int p1 = min(p0 + pix_per_block, HW);
-        for (int p = p0 + pl; p < p1; p += lanes) {
+    if (st.live()) {
+        for (int p = st.p0 + st.pl; p < st.p1; p += st.lanes) {
             const size_t m = row0 + p;
-            uint4 v;
             float f[8];
-            if (c0 < C1) { v = *reinterpret_cast<const uint4 *>(a + m * C1 + c0); unpack8<T>(v, f); }
-            else {
-                v = *reinterpret_cast<const uint4 *>(bsrc + m * C2 + (c0 - C1));
-                unpack8<T>(v, f);
-                if (c) {
-                    float fc[8];
-                    unpack8<T>(*reinterpret_cast<const uint4 *>(c + m * C2 + (c0 - C1)), fc);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) f[j] += fc[j];
-                    v = pack8<T>(f);
-                    unpack8<T>(v, f);        // statistics of the values as stored
-                }
-            }
+            const uint4 v = concat_chunk<T>(a, C1, bsrc, c, C2, m, c0, f);
             if (out) *reinterpret_cast<uint4 *>(out + m * C + c0) = v;
 #pragma unroll
             for (int j = 0; j < 8; ++j) { s1[j] += f[j]; s2[j] += f[j] * f[j]; }
         }
-        float *o = sp + ((size_t)pl * nchb + cch) * 16;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { o[2 * j] = s1[j]; o[2 * j + 1] = s2[j]; }
     }
-    __syncthreads();
     float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    if (pl == 0) {
-        for (int l = 0; l < lanes; ++l) {
-            const float *o = sp + ((size_t)l * nchb + cch) * 16;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] += o[j];
-        }
-    }
+    slab_reduce16(sp, st, s1, s2, acc);
     __syncthreads();
     float *grp = sp;                 // [G][2] group sums of this block
     for (int i = tid; i < 2 * G; i += 256) grp[i] = 0.f;
     __syncthreads();
-    if (pl == 0) {
+    if (st.pl == 0) {
         const int cpg = C / G;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -496,23 +502,20 @@ __global__ __launch_bounds__(256) void k_concat_add_parts(const unsigned short *
                                                           int HW, int nchb, int pix_per_block, int cpg, float *__restrict__ parts)
 {
     extern __shared__ float sp[];   // [lanes][nchb][16]
-    const int b = blockIdx.z, C = C1 + C2;
-    const int lanes = 256 / nchb;
-    const int tid = threadIdx.x;
-    const int cch = tid % nchb, pl = tid / nchb;
-    const int c0 = (blockIdx.y * nchb + cch) * 8;
+    const int b = blockIdx.z, C = C1 + C2, tid = threadIdx.x;
+    const SlabThread st(nchb, pix_per_block, HW);
+    const int lanes = st.lanes, cch = st.cch, c0 = st.c0;
     const size_t row0 = (size_t)b * HW;
     float s1[8], s2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    if (pl < lanes) {
-        const int p0 = blockIdx.x * pix_per_block;
-        const int p1 = min(p0 + pix_per_block, HW);
+    if (st.live()) {
+        const int p1 = st.p1;
         const bool first = c0 < C1;
         const unsigned short *src = first ? a + c0 : bsrc + (c0 - C1);
         const unsigned short *src2 = (!first && c) ? c + (c0 - C1) : nullptr;
         const int ld = first ? C1 : C2;
-        for (int p = p0 + pl; p < p1; p += 4 * lanes) {
+        for (int p = st.p0 + st.pl; p < p1; p += 4 * lanes) {
             uint4 v[4], w[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -526,34 +529,16 @@ __global__ __launch_bounds__(256) void k_concat_add_parts(const unsigned short *
                 const int pp = p + u * lanes;
                 if (pp >= p1) break;
                 float f[8];
-                unpack8<T>(v[u], f);
-                if (src2) {
-                    float fc[8];
-                    unpack8<T>(w[u], fc);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) f[j] += fc[j];
-                    v[u] = pack8<T>(f);
-                    unpack8<T>(v[u], f);        // statistics of the values as stored
-                }
+                v[u] = concat_combine<T>(v[u], w[u], src2 != nullptr, f);
                 *reinterpret_cast<uint4 *>(out + (row0 + pp) * C + c0) = v[u];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { s1[j] += f[j]; s2[j] += f[j] * f[j]; }
             }
         }
-        float *o = sp + ((size_t)pl * nchb + cch) * 16;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { o[2 * j] = s1[j]; o[2 * j + 1] = s2[j]; }
     }
-    __syncthreads();
-    if (pl == 0) {
-        float acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-        for (int l = 0; l < lanes; ++l) {
-            const float *o = sp + ((size_t)l * nchb + cch) * 16;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] += o[j];
-        }
+    float acc[16];
+    slab_reduce16(sp, st, s1, s2, acc);
+    if (st.pl == 0) {
         float *o = sp + (size_t)cch * 16;          // lane 0's own slot: per-channel (sum, sum^2) of this slab for the group pass
 #pragma unroll
         for (int j = 0; j < 16; ++j) o[j] = acc[j];
@@ -571,10 +556,12 @@ __global__ __launch_bounds__(256) void k_concat_add_parts(const unsigned short *
 
 // ------------------------------------------------------------------------------------------ LayerNorm
 // one wave64 per token row; exact two-pass in registers (C <= 64*8*4).
-template <class T>
-__global__ __launch_bounds__(256) void k_layernorm(const unsigned short *__restrict__ x, unsigned short *__restrict__ y,
+// Q8: OCP fp8 (e4m3) output, 8 bytes stored per 16-byte input chunk; stored value = y * qscale (power of two: the tensor-wide E8M0
+// activation scale of the fp8 GEMM that consumes it), saturated to +-448.
+template <class T, bool Q8>
+__global__ __launch_bounds__(256) void k_layernorm(const unsigned short *__restrict__ x, void *__restrict__ y,
                                                    int64_t M, int C, const float *__restrict__ gamma,
-                                                   const float *__restrict__ beta, float eps)
+                                                   const float *__restrict__ beta, float eps, float qscale)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -607,54 +594,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const unsigned short *__restr
             float o[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (f[i][j] - mean) * rstd * gamma[ch * 8 + j] + beta[ch * 8 + j];
-            *reinterpret_cast<uint4 *>(y + row * C + ch * 8) = pack8<T>(o);
-        }
-    }
-}
-
-// LayerNorm with an OCP fp8 (e4m3) output: same wave-per-row two-pass kernel, 8 bytes stored per 16-byte input chunk; stored value =
-// y * qscale (power of two: the tensor-wide E8M0 activation scale of the fp8 GEMM that consumes it), saturated to +-448.
-template <class T>
-__global__ __launch_bounds__(256) void k_layernorm_fp8(const unsigned short *__restrict__ x, unsigned char *__restrict__ y8,
-                                                       int64_t M, int C, const float *__restrict__ gamma,
-                                                       const float *__restrict__ beta, float eps, float qscale)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const int nch = C / 8;
-    float f[4][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < nch) {
-            unpack8<T>(*reinterpret_cast<const uint4 *>(x + row * C + ch * 8), f[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += f[i][j];
-        }
-    }
-    const float mean = wave_sum_f(s) / (float)C;
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (lane + 64 * i < nch) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float d = f[i][j] - mean; v += d * d; }
-        }
-    const float rstd = rsqrtf(wave_sum_f(v) / (float)C + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < nch) {
-            float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                o[j] = fminf(fmaxf(((f[i][j] - mean) * rstd * gamma[ch * 8 + j] + beta[ch * 8 + j]) * qscale, -448.f), 448.f);
-            int w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(o[0], o[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(o[2], o[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(o[4], o[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(o[6], o[7], w1, true);
-            *reinterpret_cast<uint2 *>(y8 + row * C + ch * 8) = make_uint2((unsigned)w0, (unsigned)w1);
+            store8<T, Q8>(reinterpret_cast<unsigned char *>(y) + (row * C + ch * 8) * (Q8 ? 1 : 2), o, qscale);
         }
     }
 }
@@ -667,24 +607,12 @@ __global__ __launch_bounds__(256) void k_concat_add(const unsigned short *__rest
                                                     const unsigned short *__restrict__ b, const unsigned short *__restrict__ c,
                                                     int C2, unsigned short *__restrict__ out, unsigned total_chunks)
 {
-    const unsigned nch = (C1 + C2) / 8, n1 = C1 / 8;
+    const unsigned nch = (C1 + C2) / 8;
     for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < total_chunks; q += gridDim.x * 256u) {
         const size_t m = q / nch;
         const unsigned ch = q - (unsigned)m * nch;
-        uint4 v;
-        if (ch < n1) v = *reinterpret_cast<const uint4 *>(a + m * C1 + ch * 8);
-        else {
-            v = *reinterpret_cast<const uint4 *>(b + m * C2 + (ch - n1) * 8);
-            if (c) {
-                float fb[8], fc[8];
-                unpack8<T>(v, fb);
-                unpack8<T>(*reinterpret_cast<const uint4 *>(c + m * C2 + (ch - n1) * 8), fc);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fb[j] += fc[j];
-                v = pack8<T>(fb);
-            }
-        }
-        *reinterpret_cast<uint4 *>(out + m * (int64_t)(C1 + C2) + ch * 8) = v;
+        float f[8];
+        *reinterpret_cast<uint4 *>(out + m * (int64_t)(C1 + C2) + ch * 8) = concat_chunk<T>(a, C1, b, c, C2, m, (int)(ch * 8), f);
     }
 }
 
@@ -797,39 +725,82 @@ __global__ __launch_bounds__(256) void k_mask_composite(const float *__restrict_
     }
 }
 
-// slab plan of the GroupNorm statistics pass: channel slices of <= 256 16-byte chunks, pixel slabs sized for ~1-2k workgroups
-inline void gn_plan(int64_t B, int64_t HW, int C, int *nslab, int *ppb, int *ny, int *nchb)
+// ------------------------------------------------------------------------------------------ host side
+// The launches of entry point `fn`: f(T{}) with T = BF16 / F16 for the dtype code of the C ABI (every launch is written once, in a generic
+// lambda), then the launch check
+template <class F>
+inline int dn_for_type(const char *fn, int dtype, F &&f)
+{
+    if (dtype == DT_BF16) f(BF16{});
+    else if (dtype == DT_F16) f(F16{});
+    else { gc::set_error("%s: bad dtype", fn); return GC_EINVAL; }
+    return gc::check_launch(fn);
+}
+
+inline const unsigned short *in16(const void *p) { return static_cast<const unsigned short *>(p); }
+inline unsigned short *out16(void *p) { return static_cast<unsigned short *>(p); }
+
+// channel slices of the slab kernels: the fewest equal slices of <= 256 16-byte chunks
+inline void chan_slices(int C, int *ny, int *nchb)
 {
     const int nch = C / 8;
     int y = 1;
     while (nch % y != 0 || nch / y > 256) ++y;
     *ny = y; *nchb = nch / y;
-    const int lanes = 256 / *nchb;
-    // at most 32 slabs per image (keeps the finalize pass tiny), each at least `lanes` pixels
-    int p = (int)((HW + 31) / 32);
-    if (p < lanes) p = lanes;
-    (void)B;
-    *ppb = p; *nslab = (int)((HW + p - 1) / p);
+}
+
+struct SlabPlan { int nslab, ppb, ny, nchb; };      // pixel slabs of ppb pixels x ny channel slices of nchb chunks
+
+inline SlabPlan slab_plan(int64_t HW, int C, int ppb_wanted)
+{
+    SlabPlan p;
+    chan_slices(C, &p.ny, &p.nchb);
+    p.ppb = std::max(ppb_wanted, 256 / p.nchb);      // a slab has at least `lanes` pixels
+    p.nslab = (int)((HW + p.ppb - 1) / p.ppb);
+    return p;
+}
+// slab plan of the GroupNorm statistics pass: pixel slabs sized for ~1-2k workgroups, at most 32 slabs per image (keeps the finalize pass tiny)
+inline SlabPlan gn_plan(int64_t HW, int C) { return slab_plan(HW, C, (int)((HW + 31) / 32)); }
+// slab plan of gc_dn_concat_add_parts and of the apply pass that reads its partials: slabs of 16 / 32 pixels
+inline SlabPlan concat_parts_plan(int64_t HW, int C) { return slab_plan(HW, C, HW >= 4096 ? 32 : 16); }
+
+// grid and dynamic LDS bytes (the [lanes][nchb][16] staging of slab_reduce16) of a slab launch
+struct SlabGrid { dim3 grid; size_t lds; };
+inline SlabGrid slab_grid(int nslab, int ny, int64_t B, int nchb)
+{
+    return {dim3((unsigned)nslab, (unsigned)ny, (unsigned)B), sizeof(float) * 16 * (size_t)(256 / nchb) * nchb};
+}
+
+// stored = value * 2^(127 - byte); the MFMA multiplies by 2^(byte - 127)
+inline float qscale_of(int a_scale) { return exp2f((float)(127 - a_scale)); }
+
+// workgroups per image of k_gn_apply_stats: enough to fill the chip, few enough that the coefficient prologue (a few KB from L2 per
+// workgroup) stays small
+inline dim3 apply_stats_grid(int64_t per_img, int64_t B)
+{
+    const int64_t cap = std::max<int64_t>(1, (256 * 4 + B - 1) / B);
+    return dim3((unsigned)std::min((per_img + 255) / 256, cap), (unsigned)B);
 }
 
 inline unsigned ew_grid(int64_t items) { return (unsigned)std::min<int64_t>((items + 255) / 256, 256 * 8); }
 
-}  // namespace
+// k_gn_partial + k_gn_finalize: x -> per-channel partial sums `part` -> coefficients coef[B][C][2]
+template <class T>
+void launch_gn_partial_finalize(const void *x, int64_t B, int64_t HW, int C, int G, const float *gamma, const float *beta, float eps, const SlabPlan &p,
+                                float *part, float *coef, hipStream_t s)
+{
+    const SlabGrid sg = slab_grid(p.nslab, p.ny, B, p.nchb);
+    hipLaunchKernelGGL((k_gn_partial<T>), sg.grid, dim3(256), sg.lds, s, in16(x), (int)HW, C, p.nchb, p.ppb, part);
+    hipLaunchKernelGGL((k_gn_finalize<T>), dim3((unsigned)(B * G)), dim3(256), 0, s, in16(x), (int)HW, C, G, p.nslab, part, gamma, beta, eps, coef);
+}
 
-#define DN_DISPATCH(dtype, CALL_BF16, CALL_F16)                 \
-    do {                                                       \
-        if ((dtype) == DT_BF16) { CALL_BF16; }                 \
-        else if ((dtype) == DT_F16) { CALL_F16; }              \
-        else { gc::set_error("%s: bad dtype", __func__); return GC_EINVAL; } \
-    } while (0)
+}  // namespace
 
 extern "C" {
 
 size_t gc_dn_groupnorm_workspace_bytes(int64_t B, int64_t HW, int C)
 {
-    int nslab, ppb, ny, nchb;
-    gn_plan(B, HW, C, &nslab, &ppb, &ny, &nchb);
-    return sizeof(float) * 2 * (size_t)B * (size_t)C * (size_t)(nslab + 1);
+    return sizeof(float) * 2 * (size_t)B * (size_t)C * (size_t)(gn_plan(HW, C).nslab + 1);
 }
 
 int gc_dn_groupnorm(int dtype, const void *x, void *y, int64_t B, int64_t HW, int C, int G, const float *gamma,
@@ -842,32 +813,18 @@ int gc_dn_groupnorm(int dtype, const void *x, void *y, int64_t B, int64_t HW, in
     const int64_t Bsel = (act & 0x100) ? 1 : B;
     act &= 0xff;
     if ((C / G) % 2 == 0 && Bsel * HW * (int64_t)C <= ((int64_t)1 << 20) && Bsel * G >= 64) {      // <= 2 MB (the 8x8 maps): one launch, 5 vs 12 us
-        DN_DISPATCH(dtype,
-                    hipLaunchKernelGGL((k_gn_small<BF16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x,
-                                       (unsigned short *)y, (int)HW, C, G, gamma, beta, eps, act),
-                    hipLaunchKernelGGL((k_gn_small<F16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x,
-                                       (unsigned short *)y, (int)HW, C, G, gamma, beta, eps, act));
-        return gc::check_launch("gc_dn_groupnorm");
+        return dn_for_type(__func__, dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_gn_small<decltype(t)>), dim3((unsigned)(B * G)), dim3(256), 0, s, in16(x), out16(y), (int)HW, C, G, gamma, beta, eps, act);
+        });
     }
-    int nslab, ppb, ny, nchb;
-    gn_plan(B, HW, C, &nslab, &ppb, &ny, &nchb);
-    float *part = stats_ws, *coef = stats_ws + 2 * (size_t)B * C * nslab;
-    const int lanes = 256 / nchb;
-    dim3 grid((unsigned)nslab, ny, (unsigned)B);
-    const size_t lds = sizeof(float) * 16 * (size_t)lanes * nchb;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_partial<BF16>), grid, dim3(256), lds, s, (const unsigned short *)x, (int)HW, C, nchb, ppb, part),
-                hipLaunchKernelGGL((k_gn_partial<F16>), grid, dim3(256), lds, s, (const unsigned short *)x, (int)HW, C, nchb, ppb, part));
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_finalize<BF16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x, (int)HW, C, G, nslab, part, gamma, beta, eps, coef),
-                hipLaunchKernelGGL((k_gn_finalize<F16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x, (int)HW, C, G, nslab, part, gamma, beta, eps, coef));
+    const SlabPlan p = gn_plan(HW, C);
+    float *part = stats_ws, *coef = stats_ws + 2 * (size_t)B * C * p.nslab;
     const int64_t chunks = B * HW * (C / 8);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_apply<BF16>), dim3(ew_grid(chunks)), dim3(256), 0, s, (const unsigned short *)x,
-                                   (unsigned short *)y, (unsigned)HW, (unsigned)C, coef, act, (unsigned)chunks),
-                hipLaunchKernelGGL((k_gn_apply<F16>), dim3(ew_grid(chunks)), dim3(256), 0, s, (const unsigned short *)x,
-                                   (unsigned short *)y, (unsigned)HW, (unsigned)C, coef, act, (unsigned)chunks));
-    return gc::check_launch("gc_dn_groupnorm");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        launch_gn_partial_finalize<decltype(t)>(x, B, HW, C, G, gamma, beta, eps, p, part, coef, s);
+        hipLaunchKernelGGL((k_gn_apply<decltype(t)>), dim3(ew_grid(chunks)), dim3(256), 0, s, in16(x), out16(y), (unsigned)HW, (unsigned)C, coef, act,
+                           (unsigned)chunks);
+    });
 }
 
 int gc_dn_groupnorm_coef(int dtype, const void *x, int64_t B, int64_t HW, int C, int G, const float *gamma, const float *beta, float eps,
@@ -875,41 +832,22 @@ int gc_dn_groupnorm_coef(int dtype, const void *x, int64_t B, int64_t HW, int C,
 {
     GC_REQUIRE(C % 8 == 0 && C % G == 0 && stats_ws && coef, "groupnorm_coef: C must be a multiple of 8 and of G; workspace and output required");
     GC_REQUIRE(C / G <= 256 && B * HW * (C / 8) < (int64_t)1 << 31, "groupnorm_coef: group too wide / tensor too large");
-    hipStream_t s = gc::S(stream);
-    int nslab, ppb, ny, nchb;
-    gn_plan(B, HW, C, &nslab, &ppb, &ny, &nchb);
-    float *part = stats_ws;
-    const int lanes = 256 / nchb;
-    dim3 grid((unsigned)nslab, ny, (unsigned)B);
-    const size_t lds = sizeof(float) * 16 * (size_t)lanes * nchb;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_partial<BF16>), grid, dim3(256), lds, s, (const unsigned short *)x, (int)HW, C, nchb, ppb, part),
-                hipLaunchKernelGGL((k_gn_partial<F16>), grid, dim3(256), lds, s, (const unsigned short *)x, (int)HW, C, nchb, ppb, part));
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_finalize<BF16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x, (int)HW, C, G, nslab, part, gamma, beta, eps, coef),
-                hipLaunchKernelGGL((k_gn_finalize<F16>), dim3((unsigned)(B * G)), dim3(256), 0, s, (const unsigned short *)x, (int)HW, C, G, nslab, part, gamma, beta, eps, coef));
-    return gc::check_launch("gc_dn_groupnorm_coef");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        launch_gn_partial_finalize<decltype(t)>(x, B, HW, C, G, gamma, beta, eps, gn_plan(HW, C), stats_ws, coef, gc::S(stream));
+    });
 }
 
 int gc_dn_groupnorm_apply(int dtype, const void *x, void *y, int64_t B, int64_t HW, int C, int G, const float *gamma,
                           const float *beta, float eps, int act, const float *group_stats, void *stream)
 {
-    const float *chan_stats = group_stats;
-    GC_REQUIRE(C % 8 == 0 && C % G == 0 && chan_stats && gamma && beta, "groupnorm_apply: C must be a multiple of 8 and of G; statistics required");
+    GC_REQUIRE(C % 8 == 0 && C % G == 0 && group_stats && gamma && beta, "groupnorm_apply: C must be a multiple of 8 and of G; statistics required");
     GC_REQUIRE(HW * (int64_t)(C / 8) < (int64_t)1 << 31 && B <= 65535, "groupnorm_apply: tensor too large");
-    const int64_t per_img = HW * (C / 8);
-    // enough workgroups per image to fill the chip, few enough that the coefficient prologue (a few KB from L2 per workgroup) stays small
-    int64_t gx = (per_img + 255) / 256;
-    const int64_t cap = std::max<int64_t>(1, (256 * 4 + B - 1) / B);
-    if (gx > cap) gx = cap;
     const size_t lds = sizeof(float) * 2 * (size_t)C;
-    dim3 grid((unsigned)gx, (unsigned)B);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_apply_stats<BF16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, (unsigned short *)y,
-                                   (unsigned)HW, (unsigned)C, G, chan_stats, gamma, beta, eps, act),
-                hipLaunchKernelGGL((k_gn_apply_stats<F16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, (unsigned short *)y,
-                                   (unsigned)HW, (unsigned)C, G, chan_stats, gamma, beta, eps, act));
-    return gc::check_launch("gc_dn_groupnorm_apply");
+    const dim3 grid = apply_stats_grid(HW * (C / 8), B);
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_gn_apply_stats<decltype(t), false>), grid, dim3(256), lds, gc::S(stream), in16(x), y, (unsigned)HW, (unsigned)C, 0u, G,
+                           group_stats, gamma, beta, eps, act, 1.f);
+    });
 }
 
 int gc_dn_groupnorm_apply_fp8(int dtype, const void *x, void *y8, int64_t B, int64_t HW, int C, int C_padded, int G, const float *gamma,
@@ -918,30 +856,21 @@ int gc_dn_groupnorm_apply_fp8(int dtype, const void *x, void *y8, int64_t B, int
     GC_REQUIRE(C % 8 == 0 && C % G == 0 && group_stats && gamma && beta, "groupnorm_apply_fp8: C must be a multiple of 8 and of G; statistics required");
     GC_REQUIRE(C_padded >= C && C_padded % 128 == 0, "groupnorm_apply_fp8: padded channel count must be a multiple of 128");
     GC_REQUIRE(HW * (int64_t)(C_padded / 8) < (int64_t)1 << 31 && B <= 65535 && a_scale > 0 && a_scale < 255, "groupnorm_apply_fp8: bad size / scale");
-    const int64_t per_img = HW * (C_padded / 8);
-    int64_t gx = (per_img + 255) / 256;
-    const int64_t cap = std::max<int64_t>(1, (256 * 4 + B - 1) / B);
-    if (gx > cap) gx = cap;
     const size_t lds = sizeof(float) * 2 * (size_t)C;
-    const float qscale = exp2f((float)(127 - a_scale));          // stored = value * 2^(127 - byte); the MFMA multiplies by 2^(byte - 127)
-    dim3 grid((unsigned)gx, (unsigned)B);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_apply_stats_fp8<BF16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, (unsigned char *)y8,
-                                   (unsigned)HW, (unsigned)C, (unsigned)C_padded, G, group_stats, gamma, beta, eps, act, qscale),
-                hipLaunchKernelGGL((k_gn_apply_stats_fp8<F16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, (unsigned char *)y8,
-                                   (unsigned)HW, (unsigned)C, (unsigned)C_padded, G, group_stats, gamma, beta, eps, act, qscale));
-    return gc::check_launch("gc_dn_groupnorm_apply_fp8");
+    const dim3 grid = apply_stats_grid(HW * (C_padded / 8), B);
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_gn_apply_stats<decltype(t), true>), grid, dim3(256), lds, gc::S(stream), in16(x), y8, (unsigned)HW, (unsigned)C,
+                           (unsigned)C_padded, G, group_stats, gamma, beta, eps, act, qscale_of(a_scale));
+    });
 }
 
 int gc_dn_layernorm(int dtype, const void *x, void *y, int64_t M, int C, const float *gamma, const float *beta,
                     float eps, void *stream)
 {
     GC_REQUIRE(C % 8 == 0 && C <= 2048, "layernorm: C must be a multiple of 8 and <= 2048");
-    dim3 grid((unsigned)((M + 3) / 4));
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_layernorm<BF16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y, M, C, gamma, beta, eps),
-                hipLaunchKernelGGL((k_layernorm<F16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y, M, C, gamma, beta, eps));
-    return gc::check_launch("gc_dn_layernorm");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_layernorm<decltype(t), false>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, gc::S(stream), in16(x), y, M, C, gamma, beta, eps, 1.f);
+    });
 }
 
 int gc_dn_layernorm_fp8(int dtype, const void *x, void *y8, int64_t M, int C, const float *gamma, const float *beta,
@@ -949,41 +878,31 @@ int gc_dn_layernorm_fp8(int dtype, const void *x, void *y8, int64_t M, int C, co
 {
     GC_REQUIRE(C % 16 == 0 && C <= 2048, "layernorm_fp8: C must be a multiple of 16 and <= 2048");
     GC_REQUIRE(a_scale > 0 && a_scale < 255 && M > 0 && x && y8 && gamma && beta, "layernorm_fp8: bad scale / null argument");
-    const float qscale = exp2f((float)(127 - a_scale));
-    dim3 grid((unsigned)((M + 3) / 4));
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_layernorm_fp8<BF16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned char *)y8, M, C, gamma, beta, eps, qscale),
-                hipLaunchKernelGGL((k_layernorm_fp8<F16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned char *)y8, M, C, gamma, beta, eps, qscale));
-    return gc::check_launch("gc_dn_layernorm_fp8");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_layernorm<decltype(t), true>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, gc::S(stream), in16(x), y8, M, C, gamma, beta, eps,
+                           qscale_of(a_scale));
+    });
 }
 
 int gc_dn_concat_add(int dtype, const void *a, int C1, const void *b, const void *c, int C2, void *out, int64_t M, int64_t rows_per_batch,
                      float *group_stats, int gn_groups, void *stream)
 {
     GC_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0, "concat: channel counts must be multiples of 8");
-    float *chan_stats = group_stats;
-    if (chan_stats) {      // copy + per-(batch, group) sums of the output, added into the caller-zeroed group_stats[B][gn_groups][2]
+    if (group_stats) {      // copy + per-(batch, group) sums of the output, added into the caller-zeroed group_stats[B][gn_groups][2]
         GC_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && M / rows_per_batch <= 65535, "concat: M must be B * rows_per_batch");
         GC_REQUIRE(gn_groups >= 1 && gn_groups <= 64 && (C1 + C2) % gn_groups == 0, "concat: gn_groups must divide C1 + C2");
-        int nslab, ppb, ny, nchb;
-        gn_plan(M / rows_per_batch, rows_per_batch, C1 + C2, &nslab, &ppb, &ny, &nchb);
-        const int lanes = 256 / nchb;
-        dim3 grid((unsigned)nslab, ny, (unsigned)(M / rows_per_batch));
-        const size_t lds = sizeof(float) * 16 * (size_t)lanes * nchb;
-        DN_DISPATCH(dtype,
-                    hipLaunchKernelGGL((k_concat_add_stats<BF16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)a, C1,
-                                       (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (int)rows_per_batch, nchb, ppb, gn_groups, chan_stats),
-                    hipLaunchKernelGGL((k_concat_add_stats<F16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)a, C1,
-                                       (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (int)rows_per_batch, nchb, ppb, gn_groups, chan_stats));
-        return gc::check_launch("gc_dn_concat_add");
+        const SlabPlan p = gn_plan(rows_per_batch, C1 + C2);
+        const SlabGrid sg = slab_grid(p.nslab, p.ny, M / rows_per_batch, p.nchb);
+        return dn_for_type(__func__, dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_concat_add_stats<decltype(t)>), sg.grid, dim3(256), sg.lds, gc::S(stream), in16(a), C1, in16(b), in16(c), C2, out16(out),
+                               (int)rows_per_batch, p.nchb, p.ppb, gn_groups, group_stats);
+        });
     }
     const int64_t chunks = M * ((C1 + C2) / 8);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_concat_add<BF16>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), (const unsigned short *)a, C1,
-                                   (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (unsigned)chunks),
-                hipLaunchKernelGGL((k_concat_add<F16>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), (const unsigned short *)a, C1,
-                                   (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (unsigned)chunks));
-    return gc::check_launch("gc_dn_concat_add");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_concat_add<decltype(t)>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), in16(a), C1, in16(b), in16(c), C2, out16(out),
+                           (unsigned)chunks);
+    });
 }
 
 int gc_dn_groupnorm_coef_parts(int64_t B, int64_t HW, int C, int G, const float *gamma, const float *beta, float eps, const float *parts,
@@ -996,23 +915,18 @@ int gc_dn_groupnorm_coef_parts(int64_t B, int64_t HW, int C, int G, const float 
     return gc::check_launch("gc_dn_groupnorm_coef_parts");
 }
 
-static void concat_parts_plan(int64_t HW, int C, int *nslab, int *ppb, int *ny, int *nchb);
-
 int gc_dn_groupnorm_apply_parts(int dtype, const void *x, void *y, int64_t B, int64_t HW, int C, int G, const float *gamma, const float *beta,
                                 float eps, int act, const float *parts, int64_t rows_per_slab, int nslab, int slab_mode, int col_tile, void *stream)
 {
     GC_REQUIRE(C % 8 == 0 && C % G == 0 && G <= 128 && parts && gamma && beta, "groupnorm_apply_parts: C must be a multiple of 8 and of G; partials required");
     GC_REQUIRE(HW * (int64_t)C < (int64_t)1 << 31 && B * HW < (int64_t)1 << 31 && B <= 65535 && rows_per_slab > 0 && nslab > 0 && col_tile > 0,
                "groupnorm_apply_parts: bad sizes");
-    int ns, ppb, ny, nchb;                      // pixel slabs of 16 / 32 pixels x channel slices of <= 256 chunks (the plan of gc_dn_concat_add_parts)
-    concat_parts_plan(HW, C, &ns, &ppb, &ny, &nchb);
-    dim3 grid((unsigned)ns, ny, (unsigned)B);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_apply_parts<BF16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y,
-                                   (unsigned)HW, (unsigned)C, (unsigned)G, parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, nchb, ppb),
-                hipLaunchKernelGGL((k_gn_apply_parts<F16>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y,
-                                   (unsigned)HW, (unsigned)C, (unsigned)G, parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, nchb, ppb));
-    return gc::check_launch("gc_dn_groupnorm_apply_parts");
+    const SlabPlan p = concat_parts_plan(HW, C);      // the walk of gc_dn_concat_add_parts; `nslab` / `rows_per_slab` describe the PRODUCER's partials
+    const dim3 grid = slab_grid(p.nslab, p.ny, B, p.nchb).grid;
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_gn_apply_parts<decltype(t), false>), grid, dim3(256), 0, gc::S(stream), in16(x), out16(y), (unsigned)HW, (unsigned)C, (unsigned)G,
+                           parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, p.nchb, p.ppb, 0u, 1.f);
+    });
 }
 
 int gc_dn_groupnorm_apply_parts_fp8(int dtype, const void *x, void *y8, int64_t B, int64_t HW, int C, int C_padded, int G, const float *gamma,
@@ -1023,40 +937,22 @@ int gc_dn_groupnorm_apply_parts_fp8(int dtype, const void *x, void *y8, int64_t 
     GC_REQUIRE(C_padded >= C && C_padded % 128 == 0 && a_scale > 0 && a_scale < 255, "groupnorm_apply_parts_fp8: padded channel count % 128 == 0; E8M0 scale byte");
     GC_REQUIRE(HW * (int64_t)C_padded < (int64_t)1 << 31 && B * HW < (int64_t)1 << 31 && B <= 65535 && rows_per_slab > 0 && nslab > 0 && col_tile > 0,
                "groupnorm_apply_parts_fp8: bad sizes");
-    int ns, ppb, ny, nchb;
-    concat_parts_plan(HW, C, &ns, &ppb, &ny, &nchb);
-    dim3 grid((unsigned)ns, ny, (unsigned)B);
-    const float qscale = exp2f((float)(127 - a_scale));
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_gn_apply_parts<BF16, true>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y8,
-                                   (unsigned)HW, (unsigned)C, (unsigned)G, parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, nchb, ppb,
-                                   (unsigned)C_padded, qscale),
-                hipLaunchKernelGGL((k_gn_apply_parts<F16, true>), grid, dim3(256), 0, gc::S(stream), (const unsigned short *)x, (unsigned short *)y8,
-                                   (unsigned)HW, (unsigned)C, (unsigned)G, parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, nchb, ppb,
-                                   (unsigned)C_padded, qscale));
-    return gc::check_launch("gc_dn_groupnorm_apply_parts_fp8");
-}
-
-static void concat_parts_plan(int64_t HW, int C, int *nslab, int *ppb, int *ny, int *nchb)
-{
-    const int nch = C / 8;
-    int y = 1;
-    while (nch % y != 0 || nch / y > 256) ++y;
-    *ny = y; *nchb = nch / y;
-    const int lanes = 256 / *nchb;
-    int p = HW >= 4096 ? 32 : 16;
-    if (p < lanes) p = lanes;
-    *ppb = p; *nslab = (int)((HW + p - 1) / p);
+    const SlabPlan p = concat_parts_plan(HW, C);
+    const dim3 grid = slab_grid(p.nslab, p.ny, B, p.nchb).grid;
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_gn_apply_parts<decltype(t), true>), grid, dim3(256), 0, gc::S(stream), in16(x), out16(y8), (unsigned)HW, (unsigned)C, (unsigned)G,
+                           parts, nslab, (unsigned)rows_per_slab, slab_mode, (unsigned)col_tile, gamma, beta, eps, act, p.nchb, p.ppb, (unsigned)C_padded,
+                           qscale_of(a_scale));
+    });
 }
 
 int gc_dn_concat_parts_layout(int64_t rows_per_batch, int C, int gn_groups, int64_t *rows_per_slab, int *nslab, int *col_tile)
 {
     GC_REQUIRE(rows_per_slab && nslab && col_tile && rows_per_batch > 0 && C % 8 == 0 && gn_groups >= 1, "concat_parts_layout: bad arguments");
     *rows_per_slab = 0; *nslab = 0; *col_tile = 0;
-    int ns, ppb, ny, nchb;
-    concat_parts_plan(rows_per_batch, C, &ns, &ppb, &ny, &nchb);
-    if (C % gn_groups != 0 || (nchb * 8) % (C / gn_groups) != 0 || nchb * 8 / (C / gn_groups) > 256) return GC_OK;     // a channel slice must hold whole groups
-    *rows_per_slab = ppb; *nslab = ns; *col_tile = nchb * 8;
+    const SlabPlan p = concat_parts_plan(rows_per_batch, C);
+    if (C % gn_groups != 0 || (p.nchb * 8) % (C / gn_groups) != 0 || p.nchb * 8 / (C / gn_groups) > 256) return GC_OK;     // a channel slice must hold whole groups
+    *rows_per_slab = p.ppb; *nslab = p.nslab; *col_tile = p.nchb * 8;
     return GC_OK;
 }
 
@@ -1067,62 +963,48 @@ int gc_dn_concat_add_parts(int dtype, const void *a, int C1, const void *b, cons
     const int cpg = (C1 + C2) / gn_groups;
     GC_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && parts && out, "concat_parts: channel counts must be multiples of 8; output and partials buffer required");
     GC_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && M / rows_per_batch <= 65535, "concat_parts: M must be B * rows_per_batch");
-    int nslab, ppb, ny, nchb;
-    concat_parts_plan(rows_per_batch, C1 + C2, &nslab, &ppb, &ny, &nchb);
-    GC_REQUIRE((nchb * 8) % cpg == 0 && nchb * 8 / cpg <= 256, "concat_parts: a channel slice must hold whole groups (see gc_dn_concat_parts_layout)");
-    const int lanes = 256 / nchb;
-    dim3 grid((unsigned)nslab, ny, (unsigned)(M / rows_per_batch));
-    const size_t lds = sizeof(float) * 16 * (size_t)lanes * nchb;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_concat_add_parts<BF16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)a, C1,
-                                   (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (int)rows_per_batch, nchb, ppb, cpg, parts),
-                hipLaunchKernelGGL((k_concat_add_parts<F16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)a, C1,
-                                   (const unsigned short *)b, (const unsigned short *)c, C2, (unsigned short *)out, (int)rows_per_batch, nchb, ppb, cpg, parts));
-    return gc::check_launch("gc_dn_concat_add_parts");
+    const SlabPlan p = concat_parts_plan(rows_per_batch, C1 + C2);
+    GC_REQUIRE((p.nchb * 8) % cpg == 0 && p.nchb * 8 / cpg <= 256, "concat_parts: a channel slice must hold whole groups (see gc_dn_concat_parts_layout)");
+    const SlabGrid sg = slab_grid(p.nslab, p.ny, M / rows_per_batch, p.nchb);
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_concat_add_parts<decltype(t)>), sg.grid, dim3(256), sg.lds, gc::S(stream), in16(a), C1, in16(b), in16(c), C2, out16(out),
+                           (int)rows_per_batch, p.nchb, p.ppb, cpg, parts);
+    });
 }
 
 int gc_dn_group_stats(int dtype, const void *x, int64_t B, int64_t HW, int C, int G, float *group_stats, void *stream)
 {
     GC_REQUIRE(C % 8 == 0 && G >= 1 && G <= 64 && C % G == 0 && group_stats && B <= 65535, "group_stats: C % 8 == 0, G | C, statistics buffer required");
-    int nslab, ppb, ny, nchb;
-    gn_plan(B, HW, C, &nslab, &ppb, &ny, &nchb);
-    const int lanes = 256 / nchb;
-    dim3 grid((unsigned)nslab, ny, (unsigned)B);
-    const size_t lds = sizeof(float) * 16 * (size_t)lanes * nchb;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_concat_add_stats<BF16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, C, (const unsigned short *)nullptr,
-                                   (const unsigned short *)nullptr, 0, (unsigned short *)nullptr, (int)HW, nchb, ppb, G, group_stats),
-                hipLaunchKernelGGL((k_concat_add_stats<F16>), grid, dim3(256), lds, gc::S(stream), (const unsigned short *)x, C, (const unsigned short *)nullptr,
-                                   (const unsigned short *)nullptr, 0, (unsigned short *)nullptr, (int)HW, nchb, ppb, G, group_stats));
-    return gc::check_launch("gc_dn_group_stats");
+    const SlabPlan p = gn_plan(HW, C);
+    const SlabGrid sg = slab_grid(p.nslab, p.ny, B, p.nchb);
+    const unsigned short *none = nullptr;
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_concat_add_stats<decltype(t)>), sg.grid, dim3(256), sg.lds, gc::S(stream), in16(x), C, none, none, 0, (unsigned short *)nullptr,
+                           (int)HW, p.nchb, p.ppb, G, group_stats);
+    });
 }
 
 int gc_dn_axpby(int dtype, const void *a, float sa, const void *b, float sb, int act, void *out, int64_t n, void *stream)
 {
     GC_REQUIRE(n % 8 == 0, "axpby: element count must be a multiple of 8");
     const int64_t chunks = n / 8;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_axpby<BF16>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), (const unsigned short *)a, sa,
-                                   (const unsigned short *)b, sb, act, (unsigned short *)out, chunks),
-                hipLaunchKernelGGL((k_axpby<F16>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), (const unsigned short *)a, sa,
-                                   (const unsigned short *)b, sb, act, (unsigned short *)out, chunks));
-    return gc::check_launch("gc_dn_axpby");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_axpby<decltype(t)>), dim3(ew_grid(chunks)), dim3(256), 0, gc::S(stream), in16(a), sa, in16(b), sb, act, out16(out), chunks);
+    });
 }
 
 int gc_dn_cast_f32(int dtype, const float *a, int act, void *out, int64_t n, void *stream)
 {
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_cast_f32<BF16>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), a, act, (unsigned short *)out, n),
-                hipLaunchKernelGGL((k_cast_f32<F16>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), a, act, (unsigned short *)out, n));
-    return gc::check_launch("gc_dn_cast_f32");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_cast_f32<decltype(t)>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), a, act, out16(out), n);
+    });
 }
 
 int gc_dn_softmax_rows(int dtype, void *s, int64_t M, int64_t N, int64_t ld, float scale, void *stream)
 {
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_softmax_rows<BF16>), dim3((unsigned)M), dim3(256), 0, gc::S(stream), (unsigned short *)s, N, ld, scale),
-                hipLaunchKernelGGL((k_softmax_rows<F16>), dim3((unsigned)M), dim3(256), 0, gc::S(stream), (unsigned short *)s, N, ld, scale));
-    return gc::check_launch("gc_dn_softmax_rows");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_softmax_rows<decltype(t)>), dim3((unsigned)M), dim3(256), 0, gc::S(stream), out16(s), N, ld, scale);
+    });
 }
 
 int gc_dn_depth_to_disparity(int dtype, const float *depth, int64_t HW, void *out, unsigned *max_ws, void *stream)
@@ -1131,10 +1013,9 @@ int gc_dn_depth_to_disparity(int dtype, const float *depth, int64_t HW, void *ou
     if (hipMemsetAsync(max_ws, 0, 4, s) != hipSuccess) return GC_ELAUNCH;
     // 64 workgroups: the maximum ends in ONE word, and 4096 waves doing an atomicMax on it cost 48 us (~12 ns each), 256 cost ~3 us
     hipLaunchKernelGGL(k_disp_max, dim3(std::min<unsigned>(ew_grid(HW), 64u)), dim3(256), 0, s, depth, HW, max_ws);
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_disp_write<BF16>), dim3(ew_grid(HW)), dim3(256), 0, s, depth, HW, max_ws, (unsigned short *)out),
-                hipLaunchKernelGGL((k_disp_write<F16>), dim3(ew_grid(HW)), dim3(256), 0, s, depth, HW, max_ws, (unsigned short *)out));
-    return gc::check_launch("gc_dn_depth_to_disparity");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_disp_write<decltype(t)>), dim3(ew_grid(HW)), dim3(256), 0, s, depth, HW, max_ws, out16(out));
+    });
 }
 
 int gc_dn_mask_composite(const float *edited, int ld_e, const float *unedited, const float *mask, float *out, int64_t HW,
@@ -1152,10 +1033,10 @@ int gc_dn_cfg_ddim_step(int dtype, const float *eps, int ld_eps, int64_t frames,
     const float c_x = sqrtf(alpha_prev / alpha_t);
     const float c_e = sqrtf(1.f - alpha_prev) - sqrtf(alpha_prev * (1.f - alpha_t) / alpha_t);
     const int64_t n = frames * HW;
-    DN_DISPATCH(dtype,
-                hipLaunchKernelGGL((k_cfg_ddim<BF16>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), eps, ld_eps, frames, HW, guidance, cfg, c_x, c_e, latents, (unsigned short *)xin, nrep),
-                hipLaunchKernelGGL((k_cfg_ddim<F16>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), eps, ld_eps, frames, HW, guidance, cfg, c_x, c_e, latents, (unsigned short *)xin, nrep));
-    return gc::check_launch("gc_dn_cfg_ddim_step");
+    return dn_for_type(__func__, dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_cfg_ddim<decltype(t)>), dim3(ew_grid(n)), dim3(256), 0, gc::S(stream), eps, ld_eps, frames, HW, guidance, cfg, c_x, c_e, latents,
+                           out16(xin), nrep);
+    });
 }
 
 }  // extern "C"

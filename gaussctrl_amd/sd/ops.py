@@ -381,11 +381,16 @@ def conv3x3(x, w, bias=None, stride=1, upsample=False, rowvec=None, ld_rowvec=No
 _gn_ws = {}
 
 
+def _bhwc(x):
+    """(B, HW, C) of a channels-last x [B, ..., C]"""
+    B, Cc = x.shape[0], x.shape[-1]
+    return B, x.numel() // (B * Cc), Cc
+
+
 def groupnorm(x, gamma, beta, groups, eps, silu, parts=None):
     """x [B,H,W,C] (or [B,HW,C]).  parts: the ChanParts x's producer left -> ONE launch (gc_dn_groupnorm_apply_parts) instead of three."""
     _gpu(x)
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     if OPTIONS.ablate:
         z = _ablated("gn", x.shape, x.dtype, x.device)
         if z is not None:
@@ -411,12 +416,10 @@ def groupnorm(x, gamma, beta, groups, eps, silu, parts=None):
 def groupnorm_apply(x, group_stats, gamma, beta, groups, eps, silu):
     """GroupNorm(+SiLU) of x [B,H,W,C] (or [B,HW,C]) from the per-(batch, group) sums [B, G, 2] its producer accumulated: ONE launch."""
     _gpu(x, group_stats)
-    chan_stats = group_stats
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     y = torch.empty_like(x)
     L.check(L.lib().gc_dn_groupnorm_apply(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta),
-                                          C.c_float(eps), int(silu), _p(chan_stats), _stream()), "gc_dn_groupnorm_apply")
+                                          C.c_float(eps), int(silu), _p(group_stats), _stream()), "gc_dn_groupnorm_apply")
     return y
 
 
@@ -427,8 +430,7 @@ def pad128(c):
 def groupnorm_apply_fp8(x, group_stats, gamma, beta, groups, eps, silu, a_scale=127):
     """GroupNorm(+SiLU) with an e4m3 output [B,H,W,pad128(C)] (uint8) for conv3x3_fp8; a_scale = E8M0 byte of the tensor-wide scale."""
     _gpu(x, group_stats)
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     Cp = pad128(Cc)
     y = torch.empty(x.shape[:-1] + (Cp,), dtype=torch.uint8, device=x.device)
     L.check(L.lib().gc_dn_groupnorm_apply_fp8(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, Cp, groups, _p(gamma), _p(beta),
@@ -439,8 +441,7 @@ def groupnorm_apply_fp8(x, group_stats, gamma, beta, groups, eps, silu, a_scale=
 def group_stats(x, gs):
     """per-(batch, GroupNorm group) (sum, sum^2) of x [B, ..., C], ADDED into the zeroed fp32 gs [B, G, 2] (one streaming launch)."""
     _gpu(x, gs)
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     L.check(L.lib().gc_dn_group_stats(_dt(x), _p(x), C.c_int64(B), C.c_int64(HW), Cc, gs.shape[-2], _p(gs), _stream()), "gc_dn_group_stats")
     return gs
 
@@ -448,9 +449,7 @@ def group_stats(x, gs):
 def groupnorm_apply_parts_fp8(x, parts, gamma, beta, groups, eps, silu, a_scale=127):
     """GroupNorm(+SiLU) -> e4m3 [B,H,W,pad128(C)] in ONE launch from the ChanParts x's producer left (gc_dn_groupnorm_apply_parts_fp8)."""
     _gpu(x)
-    Cc = x.shape[-1]
-    B = x.shape[0]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     Cp = pad128(Cc)
     assert parts.groups == groups
     y = torch.empty(x.shape[:-1] + (Cp,), dtype=torch.uint8, device=x.device)
@@ -463,10 +462,7 @@ def groupnorm_apply_parts_fp8(x, parts, gamma, beta, groups, eps, silu, a_scale=
 def groupnorm_fp8(x, gamma, beta, groups, eps, silu, a_scale=127):
     """Stand-alone GroupNorm(+SiLU) -> e4m3: one statistics launch (gc_dn_group_stats) + the quantising apply."""
     _gpu(x)
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
-    gs = torch.zeros(B, groups, 2, dtype=torch.float32, device=x.device)
-    L.check(L.lib().gc_dn_group_stats(_dt(x), _p(x), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gs), _stream()), "gc_dn_group_stats")
+    gs = group_stats(x, torch.zeros(x.shape[0], groups, 2, dtype=torch.float32, device=x.device))
     return groupnorm_apply_fp8(x, gs, gamma, beta, groups, eps, silu, a_scale)
 
 
@@ -683,8 +679,7 @@ def groupnorm_coef(x, gamma, beta, groups, eps, parts=None):
     """x [B,HW,C] -> coef fp32 [B,C,2]: GroupNorm(x)[b,:,c] = x * coef[b,c,0] + coef[b,c,1] (the statistics passes of groupnorm only;
     one tiny launch from the producer's ChanParts when given)"""
     _gpu(x)
-    B, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * Cc)
+    B, HW, Cc = _bhwc(x)
     if parts is not None and "gn" not in OPTIONS.ablate:
         coef = torch.empty(B, Cc, 2, dtype=torch.float32, device=x.device)
         L.check(L.lib().gc_dn_groupnorm_coef_parts(C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta), C.c_float(eps), _p(parts.buf),

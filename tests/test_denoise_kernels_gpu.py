@@ -147,7 +147,8 @@ def _parts_sums(parts, b, HW, cpg):
                                                ("conv", 6, 16, 1280, 1280),      # split-K: the reduce-epilogue kernel leaves the partials
                                                ("conv", 2, 16, 640, 1280), ("conv_in", 6, 64, 8, 320), ("down", 6, 64, 320, 320),
                                                ("linear", 6, 32, 640, 640), ("linear", 6, 16, 1280, 1280), ("linear", 2, 64, 320, 320),
-                                               ("concat", 6, 64, 320, 320), ("concat", 6, 32, 640, 320), ("concat", 2, 16, 1280, 640)])
+                                               ("concat", 6, 64, 320, 320), ("concat", 6, 32, 640, 320), ("concat", 2, 16, 1280, 640),
+                                               ("concat", 2, 18, 320, 320)])     # HW 324: 3 pixel lanes, a last slab of 4 pixels
 def test_groupnorm_from_producer_partials(dt, kind, B, H, Cin, Cout):
     """The statistics pass of a GroupNorm as per-channel partial sums left by the kernel that PRODUCED the tensor (conv / linear epilogue,
     split-K reduce, concat): the partials add up to the channel sums of the stored output, and GroupNorm(+SiLU) from them equals the
@@ -719,7 +720,7 @@ def test_linear_fp8_qkv_transposed_v(dt, B, L, C):
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("kind,B,H,Cin,Cout", [("linear", 6, 64, 320, 320), ("linear", 2, 32, 640, 640), ("conv", 6, 16, 1280, 1280), ("concat", 6, 64, 320, 640),
-                                               ("concat", 2, 32, 640, 640)])
+                                               ("concat", 2, 32, 640, 640), ("concat", 2, 18, 320, 320)])
 def test_groupnorm_apply_parts_fp8(dt, kind, B, H, Cin, Cout):
     """GroupNorm + SiLU -> e4m3 in ONE launch from the partial sums the producer of the tensor left (gc_dn_groupnorm_apply_parts_fp8): the
     e4m3 rounding of the fp64 GroupNorm of the stored tensor; channel counts that pad to 128 (320 -> 384, 960 -> 1024) have zero padding."""
