@@ -18,7 +18,7 @@
 // ([B][C][L], written by the projection GEMM's epilogue) so no transpose happens here.
 #include "dn_attn_common.h"
 
-void gc_dn_launch_attn5(const void *args, int dtype, int B, int depth, hipStream_t s);      // dn_attn5.hip
+void gc_dn_launch_attn5(const void *args, int dtype, int B, hipStream_t s);      // dn_attn5.hip
 
 namespace {
 using namespace dn;
@@ -118,14 +118,7 @@ __global__ __launch_bounds__(256, 2) void k_attn3(const AttnArgs a)
     const int ntiles = (a.Lk + 63) / 64;
     const int nsteps = a.nsets * ntiles;
 
-    // ---- LDS image, written once: zeros, column D of every key row = 1, the ones row of V^T
-    for (int i = tid; i < NST * (KBYTES + VBYTES) / 16; i += 256) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    for (int i = tid; i < NST * 64; i += 256) {
-        const int st = i >> 6, row = i & 63;
-        *reinterpret_cast<unsigned short *>(sK + st * KBYTES + row * (CPR * 16) + ((LCS ^ swz_k<CPR>(row)) << 4)) = One<T>::v;
-    }
-    for (int i = tid; i < NST * 64; i += 256) reinterpret_cast<unsigned short *>(sV + (i >> 6) * VBYTES + D * 128)[i & 63] = One<T>::v;
+    offset_lds_image<T, D, NST, CPR * 16, VBYTES, swz_k<CPR>>(smem, tid, 256, 0);
 
     // ---- Q fragments (B operand): lane holds Q[q = fr][d = 32*ks + 8*g .. +8]
     uint4 qf[QT][KS];
@@ -192,16 +185,9 @@ __global__ __launch_bounds__(256, 2) void k_attn3(const AttnArgs a)
             if (lane == s) { kb_tab = (unsigned long long)Kb; vb_tab = (unsigned long long)Vb; }
         }
     }
-    auto tab = [&](unsigned long long t, int s) __attribute__((always_inline)) -> const unsigned char * {
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)t, s), hi = __builtin_amdgcn_readlane((unsigned)(t >> 32), s);
-        return (const unsigned char *)(((unsigned long long)hi << 32) | lo);
-    };
     // DMA cursors: the K stream runs one tile ahead of the V^T stream; both walk the (set, tile) sequence and, past the end,
     // load the last set's first tile again (the counted waits need the same number of loads from every wave, every step)
-    struct Cur { const unsigned char *p; int tile, s; unsigned dst; };
-    Cur ck, cv;
-    ck.p = tab(kb_tab, 0); ck.tile = 0; ck.s = 0; ck.dst = ldsK + wid * 1024;
-    cv.p = tab(vb_tab, 0); cv.tile = 0; cv.s = 0; cv.dst = ldsV + wid * (VSH * 16);
+    KvCur ck{fetch(kb_tab, 0), 0, 0, ldsK + wid * 1024}, cv{fetch(vb_tab, 0), 0, 0, ldsV + wid * (VSH * 16)};
     const int64_t kstride = (int64_t)128 * a.ldk;
     auto issue_k = [&]() __attribute__((always_inline)) {
         if (!RAG) {
@@ -218,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void k_attn3(const AttnArgs a)
         }
         ck.dst = ck.dst + KBYTES == ldsK + wid * 1024 + NST * KBYTES ? ldsK + wid * 1024 : ck.dst + KBYTES;
         ck.p += kstride;
-        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = tab(kb_tab, ck.s); }
+        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = fetch(kb_tab, ck.s); }
     };
     auto issue_v = [&]() __attribute__((always_inline)) {
         const int lim = lk8 - cv.tile * 64;    // token chunks past round_up(Lk, 8) re-read chunk 0 (their P is exactly 0)
@@ -227,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void k_attn3(const AttnArgs a)
             glds16_s(cv.p, (unsigned)(!RAG || v_tok[j] < lim ? v_off[j] : v_off[j] - v_tok[j] * 2), cv.dst + j * 1024, v_msk[j]);
         cv.dst = cv.dst + VBYTES == ldsV + wid * (VSH * 16) + NST * VBYTES ? ldsV + wid * (VSH * 16) : cv.dst + VBYTES;
         cv.p += 128;
-        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = tab(vb_tab, cv.s); }
+        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = fetch(vb_tab, cv.s); }
     };
 
     // fragment read offsets.  K: MFMA row fr of key-subtile kt is key 32(kt/2) + 4(kt&1) + 8(fr/4) + (fr&3); chunk 4ks + g
@@ -474,14 +460,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 && QB == 1 ? 2 : 1) void k_attn4(c
     const int ntiles = (a.Lk + 63) / 64;
     const int nsteps = a.nsets * ntiles;
 
-    // ---- LDS image, written once: zeros, column D of every key row = 1, the ones row of V^T
-    for (int i = tid; i < NST * (KBYTES + VBYTES) / 16; i += NT) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    for (int i = tid; i < NST * 64; i += NT) {
-        const int st = i >> 6, row = i & 63;
-        *reinterpret_cast<unsigned short *>(sK + st * KBYTES + row * 128 + ((LCS ^ swz4(row)) << 4)) = One<T>::v;
-    }
-    for (int i = tid; i < NST * 64; i += NT) reinterpret_cast<unsigned short *>(sV + (i >> 6) * VBYTES + D * 128)[i & 63] = One<T>::v;
+    offset_lds_image<T, D, NST, 128, VBYTES, swz4>(smem, tid, NT, 0);
 
     // ---- Q fragments (B operand): lane holds Q[q = qi][d = 16 ks + 8 hg .. +8]
     uint4 qf[QB][KS];
@@ -542,14 +521,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 && QB == 1 ? 2 : 1) void k_attn4(c
             if (lane == s) { kb_tab = (unsigned long long)Kb; vb_tab = (unsigned long long)Vb; }
         }
     }
-    auto tab = [&](unsigned long long t, int s) __attribute__((always_inline)) -> const unsigned char * {
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)t, s), hi = __builtin_amdgcn_readlane((unsigned)(t >> 32), s);
-        return (const unsigned char *)(((unsigned long long)hi << 32) | lo);
-    };
-    struct Cur { const unsigned char *p; int tile, s; unsigned dst; };
-    Cur ck, cv;
-    ck.p = tab(kb_tab, 0); ck.tile = 0; ck.s = 0; ck.dst = ldsK + wid * 1024;
-    cv.p = tab(vb_tab, 0); cv.tile = 0; cv.s = 0; cv.dst = ldsV + wid * (VSH * 16);
+    KvCur ck{fetch(kb_tab, 0), 0, 0, ldsK + wid * 1024}, cv{fetch(vb_tab, 0), 0, 0, ldsV + wid * (VSH * 16)};
     const int64_t kstride = (int64_t)128 * a.ldk;
     auto issue_k = [&]() __attribute__((always_inline)) {
         if (!RAG) {
@@ -566,7 +538,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 && QB == 1 ? 2 : 1) void k_attn4(c
         }
         ck.dst = ck.dst + KBYTES == ldsK + wid * 1024 + NST * KBYTES ? ldsK + wid * 1024 : ck.dst + KBYTES;
         ck.p += kstride;
-        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = tab(kb_tab, ck.s); }
+        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = fetch(kb_tab, ck.s); }
     };
     auto issue_v = [&]() __attribute__((always_inline)) {
         const int lim = lk8 - cv.tile * 64;
@@ -575,7 +547,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 && QB == 1 ? 2 : 1) void k_attn4(c
             glds16_s(cv.p, (unsigned)(!RAG || v_tok[j] < lim ? v_off[j] : v_off[j] - v_tok[j] * 2), cv.dst + j * 1024, v_msk[j]);
         cv.dst = cv.dst + VBYTES == ldsV + wid * (VSH * 16) + NST * VBYTES ? ldsV + wid * (VSH * 16) : cv.dst + VBYTES;
         cv.p += 128;
-        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = tab(vb_tab, cv.s); }
+        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = fetch(vb_tab, cv.s); }
     };
 
     // fragment read offsets.  K: MFMA row qi of key block kb is key 32 kb + pi(qi); chunk 2 ks + hg.  V^T: row 32 db + qi, chunk 2 t + hg
@@ -750,46 +722,51 @@ __global__ __launch_bounds__(NW * 64, NW == 4 && QB == 1 ? 2 : 1) void k_attn4(c
     }
 }
 
-template <class T, int D, int NST, int NW, bool RAG, bool PRE, int PF = 3, int QB = 1>
-void launch_attn4_(const AttnArgs &a, int B, hipStream_t s)
+// (Lk % 64 != 0, Q prescaled) as two compile-time booleans for a generic lambda: the RAG x PRE instantiations of k_attn3 / k_attn4
+template <class F>
+void rag_pre(const AttnArgs &a, F &&f)
 {
-    constexpr int DB = (D + 32) / 32;
-    constexpr size_t ring = (size_t)NST * (64 * 128 + DB * 32 * 128), safe = SafeLds<D>::KBYTES + SafeLds<D>::VBYTES;
-    constexpr size_t lds = ring > safe ? ring : safe;
-    static gc::AttrOnce once;
-    gc::ensure_dynamic_lds(once, (const void *)k_attn4<T, D, NST, NW, RAG, PRE, PF, QB>, (int)lds);
-    AttnArgs aa = a;
-    aa.nqb = (a.Lq + 32 * QB * NW - 1) / (32 * QB * NW);
-    dim3 grid((unsigned)(aa.nqb * a.H * B));
-    hipLaunchKernelGGL((k_attn4<T, D, NST, NW, RAG, PRE, PF, QB>), grid, dim3(NW * 64), lds, s, aa);
+    const bool rag = (a.Lk & 63) != 0, pre = a.scale_log2e == 1.f;
+    if (rag) { if (pre) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (pre) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
 }
 template <class T, int D, int NST, int NW, int PF = 3, int QB = 1>
 void launch_attn4(const AttnArgs &a, int B, hipStream_t s)
 {
-    const bool pre = a.scale_log2e == 1.f;
-    if (a.Lk & 63) { if (pre) launch_attn4_<T, D, NST, NW, true, true, PF, QB>(a, B, s); else launch_attn4_<T, D, NST, NW, true, false, PF, QB>(a, B, s); }
-    else { if (pre) launch_attn4_<T, D, NST, NW, false, true, PF, QB>(a, B, s); else launch_attn4_<T, D, NST, NW, false, false, PF, QB>(a, B, s); }
-}
-
-template <class T, int D, int QT, int NST, bool RAG, bool PRE>
-void launch_attn3_(const AttnArgs &a, int B, hipStream_t s)
-{
-    constexpr int DP = (D + 31) / 32 * 32, CPR = DP / 8, DV = (D + 16) / 16 * 16;
-    constexpr size_t ring = (size_t)NST * (64 * CPR * 16 + DV * 128), safe = SafeLds<D>::KBYTES + SafeLds<D>::VBYTES;
-    constexpr size_t lds = ring > safe ? ring : safe;
-    static gc::AttrOnce once;
-    gc::ensure_dynamic_lds(once, (const void *)k_attn3<T, D, QT, NST, RAG, PRE>, (int)lds);
-    AttnArgs aa = a;
-    aa.nqb = (a.Lq + 64 * QT - 1) / (64 * QT);
-    dim3 grid((unsigned)(aa.nqb * a.H * B));
-    hipLaunchKernelGGL((k_attn3<T, D, QT, NST, RAG, PRE>), grid, dim3(256), lds, s, aa);
+    constexpr int DB = (D + 32) / 32;
+    rag_pre(a, [&](auto rag, auto pre) {
+        launch_ring<k_attn4<T, D, NST, NW, decltype(rag)::value, decltype(pre)::value, PF, QB>, D>((size_t)NST * (64 * 128 + DB * 32 * 128), 32 * QB * NW, NW * 64, a, B, s);
+    });
 }
 template <class T, int D, int QT, int NST>
 void launch_attn3(const AttnArgs &a, int B, hipStream_t s)
 {
-    const bool pre = a.scale_log2e == 1.f;
-    if (a.Lk & 63) { if (pre) launch_attn3_<T, D, QT, NST, true, true>(a, B, s); else launch_attn3_<T, D, QT, NST, true, false>(a, B, s); }
-    else { if (pre) launch_attn3_<T, D, QT, NST, false, true>(a, B, s); else launch_attn3_<T, D, QT, NST, false, false>(a, B, s); }
+    constexpr int DP = (D + 31) / 32 * 32, CPR = DP / 8, DV = (D + 16) / 16 * 16;
+    rag_pre(a, [&](auto rag, auto pre) {
+        launch_ring<k_attn3<T, D, QT, NST, decltype(rag)::value, decltype(pre)::value>, D>((size_t)NST * (64 * CPR * 16 + DV * 128), 64 * QT, 256, a, B, s);
+    });
+}
+
+// out = sum of the nsets partial outputs in a.part: the second launch of both set-split routes
+template <class T>
+void launch_combine(const AttnArgs &a, int D, int B, hipStream_t s)
+{
+    const int64_t n4 = (int64_t)B * a.Lq * (a.H * D) / 4;
+    hipLaunchKernelGGL((k_attn_combine<T>), dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, a.part, a.nsets, n4, n4, a.O, a.ldo,
+                       a.o_bs, (int64_t)(a.H * D) / 4, (int64_t)a.Lq);
+}
+// k_attn with 64 QQ queries per workgroup: one launch, or (GC_ATTN_SEL_SPLIT) one workgroup per (query block, set) + the combine
+template <class T, int D, int QQ>
+void launch_online(int route, const AttnArgs &a, int B, hipStream_t s)
+{
+    AttnArgs aa = a;
+    aa.nqb = (a.Lq + 64 * QQ - 1) / (64 * QQ);
+    const unsigned nwg = (unsigned)(aa.nqb * a.H * B);
+    if (route == GC_ATTN_SEL_SPLIT) {
+        hipLaunchKernelGGL((k_attn<T, D, QQ>), dim3(nwg, (unsigned)a.nsets), dim3(256), 0, s, aa);
+        launch_combine<T>(a, D, B, s);
+    } else
+        hipLaunchKernelGGL((k_attn<T, D, QQ>), dim3(nwg), dim3(256), 0, s, aa);
 }
 
 #ifndef ATT80_QT
@@ -807,7 +784,7 @@ int attn_route(const AttnArgs &a, int D, int B, const AttnVariant &v)
     // S -> max -> exp -> P V dependency chain): one workgroup per (query block, set) + a fixed-order fp32 combine
     if (D == 160 && a.part && a.nsets > 1 && (a.Lq & 255) == 0 && !v.d160_q64) return GC_ATTN_SEL_WIDE_SPLIT;   // (d160_q64: the 64-query form, A/B and tests)
     if (D != 8 && D != 16 && D != 32 && D != 40 && D != 64 && D != 80 && D != 160) return 0;
-    const int qq = D == 160 ? 1 : 2;                     // (GC_ATT below: queries per workgroup = 64 qq)
+    const int qq = D == 160 ? 1 : 2;                     // (launch_online below: queries per workgroup = 64 qq)
     const int64_t nwg = (int64_t)((a.Lq + 64 * qq - 1) / (64 * qq)) * a.H * B;
     return (a.part && a.nsets > 1 && nwg < 512) ? GC_ATTN_SEL_SPLIT : GC_ATTN_SEL_ONLINE;
 }
@@ -817,7 +794,7 @@ int launch_attn(const AttnArgs &a, int D, int B, const AttnVariant &v, hipStream
 {
     const int route = attn_route(a, D, B, v);
     switch (route) {
-    case GC_ATTN_SEL_K5: gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, v.ring, s); return GC_OK;
+    case GC_ATTN_SEL_K5: gc_dn_launch_attn5(&a, std::is_same<T, BF16>::value ? DT_BF16 : DT_F16, B, s); return GC_OK;
     case GC_ATTN_SEL_K4:
         if (v.k4_8wave) launch_attn4<T, 40, 3, 8>(a, B, s);              // 8 waves, one workgroup per CU
         else if (v.k4_q64) launch_attn4<T, 40, 4, 4, 3, 2>(a, B, s);     // 64 queries per wave (one wave per SIMD)
@@ -830,40 +807,23 @@ int launch_attn(const AttnArgs &a, int D, int B, const AttnVariant &v, hipStream
     case GC_ATTN_SEL_WIDE_SPLIT: {
         AttnArgs aa = a;
         aa.nqb = a.Lq / 256;
-        const unsigned nwg = (unsigned)(aa.nqb * a.H * B);
-        hipLaunchKernelGGL((k_attn_wide<T, 160, 2, 8>), dim3(nwg, (unsigned)a.nsets), dim3(512), 0, s, aa);
-        const int64_t n4 = (int64_t)B * a.Lq * (a.H * 160) / 4;
-        hipLaunchKernelGGL((k_attn_combine<T>), dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, a.part, a.nsets,
-                           n4, n4, a.O, a.ldo, a.o_bs, (int64_t)(a.H * 160) / 4, (int64_t)a.Lq);
+        hipLaunchKernelGGL((k_attn_wide<T, 160, 2, 8>), dim3((unsigned)(aa.nqb * a.H * B), (unsigned)a.nsets), dim3(512), 0, s, aa);
+        launch_combine<T>(a, 160, B, s);
         return GC_OK;
     }
     case 0: gc::set_error("gc_dn_attention: unsupported head dim %d", D); return GC_EINVAL;
     default: break;
     }
-#define GC_ATT(DD, QQ)                                                                                  \
-    do {                                                                                                \
-        AttnArgs aa = a;                                                                                \
-        aa.nqb = (a.Lq + 64 * QQ - 1) / (64 * QQ);                                                      \
-        const unsigned nwg = (unsigned)(aa.nqb * a.H * B);                                              \
-        if (route == GC_ATTN_SEL_SPLIT) {                                                               \
-            hipLaunchKernelGGL((k_attn<T, DD, QQ>), dim3(nwg, (unsigned)a.nsets), dim3(256), 0, s, aa); \
-            const int64_t n4 = (int64_t)B * a.Lq * (a.H * DD) / 4;                                      \
-            hipLaunchKernelGGL((k_attn_combine<T>), dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, a.part, a.nsets, \
-                               n4, n4, a.O, a.ldo, a.o_bs, (int64_t)(a.H * DD) / 4, (int64_t)a.Lq);     \
-        } else                                                                                          \
-            hipLaunchKernelGGL((k_attn<T, DD, QQ>), dim3(nwg), dim3(256), 0, s, aa);                    \
-    } while (0)
     switch (D) {
-    case 8: GC_ATT(8, 2); break;
-    case 16: GC_ATT(16, 2); break;
-    case 32: GC_ATT(32, 2); break;
-    case 40: GC_ATT(40, 2); break;
-    case 64: GC_ATT(64, 2); break;
-    case 80: GC_ATT(80, 2); break;
-    case 160: GC_ATT(160, 1); break;
+    case 8: launch_online<T, 8, 2>(route, a, B, s); break;
+    case 16: launch_online<T, 16, 2>(route, a, B, s); break;
+    case 32: launch_online<T, 32, 2>(route, a, B, s); break;
+    case 40: launch_online<T, 40, 2>(route, a, B, s); break;
+    case 64: launch_online<T, 64, 2>(route, a, B, s); break;
+    case 80: launch_online<T, 80, 2>(route, a, B, s); break;
+    case 160: launch_online<T, 160, 1>(route, a, B, s); break;
     default: break;
     }
-#undef GC_ATT
     return GC_OK;
 }
 

@@ -51,14 +51,8 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
     const int q_wave0 = qblk * 256 + (wid >> 1) * 64;
     const int ntiles = a.Lk >> 6;
 
-    // ---- LDS image, written once: zeros, column D of every key row = 1, the ones row of V^T
-    for (int i = tid; i < (XS + (SAMPLED ? NSAMP * KBYTES + 16 : 0)) / 16; i += NT) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    for (int i = tid; i < NST * 64; i += NT) {
-        const int st = i >> 6, row = i & 63;
-        *reinterpret_cast<unsigned short *>(sK + st * KBYTES + row * 128 + ((LCS ^ swz4(row)) << 4)) = One<T>::v;
-    }
-    for (int i = tid; i < NST * 64; i += NT) reinterpret_cast<unsigned short *>(sV + (i >> 6) * VBYTES + D * 128)[i & 63] = One<T>::v;
+    // ---- LDS image, written once (the exchange area, the sample tiles and the flag behind the ring start as zeros)
+    offset_lds_image<T, D, NST, 128, VBYTES, swz4>(smem, tid, NT, 2048 + (SAMPLED ? NSAMP * KBYTES + 16 : 0));
 
     // ---- Q fragments (B operand): lane holds Q[q = qi][d = 16 ks + 8 hg .. +8] of both query blocks
     uint4 qf[QB][KS];
@@ -121,10 +115,6 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
             if (lane == s) { kb_tab = (unsigned long long)Kb; vb_tab = (unsigned long long)Vb; }
         }
     }
-    auto tab = [&](unsigned long long t, int s) __attribute__((always_inline)) -> const unsigned char * {
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)t, s), hi = __builtin_amdgcn_readlane((unsigned)(t >> 32), s);
-        return (const unsigned char *)(((unsigned long long)hi << 32) | lo);
-    };
     // (recomputed where it is used -- twice per set at most -- instead of held in a register through the tile loop)
     auto sample_off = [&]() __attribute__((always_inline)) -> unsigned {
         const int p = wid * 64 + lane, row = p >> 3, lc = (p & 7) ^ swz4(row);
@@ -132,12 +122,9 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
         return (unsigned)((kj * (int)a.ldk + lc * 8) * 2);
     };
     auto issue_sample = [&](int s) __attribute__((always_inline)) {       // the sample tile of set s -> slot s & 1
-        glds16_s(tab(kb_tab, s), sample_off(), ldsK + XS + (s & 1) * KBYTES + wid * 1024, k_msk);
+        glds16_s(fetch(kb_tab, s), sample_off(), ldsK + XS + (s & 1) * KBYTES + wid * 1024, k_msk);
     };
-    struct Cur { const unsigned char *p; int tile, s; unsigned dst; };
-    Cur ck, cv;
-    ck.p = tab(kb_tab, 0); ck.tile = 0; ck.s = 0; ck.dst = ldsK + wid * 1024;
-    cv.p = tab(vb_tab, 0); cv.tile = 0; cv.s = 0; cv.dst = ldsV + wid * (VSH * 16);
+    KvCur ck{fetch(kb_tab, 0), 0, 0, ldsK + wid * 1024}, cv{fetch(vb_tab, 0), 0, 0, ldsV + wid * (VSH * 16)};
     const int64_t kstride = (int64_t)128 * a.ldk;
     // dslot >= 0: the ring slot is a compile-time constant (the tile loop is unrolled NST times when ntiles % NST == 0: every LDS
     // address is then an immediate and the per-tile pointer-wrap SALU disappears -- the kernel is sensitive to issue slots: the
@@ -147,11 +134,11 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
         glds16_s(ck.p, (unsigned)k_off, DS >= 0 ? ldsK + wid * 1024 + DS * KBYTES : ck.dst, k_msk);
         if (DS < 0) ck.dst = ck.dst + KBYTES == ldsK + wid * 1024 + NST * KBYTES ? ldsK + wid * 1024 : ck.dst + KBYTES;
         ck.p += kstride;
-        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = tab(kb_tab, ck.s); }
+        if (++ck.tile == ntiles) { ck.tile = 0; ck.s = ck.s + 1 < a.nsets ? ck.s + 1 : ck.s; ck.p = fetch(kb_tab, ck.s); }
         glds16_s(cv.p, (unsigned)v_off, DS >= 0 ? ldsV + wid * (VSH * 16) + DS * VBYTES : cv.dst, v_msk);
         if (DS < 0) cv.dst = cv.dst + VBYTES == ldsV + wid * (VSH * 16) + NST * VBYTES ? ldsV + wid * (VSH * 16) : cv.dst + VBYTES;
         cv.p += 128;
-        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = tab(vb_tab, cv.s); }
+        if (++cv.tile == ntiles) { cv.tile = 0; cv.s = cv.s + 1 < a.nsets ? cv.s + 1 : cv.s; cv.p = fetch(vb_tab, cv.s); }
     };
 
     // fragment read offsets.  K: MFMA row qi is key pi(qi) of the wave's key block; chunk 2 ks + hg.  V^T: row 32 db + qi, chunk 2 t + hg
@@ -361,90 +348,55 @@ __global__ __launch_bounds__(512, 1) void k_attn5(const AttnArgs a)
             __builtin_amdgcn_sched_barrier(0);          // (the MFMA issues first: its ops run in its shadow)
             uops(S1, pf[1][0], pf[1][1], integral_constant<int, 4>{}, integral_constant<int, 7>{});
             __builtin_amdgcn_sched_barrier(0);
-            return;
-        }
-        S0 = T::mfma32(kf[0], qf[0][0], zero16);        // C
-        unit(S1, pf[1][1], 0, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        S0 = T::mfma32(kf[1], qf[0][1], S0);
-        unit(S1, pf[1][1], 1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        S0 = T::mfma32(kf[2], qf[0][2], S0);
-        unit(S1, pf[1][1], 2, 1); unit(S1, pf[1][1], 3, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PV16) {
-            uint4 qa, qc;
+        } else {
+            // the round-3 schedule (the instrumented instantiation): whole exp units behind the MFMAs, P V of row block 1 on 32x32x16 MFMAs
+            S0 = T::mfma32(kf[0], qf[0][0], zero16);        // C
+            unit(S1, pf[1][1], 0, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            S0 = T::mfma32(kf[1], qf[0][1], S0);
+            unit(S1, pf[1][1], 1, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            S0 = T::mfma32(kf[2], qf[0][2], S0);
+            unit(S1, pf[1][1], 2, 1); unit(S1, pf[1][1], 3, 1);
+            __builtin_amdgcn_sched_barrier(0);
             os[1][0] = T::mfma32(vf[0][0], pf[1][0], os[1][0]);      // D
             __builtin_amdgcn_sched_barrier(0);
-            os[1][0] = T::mfma32(vf[1][0], pf[1][1], os[1][0]);
-            p16(pf[1][0], pf[1][1], qa, qc);      // after BOTH 32x32x16 MFMAs have read P: the lane swaps run in place (no copies of the 8 P registers)
+            os[1][DB - 1] = T::mfma32(vf[0][DB - 1], pf[1][0], os[1][DB - 1]);
             unit(S0, pf[0][0], 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            o1[1][0] = T::mfma(vf16, qa, o1[1][0]);
+            os[1][0] = T::mfma32(vf[1][0], pf[1][1], os[1][0]);
             unit(S0, pf[0][0], 1, 0);
             __builtin_amdgcn_sched_barrier(0);
-            o1[1][1] = T::mfma(vf16, qc, o1[1][1]);
+            os[1][DB - 1] = T::mfma32(vf[1][DB - 1], pf[1][1], os[1][DB - 1]);
             unit(S0, pf[0][0], 2, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(ABL && (abl & 16))) {     // E
-                vf[0][0] = *reinterpret_cast<const uint4 *>(vb_ + vfo[0]); vf[1][0] = *reinterpret_cast<const uint4 *>(vb_ + vfo[1]);
-                vf16 = *reinterpret_cast<const uint4 *>(vb_ + vfo16);
+            if (!(ABL && (abl & 16))) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)     // E
+#pragma unroll
+                    for (int db = 0; db < DB; ++db) vf[t][db] = *reinterpret_cast<const uint4 *>(vb_ + vfo[t] + db * 4096);
             }
-        } else {
-        os[1][0] = T::mfma32(vf[0][0], pf[1][0], os[1][0]);      // D
-        __builtin_amdgcn_sched_barrier(0);
-        os[1][DB - 1] = T::mfma32(vf[0][DB - 1], pf[1][0], os[1][DB - 1]);
-        unit(S0, pf[0][0], 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        os[1][0] = T::mfma32(vf[1][0], pf[1][1], os[1][0]);
-        unit(S0, pf[0][0], 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        os[1][DB - 1] = T::mfma32(vf[1][DB - 1], pf[1][1], os[1][DB - 1]);
-        unit(S0, pf[0][0], 2, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(ABL && (abl & 16))) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)     // E
-#pragma unroll
-                for (int db = 0; db < (PV16 ? 1 : DB); ++db) vf[t][db] = *reinterpret_cast<const uint4 *>(vb_ + vfo[t] + db * 4096);
-        }
-        }
-        S1 = T::mfma32(kf[0], qf[1][0], zero16);        // F
-        unit(S0, pf[0][0], 3, 0); unit(S0, pf[0][1], 0, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        S1 = T::mfma32(kf[1], qf[1][1], S1);
-        unit(S0, pf[0][1], 1, 1); unit(S0, pf[0][1], 2, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        S1 = T::mfma32(kf[2], qf[1][2], S1);
-        unit(S0, pf[0][1], 3, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        rd_kf(SLOT < 0 ? rk : sK + ((SLOT + 1) % NST) * KBYTES);      // tile i+1 (landed: the barrier above waited for it)
-        if constexpr (PV16) {
-            uint4 qa, qc;
+            S1 = T::mfma32(kf[0], qf[1][0], zero16);        // F
+            unit(S0, pf[0][0], 3, 0); unit(S0, pf[0][1], 0, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            S1 = T::mfma32(kf[1], qf[1][1], S1);
+            unit(S0, pf[0][1], 1, 1); unit(S0, pf[0][1], 2, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            S1 = T::mfma32(kf[2], qf[1][2], S1);
+            unit(S0, pf[0][1], 3, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            rd_kf(SLOT < 0 ? rk : sK + ((SLOT + 1) % NST) * KBYTES);      // tile i+1 (landed: the barrier above waited for it)
             os[0][0] = T::mfma32(vf[0][0], pf[0][0], os[0][0]);      // G
             __builtin_amdgcn_sched_barrier(0);
-            os[0][0] = T::mfma32(vf[1][0], pf[0][1], os[0][0]);
-            p16(pf[0][0], pf[0][1], qa, qc);
+            os[0][DB - 1] = T::mfma32(vf[0][DB - 1], pf[0][0], os[0][DB - 1]);
             unit(S1, pf[1][0], 0, 0); unit(S1, pf[1][0], 1, 0);
             __builtin_amdgcn_sched_barrier(0);
-            o1[0][0] = T::mfma(vf16, qa, o1[0][0]);
+            os[0][0] = T::mfma32(vf[1][0], pf[0][1], os[0][0]);
             unit(S1, pf[1][0], 2, 0);
             __builtin_amdgcn_sched_barrier(0);
-            o1[0][1] = T::mfma(vf16, qc, o1[0][1]);
+            os[0][DB - 1] = T::mfma32(vf[1][DB - 1], pf[0][1], os[0][DB - 1]);
             unit(S1, pf[1][0], 3, 0);
             __builtin_amdgcn_sched_barrier(0);
-        } else {
-        os[0][0] = T::mfma32(vf[0][0], pf[0][0], os[0][0]);      // G
-        __builtin_amdgcn_sched_barrier(0);
-        os[0][DB - 1] = T::mfma32(vf[0][DB - 1], pf[0][0], os[0][DB - 1]);
-        unit(S1, pf[1][0], 0, 0); unit(S1, pf[1][0], 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        os[0][0] = T::mfma32(vf[1][0], pf[0][1], os[0][0]);
-        unit(S1, pf[1][0], 2, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        os[0][DB - 1] = T::mfma32(vf[1][DB - 1], pf[0][1], os[0][DB - 1]);
-        unit(S1, pf[1][0], 3, 0);
-        __builtin_amdgcn_sched_barrier(0);
         }
     };
     // end of a K/V set: finish the pipeline (B and D of the last tile), then O_total += w / (l_a + l_b) * O_set; a wave's partial
@@ -606,14 +558,7 @@ template <class T, bool PRE, int NST, bool ABL = false>
 void launch_attn5_(const AttnArgs &a, int B, hipStream_t s)
 {
     constexpr size_t ring = (size_t)NST * (64 * 128 + 2 * 32 * 128) + 2048 + 2 * (64 * 128) + 16, xchg = (size_t)8 * 24 * 64 * 4;   // ring + exchange + 2 sample tiles + flag
-    constexpr size_t safe = SafeLds<40>::KBYTES + SafeLds<40>::VBYTES;
-    constexpr size_t lds = ring > xchg ? (ring > safe ? ring : safe) : (xchg > safe ? xchg : safe);
-    static gc::AttrOnce once;
-    gc::ensure_dynamic_lds(once, (const void *)k_attn5<T, PRE, NST, ABL>, (int)lds);
-    AttnArgs aa = a;
-    aa.nqb = a.Lq / 256;
-    dim3 grid((unsigned)(aa.nqb * a.H * B));
-    hipLaunchKernelGGL((k_attn5<T, PRE, NST, ABL>), grid, dim3(512), lds, s, aa);
+    launch_ring<k_attn5<T, PRE, NST, ABL>, 40>(ring > xchg ? ring : xchg, 256, 512, a, B, s);
 }
 template <class T, int NST>
 void launch_attn5(const AttnArgs &a, int B, hipStream_t s)
@@ -624,10 +569,9 @@ void launch_attn5(const AttnArgs &a, int B, hipStream_t s)
 }  // namespace
 
 // AttnArgs has internal linkage per translation unit (same definition in both): the entry point takes it through a void pointer.
-// depth: stages of the K / V^T LDS ring (4, 6 or 8: the DMA of a tile is issued depth - 1 tiles before its barrier)
-void gc_dn_launch_attn5(const void *args, int dtype, int B, int depth, hipStream_t s)
+// The ring has 4 stages, which divides the 64 tiles of L = 4096 (depths 4 / 6 / 8 measured equal, profiles/r03_attn5_ablation.txt).
+void gc_dn_launch_attn5(const void *args, int dtype, int B, hipStream_t s)
 {
-    (void)depth;       // ring depths 4 / 6 / 8 measured equal (profiles/r03_attn5_ablation.txt): 4 stages, which divides the 64 tiles of L = 4096
     const AttnArgs &a = *static_cast<const AttnArgs *>(args);
     if (a.abl & ABL_BYTE) { launch_attn5_<BF16, true, 4, true>(a, B, s); return; }
     if (dtype == DT_BF16) launch_attn5<BF16, 4>(a, B, s);

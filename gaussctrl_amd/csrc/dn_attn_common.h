@@ -1,6 +1,12 @@
 // dn_attn_common.h -- pieces shared by the attention translation units (dn_attn.hip: k_attn / k_attn3 / k_attn4 and the C ABI entry;
-// dn_attn5.hip: k_attn5): argument block, XCD-aware workgroup order, the online-softmax body (whole kernel for plain head sizes,
-// in-kernel fallback of the static-offset kernels), LDS-DMA helpers.  Everything has internal linkage (anonymous namespace per TU).
+// dn_attn5.hip: k_attn5), each written once: argument block, XCD-aware workgroup order, the online-softmax body (whole kernel for plain head
+// sizes, in-kernel fallback of the static-offset kernels), and for the static-offset kernels the LDS image (offset_lds_image), the readlane fetch
+// of the lane-parked set table (fetch), the DMA cursor type (KvCur), the LDS-DMA helpers and the launcher (launch_ring).  Everything has
+// internal linkage (anonymous namespace per TU).
+// What is shared is what leaves every kernel's machine code as it was.  The per-set base addresses, the cursor advance, the DMA plan and the Q
+// fragment load stay in line in each kernel: as helpers they changed the code of the tile loops or prologues, and the product launches measured
+// 0.3 - 0.8 % slower.  A helper that takes AttnArgs & and selects between the ADDRESSES of a.K and a.Kr is worse: it keeps the whole 224-byte
+// kernarg copy in private memory (224-248 bytes in every k_attn5 instantiation; tests/test_kernel_resources.py holds them at 0).
 #pragma once
 #include "dn_common.h"
 #include <cstdlib>
@@ -43,9 +49,8 @@ constexpr int ABL_BYTE = GC_ATTN_VAR_ABL_MASK >> GC_ATTN_VAR_ABL_SHIFT, ABL_CSHI
 
 // gc_attn_desc.kernel_variant decoded (GC_ATTN_VAR_* in gaussctrl_hip.h; all zero = the product)
 struct AttnVariant {
-    bool online_only, d40_k3, k4_8wave, k4_q64, k4;
-    int ring;              // stages asked of k_attn5's LDS ring: 4, 8 or the default 6
-    bool d160_q64;
+    bool online_only, d40_k3, k4_8wave, k4_q64, k4, d160_q64;      // (GC_ATTN_VAR_RING4 / RING8 are accepted and select nothing: k_attn5's
+                                                                   // ring has 4 stages, depths 4 / 6 / 8 measured equal, profiles/r03_attn5_ablation.txt)
     int abl, cshift;       // -> AttnArgs.abl
     int undefined;         // bits no switch owns: refused where there is an error channel (dn::refuse_variant_bits)
     bool off_k5() const { return d40_k3 || k4_8wave || k4_q64 || k4; }      // a switch sends head_dim 40 to another kernel than k_attn5
@@ -56,7 +61,7 @@ inline AttnVariant decode_variant(int kv)
     constexpr int flags = GC_ATTN_VAR_ONLINE_ONLY | GC_ATTN_VAR_D40_K3 | GC_ATTN_VAR_K4_8WAVE | GC_ATTN_VAR_K4_Q64 | GC_ATTN_VAR_K4 | GC_ATTN_VAR_RING4 |
                           GC_ATTN_VAR_RING8 | GC_ATTN_VAR_D160_Q64;
     return {bit(GC_ATTN_VAR_ONLINE_ONLY), bit(GC_ATTN_VAR_D40_K3), bit(GC_ATTN_VAR_K4_8WAVE), bit(GC_ATTN_VAR_K4_Q64), bit(GC_ATTN_VAR_K4),
-            bit(GC_ATTN_VAR_RING4) ? 4 : bit(GC_ATTN_VAR_RING8) ? 8 : 6, bit(GC_ATTN_VAR_D160_Q64),
+            bit(GC_ATTN_VAR_D160_Q64),
             (kv & GC_ATTN_VAR_ABL_MASK) >> GC_ATTN_VAR_ABL_SHIFT, (kv & GC_ATTN_VAR_CSHIFT_MASK) >> GC_ATTN_VAR_CSHIFT_SHIFT,
             kv & ~(flags | GC_ATTN_VAR_ABL_MASK | GC_ATTN_VAR_CSHIFT_MASK)};
 }
@@ -382,4 +387,50 @@ template <int N> __device__ __forceinline__ void wait_vmcnt()
 }
 
 __device__ __forceinline__ int swz4(int row) { return ((row >> 1) ^ (row << 1) ^ (row << 2)) & 7; }   // conflict-free for both tiles (search: scripts/lds_swizzle_search.py)
+
+// ---- the static-offset kernels (k_attn3 / k_attn4 / k_attn5): shared prologue pieces
+
+// Per-set K / V^T base addresses are parked by each kernel in lane s of two VGPR pairs (kb_tab, vb_tab): the v_readlane pair that fetches set s
+__device__ __forceinline__ const unsigned char *fetch(unsigned long long table_word, int s)
+{
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)table_word, s), hi = __builtin_amdgcn_readlane((unsigned)(table_word >> 32), s);
+    return (const unsigned char *)(((unsigned long long)hi << 32) | lo);
+}
+
+// LDS image of an offset kernel, written once (the DMA only ever lands data chunks on it): NST stages of 64 key rows of KPITCH bytes, then NST
+// stages of VBYTES of V^T rows (128 bytes each), then extra_zero_bytes of the caller's; all zero, except column D of every key row = 1 (it
+// meets the offset in column D of Q) and row D of V^T = ones (the softmax denominator comes out of the P V MFMAs).  Swz: the key rows' chunk swizzle.
+template <class T, int D, int NST, int KPITCH, int VBYTES, int (*Swz)(int)>
+__device__ __forceinline__ void offset_lds_image(unsigned char *smem, int tid, int NT, int extra_zero_bytes)
+{
+    constexpr int KBYTES = 64 * KPITCH, LCS = D / 8;
+    unsigned char *sK = smem, *sV = smem + NST * KBYTES;
+    for (int i = tid; i < (NST * (KBYTES + VBYTES) + extra_zero_bytes) / 16; i += NT) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    for (int i = tid; i < NST * 64; i += NT) {
+        const int st = i >> 6, row = i & 63;
+        *reinterpret_cast<unsigned short *>(sK + st * KBYTES + row * KPITCH + ((LCS ^ Swz(row)) << 4)) = One<T>::v;
+    }
+    for (int i = tid; i < NST * 64; i += NT) reinterpret_cast<unsigned short *>(sV + (i >> 6) * VBYTES + D * 128)[i & 63] = One<T>::v;
+}
+
+// DMA cursor of the K or the V^T stream over the flattened (set, tile) sequence: global source of the next tile, its tile and set, the LDS
+// destination of this wave.  Each kernel advances it in line after a tile's loads (ring slot wraps, source steps one tile, past a set's last
+// tile it is fetched again from the table; past the last set, the last set's first tile: the counted waits need the same number of loads from
+// every wave, every step).  A shared by-value advance(cur, ...) was built and taken out: it changed the code of the k_attn3 / k_attn4 tile loop.
+struct KvCur { const unsigned char *p; int tile, s; unsigned dst; };
+
+// Launcher of the three: dynamic LDS = the larger of the kernel's own plan (lds_ring) and the fallback body's two tiles; one workgroup of
+// `threads` per `queries_per_wg` queries of a (frame, head)
+template <auto Kernel, int D>
+void launch_ring(size_t lds_ring, int queries_per_wg, int threads, const AttnArgs &a, int B, hipStream_t s)
+{
+    constexpr size_t safe = SafeLds<D>::KBYTES + SafeLds<D>::VBYTES;
+    const size_t lds = lds_ring > safe ? lds_ring : safe;
+    static gc::AttrOnce once;
+    gc::ensure_dynamic_lds(once, (const void *)Kernel, (int)lds);
+    AttnArgs aa = a;
+    aa.nqb = (a.Lq + queries_per_wg - 1) / queries_per_wg;
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)(aa.nqb * a.H * B)), dim3(threads), lds, s, aa);
+}
 }  // namespace

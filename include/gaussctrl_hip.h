@@ -479,7 +479,7 @@ enum { GC_ATTN_VAR_ONLINE_ONLY = 1,                                    /* the on
        GC_ATTN_VAR_K4_8WAVE = 4,                                       /* head_dim 40 on k_attn4 with 8 waves, one workgroup per CU */
        GC_ATTN_VAR_K4_Q64 = 8,                                         /* head_dim 40 on k_attn4 with 64 queries per wave (25 % slower: DESIGN.md 7.1) */
        GC_ATTN_VAR_K4 = 16,                                            /* head_dim 40 on k_attn4 instead of k_attn5 */
-       GC_ATTN_VAR_RING4 = 32, GC_ATTN_VAR_RING8 = 64,                 /* k_attn5 asked for an LDS ring of 4 / 8 tiles instead of 6 */
+       GC_ATTN_VAR_RING4 = 32, GC_ATTN_VAR_RING8 = 64,                 /* accepted, select nothing: k_attn5's LDS ring has 4 tiles (4 / 6 / 8 measured equal) */
        GC_ATTN_VAR_D160_Q64 = 128,                                     /* head_dim 160 on the 64-query form (k_attn), not k_attn_wide */
        GC_ATTN_VAR_ABL_MASK = 0xff00, GC_ATTN_VAR_ABL_SHIFT = 8,       /* TIMING ablations of k_attn5's instrumented instantiation (results wrong by construction; csrc/dn_attn5.hip) */
        GC_ATTN_VAR_CSHIFT_MASK = 0x1f0000, GC_ATTN_VAR_CSHIFT_SHIFT = 16 };      /* k_attn5: P = exp2(s - m0 - cshift) (experiment; csrc/dn_attn5.hip) */

@@ -135,3 +135,27 @@ def test_compositing_kernels_use_no_private_memory(kernels):
         hit.update(fam)
     assert len(hit) == 18, sorted(hit)
     assert all(v == (0, 0) for v in hit.values()), {k: v for k, v in hit.items() if v != (0, 0)}
+
+
+def test_attention_kernels_use_no_private_memory(kernels):
+    """every kernel of csrc/dn_attn.hip -- k_attn x 14, k_attn3 x 16, k_attn4 x 24, k_attn_wide x 2, k_attn_combine x 2 -- and the four product
+    instantiations of k_attn5: no scratch, no spilled VGPRs.  In k_attn3 / k_attn4 / k_attn5 a scratch access drains the K / V^T DMA ring on
+    every tile, and a prologue helper that chose between the addresses of two pointer fields of the argument block kept the whole 224-byte
+    block in private memory (csrc/dn_attn_common.h).  The instrumented (timing-ablation) instantiation of k_attn5 is held at its recorded
+    numbers.  The counts are asserted so that no instantiation is silently missed."""
+    want = {r"\bk_attn<": 14, r"\bk_attn3<": 16, r"\bk_attn4<": 24, r"\bk_attn_wide<": 2, r"\bk_attn_combine<": 2}
+    hit = {}
+    for p, n in want.items():
+        fam = {k: v for k, v in kernels.items() if re.search(p, k)}
+        assert len(fam) == n, (p, sorted(fam))
+        hit.update(fam)
+    assert len(hit) == 58, sorted(hit)
+    k5 = {k: v for k, v in kernels.items() if re.search(r"\bk_attn5<", k)}
+    assert len(k5) == 5, sorted(k5)
+    abl = {k: v for k, v in k5.items() if re.search(r"k_attn5<dn::BF16, true, 4, true, false>", k)}
+    assert len(abl) == 1, sorted(k5)
+    hit.update({k: v for k, v in k5.items() if k not in abl})
+    assert len(hit) == 62
+    assert all(v == (0, 0) for v in hit.values()), {k: v for k, v in hit.items() if v != (0, 0)}
+    (v,) = abl.values()
+    assert v[0] <= 124 and v[1] <= 46, abl
