@@ -51,6 +51,10 @@ EXT_SYMBOLS = [
     # bilateral-grid colour compensation (slice forward / backward, total variation): include/gaussctrl_bilagrid.h
     "gcx_bilagrid_slice_fwd_views", "gcx_bilagrid_slice_bwd_views", "gcx_bilagrid_tv_workspace_bytes", "gcx_bilagrid_tv_fwd_bwd",
 ]
+# the extension set of include/gaussctrl_pose.h (camera gradient of the front end), a list of its own beside the bilateral grid's
+# (tests/test_pose_abi_cpu.py checks the header against it); EXT_SETS is everything the loader resolves beyond SYMBOLS
+POSE_SYMBOLS = ["gcx_pose_bwd_views_workspace_bytes", "gcx_pose_bwd_views"]
+EXT_SETS = {"gaussctrl_bilagrid.h": EXT_SYMBOLS, "gaussctrl_pose.h": POSE_SYMBOLS}
 
 _lib = None
 
@@ -67,11 +71,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
         l = C.CDLL(LIB_PATH)
-        for s in SYMBOLS + EXT_SYMBOLS:
+        every = SYMBOLS + [s for ext in EXT_SETS.values() for s in ext]
+        for s in every:
             if not hasattr(l, s):
                 raise GaussCtrlHipError(f"libgaussctrl_hip.so does not export {s}")
         l.gc_last_error_string.restype = C.c_char_p
-        for s in SYMBOLS + EXT_SYMBOLS:
+        for s in every:
             if s.endswith("_bytes"):
                 getattr(l, s).restype = C.c_size_t
                 continue

@@ -10,6 +10,7 @@
 // outputs (radii, tile boxes, num_tiles_hit -> sort keys) are bit-identical to the CPU oracle.
 #include "common.h"
 #include "../../include/gaussctrl_antialias.h"
+#include "../../include/gaussctrl_pose.h"
 #include <type_traits>
 
 namespace {
@@ -161,16 +162,29 @@ struct ProjGrad {
 // (the forms (s X00 - h detX), (s X11 - h detX), 2 s X01 with s = 1 - rho^2 of the conic X, multiplied out), d rho = d rho^2 / (2 rho).
 // b stands for BOTH off-diagonal entries, so each of them takes half of d/db -- the convention of G01 = 0.5 g1 below.  rho == 0 (or a zero
 // cotangent, which is all a splat below 1/255 can receive) contributes nothing, and nothing is divided by it.
-template <bool AA = false>
+// one row of a camera matrix applied to (p, 1), in double, rounded to float32 once
+__device__ __forceinline__ float dot3(const float *m, float p0, float p1, float p2)
+{
+    return (float)((((double)m[0] * (double)p0 + (double)m[1] * (double)p1) + (double)m[2] * (double)p2) + (double)m[3]);
+}
+
+// POSE (gcx_pose_bwd_views, include/gaussctrl_pose.h): also the cotangents of the two camera matrices, from the values formed here anyway --
+// pose[0..11] = v_V [3][4] (the camera-space mean t = V (p, 1) with its depth, and T = J V[:, :3]), pose[12..23] = rows 0, 1, 3 of v_P (the pixel
+// centre; row 2 of P is never read).  With AA the v_rho term already sits inside vT.  POSE = false compiles to the code it always was.
+template <bool AA = false, bool POSE = false>
 __device__ __forceinline__ void project_one_bwd(const Cam &cam, float p0, float p1, float p2, float s0, float s1,
                                                 float s2, float qw, float qx, float qy, float qz,
                                                 float X00, float X01, float X11, float vx, float vy, float vz,
-                                                float g0, float g1, float g2, ProjGrad &o, float v_rho = 0.f)
+                                                float g0, float g1, float g2, ProjGrad &o, float v_rho = 0.f, float *pose = nullptr)
 {
     const float *V = cam.V, *P = cam.P;
     float hx = ((P[0] * p0 + P[1] * p1) + P[2] * p2) + P[3];
     float hy = ((P[4] * p0 + P[5] * p1) + P[6] * p2) + P[7];
     float hw = ((P[12] * p0 + P[13] * p1) + P[14] * p2) + P[15];
+    if (POSE) {      // the camera sums are led by the Gaussians nearest the camera, whose hw (and tz below) cancel from terms fifty times their
+                     // size and enter squared in the denominator: formed in double from the same float32 inputs, rounded once (dot3)
+        hx = dot3(P, p0, p1, p2); hy = dot3(P + 4, p0, p1, p2); hw = dot3(P + 12, p0, p1, p2);
+    }
     float rw = 1.f / (hw + 1e-6f);
     float vnx = 0.5f * (float)cam.W * vx, vny = 0.5f * (float)cam.H * vy;
     float vhx = vnx * rw, vhy = vny * rw, vhw = -(vnx * hx + vny * hy) * rw * rw;
@@ -185,6 +199,7 @@ __device__ __forceinline__ void project_one_bwd(const Cam &cam, float p0, float 
     float tx = ((V[0] * p0 + V[1] * p1) + V[2] * p2) + V[3];
     float ty = ((V[4] * p0 + V[5] * p1) + V[6] * p2) + V[7];
     float tz = ((V[8] * p0 + V[9] * p1) + V[10] * p2) + V[11];
+    if (POSE) { tx = dot3(V, p0, p1, p2); ty = dot3(V + 4, p0, p1, p2); tz = dot3(V + 8, p0, p1, p2); }
     float lim_x = 1.3f * (0.5f * (float)cam.W / cam.fx), lim_y = 1.3f * (0.5f * (float)cam.H / cam.fy);
     float rx = tx / tz, ry = ty / tz;
     float rxc = clampf(rx, -lim_x, lim_x), ryc = clampf(ry, -lim_y, lim_y);
@@ -267,6 +282,22 @@ __device__ __forceinline__ void project_one_bwd(const Cam &cam, float p0, float 
     o.vm[0] += V[0] * v_tx + V[4] * v_ty + V[8] * v_tz;
     o.vm[1] += V[1] * v_tx + V[5] * v_ty + V[9] * v_tz;
     o.vm[2] += V[2] * v_tx + V[6] * v_ty + V[10] * v_tz;
+    if (POSE) {
+        const float p[3] = {p0, p1, p2};
+        const float vt[3] = {v_tx, v_ty, v_tz + vz}, vh[3] = {vhx, vhy, vhw};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { pose[4 * r + k] = vt[r] * p[k]; pose[12 + 4 * r + k] = vh[r] * p[k]; }
+            pose[4 * r + 3] = vt[r]; pose[12 + 4 * r + 3] = vh[r];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            pose[k] += j00 * vT[k];
+            pose[4 + k] += j11 * vT[3 + k];
+            pose[8 + k] += j02 * vT[k] + j12 * vT[3 + k];
+        }
+    }
 }
 
 // ---------------------------------------------------------------- SH (Appendix A.2)
@@ -777,6 +808,110 @@ __global__ __launch_bounds__(256) void k_project_sh_bwd_views(int64_t N, CamBatc
     flush_rest_out<R, ACC>(svr, v_rest, N, i0, tid);
 }
 
+// ---------------------------------------------------------------- kernels: camera (pose) gradient over C views (include/gaussctrl_pose.h)
+// The 24 camera cotangents of project_one_bwd<AA, true>, summed over the Gaussians of each view.  The CamBatch walk of k_project_sh_bwd_views: the
+// record is read once and serves every view of the launch.  A workgroup covers POSE_ITEMS * 256 consecutive Gaussians; per (Gaussian, view) a
+// wave folds its 64 x 24 values to 24 with a reduce-scatter (each of the first three steps halves the values a lane still owns: 12 + 6 + 3
+// exchanges, then 3 x 3 butterfly steps -- 30 cross-lane moves instead of 144) and adds them to its own LDS row; the four rows are added in wave
+// order into one float32 partial per (workgroup, view) in the caller's workspace, [C][workgroups][24].  k_pose_sum adds a view's partials in a
+// fixed order in double.  No atomics anywhere: the same bits every run.  A view in which no lane of a wave kept its Gaussian costs that wave
+// one ballot.
+constexpr int POSE_ITEMS = 4, POSE_VALS = 24;
+
+__device__ __forceinline__ void pose_wave_fold(float *v /* [24] -> the lane's 3 totals in v[0..2] */, int lane)
+{
+    const bool up5 = (lane & 32) != 0, up4 = (lane & 16) != 0, up3 = (lane & 8) != 0;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {      // 24 -> 12: the upper half-wave keeps values 12..23
+        const float keep = up5 ? v[12 + j] : v[j], send = up5 ? v[j] : v[12 + j];
+        v[j] = keep + __shfl_xor(send, 32);
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {       // 12 -> 6
+        const float keep = up4 ? v[6 + j] : v[j], send = up4 ? v[j] : v[6 + j];
+        v[j] = keep + __shfl_xor(send, 16);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {       // 6 -> 3
+        const float keep = up3 ? v[3 + j] : v[j], send = up3 ? v[j] : v[3 + j];
+        v[j] = keep + __shfl_xor(send, 8);
+    }
+#pragma unroll
+    for (int off = 4; off >= 1; off >>= 1)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v[j] = v[j] + __shfl_xor(v[j], off);
+}
+
+template <bool AA>
+__global__ __launch_bounds__(256) void k_pose_bwd_views(int64_t N, CamBatch cb, int64_t nblk, const float *__restrict__ means,
+        const float *__restrict__ log_scales, const float *__restrict__ quats, const float *__restrict__ op_logit,
+        const int32_t *__restrict__ radii, const float *__restrict__ conics, const float *__restrict__ v_xy, const float *__restrict__ v_conic,
+        const float *__restrict__ v_opac, const float *__restrict__ v_depths /* may be NULL */, float *__restrict__ partials /* this launch's views */)
+{
+    __shared__ float acc[4][MAXV][POSE_VALS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int j = tid; j < 4 * MAXV * POSE_VALS; j += 256) (&acc[0][0][0])[j] = 0.f;
+    __syncthreads();
+    // the three values this lane ends a fold with: 12 (bit 5) + 6 (bit 4) + 3 (bit 3) of its lane number; lanes 0, 8, .., 56 store them
+    const int slot = ((lane >> 5) & 1) * 12 + ((lane >> 4) & 1) * 6 + ((lane >> 3) & 1) * 3;
+    const int64_t i0 = (int64_t)blockIdx.x * (256 * POSE_ITEMS);
+    for (int it = 0; it < POSE_ITEMS; ++it) {
+        const int64_t i = i0 + (int64_t)it * 256 + tid;
+        if (i0 + (int64_t)it * 256 >= N) break;                       // (uniform over the workgroup)
+        const bool live = i < N;
+        Record r;
+        load_record<false>(r, live ? i : N - 1, means, log_scales, quats, op_logit, nullptr);
+        activate(r);
+        for (int v = 0; v < cb.C; ++v) {
+            const int64_t o = (int64_t)v * N + (live ? i : N - 1);
+            const bool kept = live && radii[o] > 0;
+            if (__ballot(kept) == 0ull) continue;                     // (uniform over the wave)
+            float pose[POSE_VALS];
+#pragma unroll
+            for (int k = 0; k < POSE_VALS; ++k) pose[k] = 0.f;
+            if (kept) {
+                ProjGrad pg;
+                project_one_bwd<AA, true>(cb.cam[v], r.p[0], r.p[1], r.p[2], r.s[0], r.s[1], r.s[2], r.q[0], r.q[1], r.q[2], r.q[3],
+                                          conics[3 * o], conics[3 * o + 1], conics[3 * o + 2], v_xy[2 * o], v_xy[2 * o + 1],
+                                          v_depths ? v_depths[o] : 0.f, v_conic[3 * o], v_conic[3 * o + 1], v_conic[3 * o + 2], pg,
+                                          AA ? v_opac[o] * r.op : 0.f, pose);
+            }
+            pose_wave_fold(pose, lane);
+            if ((lane & 7) == 0) {                                    // the wave's own row: no other wave touches it, program order suffices
+                float *a = &acc[wave][v][slot];
+                a[0] = a[0] + pose[0]; a[1] = a[1] + pose[1]; a[2] = a[2] + pose[2];
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < cb.C * POSE_VALS) {
+        const int v = tid / POSE_VALS, k = tid % POSE_VALS;
+        partials[((int64_t)v * nblk + blockIdx.x) * POSE_VALS + k] = ((acc[0][v][k] + acc[1][v][k]) + acc[2][v][k]) + acc[3][v][k];
+    }
+}
+
+// One workgroup per view: thread (s, k) = (tid / 24, tid % 24), s < 10, adds the partials s, s + 10, s + 20, ... of value k in double; thread k
+// then adds the ten slice sums in slice order and rounds to float32 once.
+__global__ __launch_bounds__(256) void k_pose_sum(int64_t nblk, const float *__restrict__ partials, float *__restrict__ out)
+{
+    constexpr int SLICES = 10;
+    __shared__ double part[SLICES][POSE_VALS];
+    const int tid = threadIdx.x, s = tid / POSE_VALS, k = tid % POSE_VALS;
+    const float *p = partials + (int64_t)blockIdx.x * nblk * POSE_VALS;
+    if (s < SLICES) {
+        double sum = 0.0;
+        for (int64_t b = s; b < nblk; b += SLICES) sum = sum + (double)p[b * POSE_VALS + k];
+        part[s][k] = sum;
+    }
+    __syncthreads();
+    if (tid < POSE_VALS) {
+        double sum = part[0][tid];
+#pragma unroll
+        for (int j = 1; j < SLICES; ++j) sum = sum + part[j][tid];
+        out[(int64_t)blockIdx.x * POSE_VALS + tid] = (float)sum;
+    }
+}
+
 // img_out == img_raw: in place.  Otherwise the un-clamped image stays where the compositing wrote it (the backward needs it for the
 // clamp's gradient mask) and the clamped one goes to img_out: no separate copy pass.
 __global__ __launch_bounds__(256) void k_finalize(int64_t npix, const float *img_raw, float *img_out, float *__restrict__ extra,
@@ -921,9 +1056,48 @@ int project_sh_bwd_views_impl(const char *what, int C, int accumulate, const Bwd
     return gc::check_launch(what);
 }
 
+int64_t pose_workgroups(int64_t N) { return N > 0 ? (N + 256 * POSE_ITEMS - 1) / (256 * POSE_ITEMS) : 0; }
+
 }  // namespace
 
 extern "C" {
+
+/* ---- Camera (pose) gradient of the front end: include/gaussctrl_pose.h.  One float32 partial [24] per (view, workgroup of 1024 Gaussians). */
+size_t gcx_pose_bwd_views_workspace_bytes(int64_t N, int C)
+{
+    if (N <= 0 || C < 1) return 0;
+    return (size_t)C * (size_t)pose_workgroups(N) * POSE_VALS * sizeof(float);
+}
+
+int gcx_pose_bwd_views(int64_t N, int C, int antialiased, const float *means, const float *log_scales, const float *quats,
+        const float *opacity_logits, const float *cams, int img_h, int img_w, const int32_t *radii, const float *conics, const float *v_xy,
+        const float *v_conic, const float *v_opac, const float *v_depths, void *workspace, float *out, void *stream)
+{
+    GC_REQUIRE(N >= 0 && C >= 1 && cams, "N >= 0, C >= 1; cams is a host pointer and must not be NULL");
+    GC_REQUIRE((int64_t)C * N * 3 < (1ll << 31), "C * N * 3 must be < 2^31 elements");
+    GC_REQUIRE(img_h > 0 && img_w > 0, "the image must not be empty");
+    GC_REQUIRE(out, "out is NULL");
+    if (N == 0) {
+        if (hipMemsetAsync(out, 0, (size_t)C * 2 * 12 * sizeof(float), gc::S(stream)) != hipSuccess) return gc::check_launch("gcx_pose_bwd_views");
+        return GC_OK;
+    }
+    GC_REQUIRE(means && log_scales && quats && opacity_logits && radii && conics, "an input pointer is NULL");
+    GC_REQUIRE(v_xy && v_conic && (v_opac || !antialiased), "a cotangent pointer is NULL (v_opac may be NULL only when antialiased == 0)");
+    GC_REQUIRE(workspace, "workspace is NULL");
+    const int64_t nblk = pose_workgroups(N);
+    float *partials = (float *)workspace;
+    for (int v0 = 0; v0 < C; v0 += MAXV) {
+        const CamBatch cb = make_cams(cams, v0, C - v0 < MAXV ? C - v0 : MAXV, img_h, img_w, 0, 0, 0.f);
+        const size_t o = (size_t)v0 * (size_t)N;
+        for_flag(antialiased != 0, [&](auto AA) {
+            hipLaunchKernelGGL((k_pose_bwd_views<decltype(AA)::value>), dim3((unsigned)nblk), dim3(256), 0, gc::S(stream), N, cb, nblk, means,
+                               log_scales, quats, opacity_logits, radii + o, conics + 3 * o, v_xy + 2 * o, v_conic + 3 * o,
+                               v_opac ? v_opac + o : nullptr, v_depths ? v_depths + o : nullptr, partials + (size_t)v0 * nblk * POSE_VALS);
+        });
+    }
+    hipLaunchKernelGGL(k_pose_sum, dim3((unsigned)C), dim3(256), 0, gc::S(stream), nblk, (const float *)partials, out);
+    return gc::check_launch("gcx_pose_bwd_views");
+}
 
 int gc_project_gaussians_fwd(int64_t N, const float *means3d, const float *scales, float glob_scale,
                              const float *quats, const float *viewmat, const float *projmat, float fx, float fy,

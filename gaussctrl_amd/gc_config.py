@@ -79,12 +79,18 @@ def scheduled_lr(group: str, step: int, table: dict | None = None) -> float:
 
 def build_optimizers(model, table: dict | None = None, step: int = 30000):
     """Adam per parameter group with the reference's learning rates / eps / schedules (gc_config.py:58-87) on the fused HIP Adam; a model
-    with use_bilateral_grid also gets the group "bilateral_grid" at config.bilagrid_lr, eps 1e-15, constant."""
+    with use_bilateral_grid also gets the group "bilateral_grid" at config.bilagrid_lr, eps 1e-15, constant.  A model with
+    camera_optimizer_mode "SO3xR3" has the group "camera_opt": the table's schedule, or config.camera_opt_lr (a number), eps 1e-15, constant."""
     from .train_ops import FusedAdam
     table = table or optimizer_table()
     groups = model.get_param_groups()
     opts = {name: FusedAdam(params, lr=scheduled_lr(name, step, table), eps=table[name]["optimizer"]["eps"])
             for name, params in groups.items() if name in table}
+    cam_lr = getattr(getattr(model, "config", None), "camera_opt_lr", None)
+    if "camera_opt" in groups and (cam_lr is not None or "camera_opt" not in table):
+        if cam_lr is None:
+            raise ValueError("the optimizer table has no group 'camera_opt': set GaussCtrlModelConfig.camera_opt_lr")
+        opts["camera_opt"] = FusedAdam(groups["camera_opt"], lr=float(cam_lr), eps=1e-15)
     if "bilateral_grid" in groups and "bilateral_grid" not in table:
         # use_bilateral_grid: a group of this implementation, outside the reference's table (optimizer_table() stays the reference's)
         opts["bilateral_grid"] = FusedAdam(groups["bilateral_grid"], lr=model.config.bilagrid_lr, eps=1e-15)

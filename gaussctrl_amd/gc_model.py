@@ -105,6 +105,18 @@ class GaussCtrlModelConfig(_ModelConfigBase):
     bilateral_grid_shape: tuple = (16, 16, 8)     # (GW, GH, L): vertices along x, y and luma; each at least 2
     bilagrid_tv_mult: float = 10.0                # loss += bilagrid_tv_mult * (total variation of all grids)   [gsplat's value, as recalled]
     bilagrid_lr: float = 2e-3                     # Adam learning rate of the group "bilateral_grid" (eps 1e-15)   [gsplat's value, as recalled]
+    camera_optimizer_mode: str = "off"            # "off": constant poses, the reference's behaviour; "SO3xR3" (stand-alone model, one GPU, gradients
+                                                  # through autograd): every training view owns a 6-vector (tau, omega) of the parameter
+                                                  # `pose_adjustment`, group "camera_opt"; in training mode the view named by
+                                                  # camera.metadata["cam_idx"] is rendered from c2w @ [exp(omega) | tau] and the renderer's view-matrix
+                                                  # gradient (ops.RenderAux.pose_grad, include/gaussctrl_pose.h) reaches the row
+                                                  # (gaussctrl_amd/camera_opt.py).  get_outputs_for_camera[s], render_reverse, metrics and evaluation
+                                                  # never see the adjustment.  Later splatfacto's camera_optimizer, conventions as recalled.  Under
+                                                  # nerfstudio the fields exist and are validated; the inherited behaviour stays
+    camera_opt_lr: Optional[float] = None         # None: the group "camera_opt" follows the optimizer table (the reference's 1e-3 -> 5e-5 schedule);
+                                                  # a number: constant Adam learning rate of the group (eps 1e-15), as bilagrid_lr
+    camera_opt_trans_l2_penalty: float = 1e-2     # loss += this * mean |tau|      [nerfstudio's default, as recalled]
+    camera_opt_rot_l2_penalty: float = 1e-3       # loss += this * mean |omega|    [nerfstudio's default, as recalled]
 
     def __post_init__(self):
         parent = getattr(super(), "__post_init__", None)
@@ -113,6 +125,7 @@ class GaussCtrlModelConfig(_ModelConfigBase):
         _antialiased(self.rasterize_mode)
         _mcmc(self.densify_strategy)
         _bilagrid(self)
+        _camera_opt(self)
 
 
 RASTERIZE_MODES = ("classic", "antialiased")
@@ -146,6 +159,12 @@ def _bilagrid(config) -> bool:
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0 or v == float("inf") or (name == "bilagrid_lr" and v == 0):
             raise ValueError(f"{name} must be a finite {'positive' if name == 'bilagrid_lr' else 'non-negative'} number, got {v!r}")
     return bool(getattr(config, "use_bilateral_grid", False))
+
+
+def _camera_opt(config) -> bool:
+    """camera_optimizer_mode with its three numbers checked; a wrong name, type or range is a ValueError"""
+    from .camera_opt import check_config
+    return check_config(config)
 
 
 class GaussCtrlModel(_ModelBase):
@@ -183,6 +202,12 @@ class GaussCtrlModel(_ModelBase):
             if isinstance(n, bool) or not isinstance(n, int) or n < 1:
                 raise ValueError(f"use_bilateral_grid needs num_train_data, the number of training views (a positive integer), got {n!r}")
             self.bilateral_grid = nn.Parameter(identity_grids(n, *config.bilateral_grid_shape, device=device))
+        if _camera_opt(config):
+            # one (tau, omega) row per training view, zero at the start: a parameter, so it is in state_dict and in its own group
+            n = kwargs.get("num_train_data")
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"camera_optimizer_mode 'SO3xR3' needs num_train_data, the number of training views (a positive integer), got {n!r}")
+            self.pose_adjustment = nn.Parameter(torch.zeros(n, 6, dtype=torch.float32, device=device))
 
     @property
     def device(self):
@@ -202,6 +227,8 @@ class GaussCtrlModel(_ModelBase):
                   "opacity": [self.opacities], "scaling": [self.scales], "rotation": [self.quats]}
         if getattr(self, "bilateral_grid", None) is not None:
             groups["bilateral_grid"] = [self.bilateral_grid]
+        if getattr(self, "pose_adjustment", None) is not None:
+            groups["camera_opt"] = [self.pose_adjustment]
         return groups
 
     def get_training_callbacks(self, training_callback_attributes):
@@ -244,7 +271,17 @@ class GaussCtrlModel(_ModelBase):
             if crop_ids.sum() == 0:
                 return {"rgb": background.repeat(H, W, 1)}
             p = [t[crop_ids] for t in p]
-        cam = camera_to_gsplat(camera.camera_to_worlds[0].detach().cpu().numpy(), float(camera.fx.reshape(-1)[0]),
+        c2w = camera.camera_to_worlds[0].detach().cpu().numpy()
+        pose = getattr(self, "pose_adjustment", None) if (not HAVE_NERFSTUDIO and self.training) else None
+        pose_row = None
+        if pose is not None:
+            # camera_optimizer_mode "SO3xR3": this view's pose, adjusted by its row (composed in float64 on the host; a zero row changes no bit)
+            from . import camera_opt
+            camera_opt.refuse_unsupported(self.config, train_mode="throughput" if getattr(self, "grad_into", None) is not None else "single",
+                                          crop_in_training=self.crop_box is not None)
+            pose_row = pose[camera_opt.check_view(camera, pose.shape[0])]
+            c2w_plain, c2w = c2w, camera_opt.adjusted_c2w(c2w, pose_row)
+        cam = camera_to_gsplat(c2w, float(camera.fx.reshape(-1)[0]),
                                float(camera.fy.reshape(-1)[0]), float(camera.cx.reshape(-1)[0]),
                                float(camera.cy.reshape(-1)[0]), W, H)        # :97-121 on the host
         self.last_size = (H, W)
@@ -260,6 +297,9 @@ class GaussCtrlModel(_ModelBase):
         aux.depth_grad = train_depth
         aux.absgrad = bool(self.training and getattr(self.config, "use_absgrad", False))
         want_depth = train_depth or not self.training
+        if pose_row is not None and torch.is_grad_enabled() and pose_row.requires_grad:
+            aux.pose_grad = True             # the projection backward also leaves aux.viewmat_grad, which the link chains to the row
+            p[0] = camera_opt.link(p[0], pose_row, aux, c2w_plain)
         rgb, alpha, depth = ops.render_view(*p, cam, background, want_depth, n, aux)
         self.xys, self.radii = aux.xys, aux.radii
         if aux.M == 0:                                                          # :155-156
@@ -331,13 +371,19 @@ class GaussCtrlModel(_ModelBase):
     def get_metrics_dict(self, outputs, batch) -> Dict[str, torch.Tensor]:
         gt = batch["image"].to(self.device)
         mse = ((outputs["rgb"] - gt) ** 2).mean()
-        return {"psnr": -10.0 * torch.log10(mse.clamp_min(1e-12)), "gaussian_count": torch.tensor(self.num_points)}
+        metrics = {"psnr": -10.0 * torch.log10(mse.clamp_min(1e-12)), "gaussian_count": torch.tensor(self.num_points)}
+        pose = getattr(self, "pose_adjustment", None) if not HAVE_NERFSTUDIO else None
+        if pose is not None:             # camera_optimizer_mode "SO3xR3": how far the poses have moved, mean over the views
+            metrics["camera_opt_translation"] = pose.detach()[:, :3].norm(dim=-1).mean()
+            metrics["camera_opt_rotation"] = pose.detach()[:, 3:].norm(dim=-1).mean()
+        return metrics
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, torch.Tensor]:
         """SplatfactoModel.get_loss_dict [recall, SURVEY 8a/A8]: (1-l)*L1 + l*(1-SSIM), l = 0.2.  The stand-alone model with
         config.densify_strategy = "mcmc" adds the strategy's two regularisers (plain torch: two reductions over N, not the hot path).
         The stand-alone model with config.use_bilateral_grid, in training mode, takes the main loss on the render sliced through the grid
-        of batch["image_idx"] and adds "tv_loss"; outputs["rgb"] itself, the metrics and everything at evaluation stay un-gridded."""
+        of batch["image_idx"] and adds "tv_loss"; outputs["rgb"] itself, the metrics and everything at evaluation stay un-gridded.
+        With config.camera_optimizer_mode = "SO3xR3" it adds, in training mode, "camera_opt_regularizer" (camera_opt.regularizer)."""
         from .train_ops import l1_ssim_loss
         gt = batch["image"].to(self.device)
         grid = getattr(self, "bilateral_grid", None) if (not HAVE_NERFSTUDIO and self.training) else None
@@ -352,4 +398,8 @@ class GaussCtrlModel(_ModelBase):
         if not HAVE_NERFSTUDIO and _mcmc(getattr(self.config, "densify_strategy", "default")):
             loss["opacity_reg"] = self.config.mcmc_opacity_reg * torch.sigmoid(self.opacities).mean()
             loss["scale_reg"] = self.config.mcmc_scale_reg * torch.exp(self.scales).mean()
+        pose = getattr(self, "pose_adjustment", None) if (not HAVE_NERFSTUDIO and self.training) else None
+        if pose is not None:             # camera_optimizer_mode "SO3xR3": keep the adjustments small (plain torch over [V, 6])
+            from .camera_opt import regularizer
+            loss["camera_opt_regularizer"] = regularizer(pose, self.config.camera_opt_trans_l2_penalty, self.config.camera_opt_rot_l2_penalty)
         return loss

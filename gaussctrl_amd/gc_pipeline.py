@@ -133,6 +133,7 @@ class GaussCtrlPipeline(_PipelineBase):
         self.mask_fn = mask_fn
         self._edit_region_traced()          # refuses the combinations "traced" does not cover before anything is loaded
         self._bilagrid_check()              # likewise use_bilateral_grid
+        self._camera_opt_check()            # likewise camera_optimizer_mode
         self.edit_prompt, self.reverse_prompt = config.edit_prompt, config.reverse_prompt
         added_prompt = "best quality, extremely detailed"                                        # :104-107
         self.positive_prompt = self.edit_prompt + ", " + added_prompt
@@ -242,6 +243,20 @@ class GaussCtrlPipeline(_PipelineBase):
         if grid is not None and td is not None and grid.shape[0] != len(td):
             raise ValueError(f"use_bilateral_grid: the model holds {grid.shape[0]} grids, the datamanager {len(td)} training views "
                              "(build the model with num_train_data=len(train_data))")
+
+    def _camera_opt_check(self) -> None:
+        """camera_optimizer_mode of the model's config, checked where it is read: under nerfstudio, more than one GPU, a train_mode that
+        writes the gradients into grad_into buffers, and a model whose rows do not match the training views, raise here"""
+        from . import camera_opt
+        m = self.model
+        multi = self.world_size > 1
+        camera_opt.refuse_unsupported(getattr(m, "config", None), self.world_size, getattr(self.config, "train_mode", "parity") if multi else "single",
+                                      HAVE_NERFSTUDIO)
+        rows = getattr(m, "pose_adjustment", None)
+        td = getattr(self.datamanager, "train_data", None)
+        if rows is not None and td is not None and rows.shape[0] != len(td):
+            raise ValueError(f"camera_optimizer_mode 'SO3xR3': the model holds {rows.shape[0]} pose rows, the datamanager {len(td)} training "
+                             "views (build the model with num_train_data=len(train_data))")
 
     @torch.no_grad()
     def trace_edit_region(self):
@@ -614,6 +629,8 @@ class GaussCtrlPipeline(_PipelineBase):
             raise ValueError("densify_strategy 'mcmc' trains on one GPU only (world_size > 1 is out of its scope)")
         from .bilagrid import refuse_unsupported as _refuse_bilagrid
         _refuse_bilagrid(getattr(self.model, "config", None), self.world_size)      # whatever train_mode says
+        from .camera_opt import refuse_unsupported as _refuse_camera_opt
+        _refuse_camera_opt(getattr(self.model, "config", None), self.world_size, self.config.train_mode if multi else "single", HAVE_NERFSTUDIO)
         mode = self.config.train_mode if multi else "single"
         if mode not in ("single", "parity", "throughput", "sharded"):
             raise ValueError(f"train_mode must be 'parity', 'throughput' or 'sharded', not {mode!r}")

@@ -120,6 +120,10 @@ else:
             table = self.config.optimizers or optimizer_table()
             if group == "bilateral_grid" and group not in table:       # use_bilateral_grid: outside the reference's table, constant (build_optimizers)
                 return float(self.pipeline.model.config.bilagrid_lr)
+            if group == "camera_opt":                                  # camera_optimizer_mode "SO3xR3": config.camera_opt_lr, when a number, is constant
+                cam_lr = getattr(getattr(self.pipeline.model, "config", None), "camera_opt_lr", None)
+                if cam_lr is not None:
+                    return float(cam_lr)
             return scheduled_lr(group, step, table)
 
         # -- gc_trainer.py:176-207 (no viewer lock / writers)

@@ -355,6 +355,14 @@ class RenderAux:
     # they are without it.  Combines freely with depth_grad, antialiased and grad_into (the projection backward is not involved).
     absgrad = False
     xys_absgrad = None
+    # camera pose refinement (include/gaussctrl_pose.h): True makes the projection backward also sum, over the Gaussians of every view, the
+    # gradient with respect to the view's camera matrices (gcx_pose_bwd_views, on the same v_xy / v_conic / v_opac / v_depths the leaf backward
+    # takes) and leave `viewmat_grad`: device float32 [C, 3, 4] (C = 1 from render_view), d loss / d viewmat[:3] of each `cam` dict, chained as
+    # v_V + (projmat4^T v_P)[:3] because camera_to_gsplat forms fullproj = projmat4 @ viewmat4.  None until a backward with the switch has run.
+    # The SH view directions move with the camera in the forward (cam["origin"]) but pass no gradient to the pose; they pass none to the means
+    # either.  With the switch off nothing new runs; on, every output and leaf gradient is computed by the same launches as without it.
+    pose_grad = False
+    viewmat_grad = None
 
 
 def _finalize(ctx, npix, img, dep, fT):
@@ -411,7 +419,7 @@ def _end_forward(ctx, aux, want_depth, meta, comp, saved, depths, dep, nth, M, b
     if aux is not None:
         aux.xys, aux.radii, aux.num_tiles_hit, aux.M, aux.depths, aux.tile_boxes = xys, radii, nth, M, depths, boxes
         aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
-        aux.xys_grad = aux.xys_absgrad = None
+        aux.xys_grad = aux.xys_absgrad = aux.viewmat_grad = None
         aux.compensation = comp
     ctx.meta, ctx.aux = meta, aux
     ctx.comp = comp          # (not an input or output of the function: kept as an attribute)
@@ -505,9 +513,57 @@ def _project_bwd(ctx, v_xy, v_conic, v_col, v_op, v_ex):
                 L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
                 L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
                 L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
+    if ctx.aux is not None and ctx.aux.pose_grad:
+        ctx.aux.viewmat_grad = _pose_bwd(ctx, v_xy, v_conic, v_op, v_ex)
     if into is not None:
         return (None,) * 11
     return vm, vls, vq, vop[:, None], vdc, vrest, None, None, None, None, None
+
+
+def pose_bwd_views(means, log_scales, quats, opacity_logits, cams, radii, conics, v_xy, v_conic, v_opac=None, v_depths=None, antialiased=False):
+    """gcx_pose_bwd_views (include/gaussctrl_pose.h) on device tensors laid out as the fused render keeps them: radii [C, N] (or [N] for one
+    camera), conics, v_xy, v_conic, v_opac, v_depths alike; cams: the list of `cam` dicts.  Returns the raw sums, float32 [C, 2, 3, 4]:
+    [:, 0] = v_V, [:, 1] = rows 0, 1, 3 of v_P (row 2 is identically zero)."""
+    _need_gpu(means, radii)
+    N, C = means.shape[0], len(cams)
+    H, W = cams[0]["H"], cams[0]["W"]
+    lib = L.lib()
+    nbytes = int(lib.gcx_pose_bwd_views_workspace_bytes(L.i64(N), L.i32(C)))
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=means.device)
+    out = torch.empty(C, 2, 3, 4, dtype=torch.float32, device=means.device)
+    L.check(lib.gcx_pose_bwd_views(
+        L.i64(N), L.i32(C), L.i32(1 if antialiased else 0), L.ptr(means), L.ptr(log_scales), L.ptr(quats), L.ptr(opacity_logits),
+        _cams_host(cams), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_opac), L.ptr(v_depths),
+        L.ptr(ws), L.ptr(out), L.stream_ptr()), "gcx_pose_bwd_views")
+    return out
+
+
+def chain_viewmat_grad(raw, cams):
+    """raw [C, 2, 3, 4] of pose_bwd_views -> d / d viewmat[:3] per view, float32 [C, 3, 4]: v_V + (projmat4^T v_P4)[:3] with v_P4 = v_P and a zero
+    row 2 (camera_to_gsplat: fullproj = projmat4 @ viewmat4).  Sixteen multiply-adds per entry, taken in float64."""
+    import numpy as np
+    # [C, 3, 3]: rows 0..2 of projmat4^T, columns 0, 1, 3 (the rows of v_P that exist).  Kept on the device per set of projection matrices:
+    # a training run has one or a few, and an upload per backward would make the host wait for the stream
+    proj = [np.asarray(c["projmat4"], dtype=np.float64) for c in cams]
+    key = (str(raw.device),) + tuple(p.tobytes() for p in proj)
+    PT = _proj_t_cache.get(key)
+    if PT is None:
+        if len(_proj_t_cache) >= 16:
+            _proj_t_cache.clear()
+        PT = _proj_t_cache[key] = torch.from_numpy(np.stack([p.T[:3][:, [0, 1, 3]] for p in proj])).to(raw.device)
+    r = raw.double()
+    return (r[:, 0] + PT @ r[:, 1]).float()
+
+
+_proj_t_cache = {}
+
+
+def _pose_bwd(ctx, v_xy, v_conic, v_op, v_ex):
+    """RenderAux.pose_grad: the camera gradient of the views of this render, from the cotangents the projection backward was just handed"""
+    m, ls, q, op, _, _, radii, conics = ctx.saved_tensors[:8]
+    aa = ctx.comp is not None
+    raw = pose_bwd_views(m, ls, q, op, ctx.meta.cams, radii, conics, v_xy, v_conic, v_op if aa else None, v_ex, aa)
+    return chain_viewmat_grad(raw, ctx.meta.cams)
 
 
 def _render_bwd(ctx, v_img, v_alpha, v_dep):
