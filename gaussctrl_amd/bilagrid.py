@@ -14,8 +14,6 @@ edited views lands in the grids instead of in floaters and view-dependent SH.
 Opt-in: GaussCtrlModelConfig.use_bilateral_grid (stand-alone model)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
@@ -78,10 +76,9 @@ class _Apply(torch.autograd.Function):
             raise ValueError(f"bilagrid_apply: {Cn} images, {len(view_idx)} view indices")
         g = grids.detach().float().contiguous()
         x = rgb.detach().float().contiguous()
-        idx = (C.c_int32 * Cn)(*view_idx)
+        idx = (L.C.c_int32 * Cn)(*view_idx)
         out = torch.empty(Cn, H, W, 3, dtype=torch.float32, device=x.device)
-        L.check(L.lib().gcx_bilagrid_slice_fwd_views(L.i32(Cn), L.i32(H), L.i32(W), L.i32(V), L.i32(GW), L.i32(GH), L.i32(Lz), L.ptr(g), L.ptr(x),
-                                                     idx, L.ptr(out), L.stream_ptr()), "gcx_bilagrid_slice_fwd_views")
+        L.call("gcx_bilagrid_slice_fwd_views", Cn, H, W, V, GW, GH, Lz, g, x, idx, out)
         ctx.save_for_backward(g, x)
         ctx.view_idx = idx
         return out
@@ -94,9 +91,7 @@ class _Apply(torch.autograd.Function):
         v = v_out.detach().float().contiguous()
         v_grids = torch.zeros(V, 12, Lz, GH, GW, dtype=torch.float32, device=x.device)
         v_rgb = torch.empty(Cn, H, W, 3, dtype=torch.float32, device=x.device)
-        L.check(L.lib().gcx_bilagrid_slice_bwd_views(L.i32(Cn), L.i32(H), L.i32(W), L.i32(V), L.i32(GW), L.i32(GH), L.i32(Lz), L.ptr(g), L.ptr(x),
-                                                     ctx.view_idx, L.ptr(v), L.ptr(v_grids), L.ptr(v_rgb), L.stream_ptr()),
-                "gcx_bilagrid_slice_bwd_views")
+        L.call("gcx_bilagrid_slice_bwd_views", Cn, H, W, V, GW, GH, Lz, g, x, ctx.view_idx, v, v_grids, v_rgb)
         return v_grids, v_rgb, None
 
 
@@ -122,11 +117,9 @@ class _TV(torch.autograd.Function):
         g = grids.detach().float().contiguous()
         tv = torch.zeros(1, dtype=torch.float32, device=g.device)
         v = torch.zeros(V, 12, Lz, GH, GW, dtype=torch.float32, device=g.device)
-        lib = L.lib()
-        nbytes = lib.gcx_bilagrid_tv_workspace_bytes(L.i32(V), L.i32(GW), L.i32(GH), L.i32(Lz))
+        nbytes = L.call("gcx_bilagrid_tv_workspace_bytes", V, GW, GH, Lz)
         ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=g.device)
-        L.check(lib.gcx_bilagrid_tv_fwd_bwd(L.i32(V), L.i32(GW), L.i32(GH), L.i32(Lz), L.ptr(g), L.f32(1.0), L.ptr(tv), L.ptr(v), L.ptr(ws),
-                                            C.c_size_t(nbytes), L.stream_ptr()), "gcx_bilagrid_tv_fwd_bwd")
+        L.call("gcx_bilagrid_tv_fwd_bwd", V, GW, GH, Lz, g, 1.0, tv, v, ws, nbytes)
         ctx.save_for_backward(v)
         return tv[0]
 

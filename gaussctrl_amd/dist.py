@@ -359,8 +359,7 @@ def _hip_adam(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
     from . import _lib as L
     if not param.is_cuda:
         raise L.GaussCtrlHipError("ShardedAdam: the fused Adam kernel needs GPU tensors")
-    L.check(L.lib().gc_adam_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.i64(param.numel()), L.f32(lr), L.f32(beta1), L.f32(beta2),
-                                 L.f32(eps), L.i32(step), L.stream_ptr()), "gc_adam_step")
+    L.call("gc_adam_step", param, grad, exp_avg, exp_avg_sq, param.numel(), lr, beta1, beta2, eps, step)
 
 
 class ShardedAdam:

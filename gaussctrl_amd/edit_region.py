@@ -63,8 +63,7 @@ def select(w_in, w_all, ratio_thresh: float = 0.5, min_weight: float = 0.0):
         raise ValueError("edit_region.select: w_in and w_all must be contiguous float32 tensors of one length")
     sel = torch.empty(N, dtype=torch.uint8, device=w_in.device)
     count = torch.empty(1, dtype=torch.int32, device=w_in.device)
-    L.check(L.lib().gc_trace_select(L.i64(N), L.ptr(w_in), L.ptr(w_all), L.f32(ratio_thresh), L.f32(min_weight), L.ptr(sel), L.ptr(count),
-                                    L.stream_ptr()), "gc_trace_select")
+    L.call("gc_trace_select", N, w_in, w_all, ratio_thresh, min_weight, sel, count)
     return sel, int(count.item())
 
 

@@ -36,10 +36,7 @@ def num_sh_bases(degree: int) -> int:
     return 25
 
 
-def _need_gpu(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise L.GaussCtrlHipError("gaussctrl_amd ops need GPU tensors (HIP path only; no CPU fallback)")
+_need_gpu = L.need_gpu
 
 
 def _c(t, dtype=torch.float32):
@@ -70,10 +67,8 @@ class _ProjectGaussians(torch.autograd.Function):
         cov3d = torch.empty(N, 6, device=dev); xys = torch.empty(N, 2, device=dev); depths = torch.empty(N, device=dev)
         radii = torch.empty(N, dtype=torch.int32, device=dev); conics = torch.empty(N, 3, device=dev)
         nth = torch.empty(N, dtype=torch.int32, device=dev)
-        L.check(L.lib().gc_project_gaussians_fwd(
-            L.i64(N), L.ptr(m), L.ptr(s), L.f32(glob_scale), L.ptr(q), V, P, L.f32(fx), L.f32(fy), L.f32(cx), L.f32(cy),
-            L.i32(H), L.i32(W), L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.f32(clip), L.ptr(cov3d), L.ptr(xys),
-            L.ptr(depths), L.ptr(radii), L.ptr(conics), L.ptr(nth), L.stream_ptr()), "gc_project_gaussians_fwd")
+        L.call("gc_project_gaussians_fwd", N, m, s, glob_scale, q, V, P, fx, fy, cx, cy, H, W, tile_bounds[0], tile_bounds[1], clip,
+               cov3d, xys, depths, radii, conics, nth)
         ctx.save_for_backward(m, s, q, radii, conics)
         ctx.cam = (V, P, float(glob_scale), float(fx), float(fy), float(cx), float(cy), int(H), int(W))
         ctx.mark_non_differentiable(radii, nth)
@@ -89,10 +84,7 @@ class _ProjectGaussians(torch.autograd.Function):
         v_con = _c(v_conics) if v_conics is not None else torch.zeros(N, 3, device=dev)
         v_dep = _c(v_depths) if v_depths is not None else None
         vm = torch.empty(N, 3, device=dev); vs = torch.empty(N, 3, device=dev); vq = torch.empty(N, 4, device=dev)
-        L.check(L.lib().gc_project_gaussians_bwd(
-            L.i64(N), L.ptr(m), L.ptr(s), L.f32(glob), L.ptr(q), V, P, L.f32(fx), L.f32(fy), L.f32(cx), L.f32(cy),
-            L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_dep), L.ptr(v_con), L.ptr(vm),
-            L.ptr(vs), L.ptr(vq), L.stream_ptr()), "gc_project_gaussians_bwd")
+        L.call("gc_project_gaussians_bwd", N, m, s, glob, q, V, P, fx, fy, cx, cy, H, W, radii, conics, v_xy, v_dep, v_con, vm, vs, vq)
         return (vm, vs, None, vq) + (None,) * 10
 
 
@@ -112,8 +104,7 @@ class _SphericalHarmonics(torch.autograd.Function):
         degree = {1: 0, 4: 1, 9: 2, 16: 3}[K]
         d, c = _c(viewdirs), _c(coeffs)
         out = torch.empty(N, 3, device=coeffs.device)
-        L.check(L.lib().gc_sh_fwd(L.i64(N), L.i32(degree), L.i32(degrees_to_use), L.ptr(d), L.ptr(c), L.ptr(out),
-                                  L.stream_ptr()), "gc_sh_fwd")
+        L.call("gc_sh_fwd", N, degree, degrees_to_use, d, c, out)
         ctx.save_for_backward(d)
         ctx.meta = (degree, int(degrees_to_use), K)
         return out
@@ -125,8 +116,7 @@ class _SphericalHarmonics(torch.autograd.Function):
         N = d.shape[0]
         vc = _c(v_colors)
         out = torch.empty(N, K, 3, device=d.device)
-        L.check(L.lib().gc_sh_bwd(L.i64(N), L.i32(degree), L.i32(n), L.ptr(d), L.ptr(vc), L.ptr(out), L.stream_ptr()),
-                "gc_sh_bwd")
+        L.call("gc_sh_bwd", N, degree, n, d, vc, out)
         return None, None, out
 
 
@@ -143,74 +133,65 @@ def bin_and_sort_gaussians(N, xys, depths, radii, num_tiles_hit, tile_bounds, wa
     cum_tiles_hit_in_depth_order).  One 4-byte readback (M).
     tile_boxes: the packed tight boxes of gc_project_sh_fwd_boxes (num_tiles_hit must be the counts it wrote): the emission walks
     them instead of the boxes recomputed from xys / radii -- fewer pairs, bit-identical images (fused product path)."""
-    lib = L.lib()
     dev = xys.device
-    st = L.stream_ptr()
     T = tile_bounds[0] * tile_bounds[1]
     order = torch.empty(N, dtype=torch.int32, device=dev)
     cum = torch.empty(N, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
-    wb = int(lib.gc_raster_depth_order_workspace_bytes(L.i64(N)))
+    wb = L.call("gc_raster_depth_order_workspace_bytes", N)
     ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-    L.check(lib.gc_raster_depth_order(L.i64(N), L.ptr(depths), L.ptr(radii), L.ptr(num_tiles_hit), L.ptr(order), L.ptr(cum),
-                                      L.ptr(cnt), L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_depth_order")
+    L.call("gc_raster_depth_order", N, depths, radii, num_tiles_hit, order, cum, cnt, ws, wb)
     bins = torch.empty(T, 2, dtype=torch.int32, device=dev)
     if m_cap is not None:
         # sync-free: buffers sized for the caller's capacity, count and overflow flag stay on the device.
         # Returns M = (count tensor, overflow tensor) instead of a host int.
         M = int(m_cap)
         ovf = torch.empty(1, dtype=torch.int32, device=dev)
-        dev_cnt, ret_M = (L.ptr(cnt), L.ptr(ovf)), (cnt, ovf)
+        dev_cnt = ret_M = (cnt, ovf)
     else:
-        m_host = L.C.c_int32(0)
-        L.check(lib.gc_raster_read_count(L.ptr(cnt), L.C.byref(m_host), st), "gc_raster_read_count")
-        M = int(m_host.value)
+        M = _read_count(cnt)
         dev_cnt, ret_M = (None, None), M
     ids_s = torch.empty(M, dtype=torch.int32, device=dev)
     keys_s = torch.empty(M, dtype=torch.int64, device=dev) if want_keys else None
-    bb = int(lib.gc_raster_bin_workspace_bytes(L.i64(M)))
+    bb = L.call("gc_raster_bin_workspace_bytes", M)
     bws = torch.empty(bb, dtype=torch.uint8, device=dev)
-    out = (L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(keys_s), L.ptr(bws), L.C.c_size_t(bb), st)
+    lead, out = (N, M), (tile_bounds[0], tile_bounds[1], ids_s, bins, keys_s, bws, bb)
     if tile_boxes is not None:
-        L.check(lib.gc_raster_bin_tiles_boxes(L.i64(N), L.i64(M), *dev_cnt, L.ptr(order), L.ptr(cum), L.ptr(tile_boxes), L.ptr(depths), *out),
-                "gc_raster_bin_tiles_boxes")
+        L.call("gc_raster_bin_tiles_boxes", *lead, *dev_cnt, order, cum, tile_boxes, depths, *out)
     elif m_cap is not None:
-        L.check(lib.gc_raster_bin_tiles_dev(L.i64(N), L.i64(M), *dev_cnt, L.ptr(order), L.ptr(cum), L.ptr(xys), L.ptr(depths), L.ptr(radii), *out),
-                "gc_raster_bin_tiles_dev")
+        L.call("gc_raster_bin_tiles_dev", *lead, *dev_cnt, order, cum, xys, depths, radii, *out)
     else:
-        L.check(lib.gc_raster_bin_tiles(L.i64(N), L.i64(M), L.ptr(order), L.ptr(cum), L.ptr(xys), L.ptr(depths), L.ptr(radii), *out),
-                "gc_raster_bin_tiles")
+        L.call("gc_raster_bin_tiles", *lead, order, cum, xys, depths, radii, *out)
     return ret_M, keys_s, ids_s, bins, cum
+
+
+def _read_count(cnt):
+    """the one blocking 4-byte read-back (gc_raster_read_count) of a device counter, as a host int"""
+    m_host = L.C.c_int32(0)
+    L.call("gc_raster_read_count", cnt, L.C.byref(m_host))
+    return int(m_host.value)
 
 
 def bin_and_sort_gaussians_keys64(N, xys, depths, radii, num_tiles_hit, tile_bounds):
     """gsplat-shaped chain: cumsum -> map -> 64-bit key sort -> tile bins (kept for API parity / cross-checks).
     Returns (M, isect_ids_sorted, gaussian_ids_sorted, tile_bins, cum_tiles_hit)."""
-    lib = L.lib()
     dev = xys.device
-    st = L.stream_ptr()
     T = tile_bounds[0] * tile_bounds[1]
     cum = torch.empty(N, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = lib.gc_raster_scan_workspace_bytes(L.i64(N))
+    ws_bytes = L.call("gc_raster_scan_workspace_bytes", N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    L.check(lib.gc_raster_scan_tiles(L.i64(N), L.ptr(num_tiles_hit), L.ptr(cum), L.ptr(cnt), L.ptr(ws),
-                                     L.C.c_size_t(ws_bytes), st), "gc_raster_scan_tiles")
-    m_host = L.C.c_int32(0)
-    L.check(lib.gc_raster_read_count(L.ptr(cnt), L.C.byref(m_host), st), "gc_raster_read_count")
-    M = int(m_host.value)
+    L.call("gc_raster_scan_tiles", N, num_tiles_hit, cum, cnt, ws, ws_bytes)
+    M = _read_count(cnt)
     bins = torch.empty(T, 2, dtype=torch.int32, device=dev)
     keys = torch.empty(M, dtype=torch.int64, device=dev); ids = torch.empty(M, dtype=torch.int32, device=dev)
     keys_s = torch.empty(M, dtype=torch.int64, device=dev); ids_s = torch.empty(M, dtype=torch.int32, device=dev)
     if M > 0:
-        L.check(lib.gc_raster_map_intersects(L.i64(N), L.i64(M), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(cum),
-                                             L.i32(tile_bounds[0]), L.i32(tile_bounds[1]), L.ptr(keys), L.ptr(ids), st),
-                "gc_raster_map_intersects")
-        sb = lib.gc_raster_sort_workspace_bytes(L.i64(M), L.i32(T))
-        sws = torch.empty(max(int(sb), 1), dtype=torch.uint8, device=dev)
-        L.check(lib.gc_raster_sort_intersects(L.i64(M), L.i32(T), L.ptr(keys), L.ptr(ids), L.ptr(keys_s), L.ptr(ids_s),
-                                              L.ptr(sws), L.C.c_size_t(int(sb)), st), "gc_raster_sort_intersects")
-    L.check(lib.gc_raster_tile_bins(L.i64(M), L.i32(T), L.ptr(keys_s), L.ptr(bins), st), "gc_raster_tile_bins")
+        L.call("gc_raster_map_intersects", N, M, xys, depths, radii, cum, tile_bounds[0], tile_bounds[1], keys, ids)
+        sb = L.call("gc_raster_sort_workspace_bytes", M, T)
+        sws = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+        L.call("gc_raster_sort_intersects", M, T, keys, ids, keys_s, ids_s, sws, sb)
+    L.call("gc_raster_tile_bins", M, T, keys_s, bins)
     return M, keys_s, ids_s, bins, cum
 
 
@@ -220,10 +201,7 @@ def _rasterize_fwd(H, W, tb, ids_s, bins, xys, conics, colors, opac, extra, back
     out_e = torch.empty(H, W, device=dev) if extra is not None else None
     fT = torch.empty(H, W, device=dev)
     fi = torch.empty(H, W, dtype=torch.int32, device=dev)
-    L.check(L.lib().gc_rasterize_fwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins),
-                                     L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(extra),
-                                     L.ptr(background), L.ptr(out), L.ptr(out_e), L.ptr(fT), L.ptr(fi), L.stream_ptr()),
-            "gc_rasterize_fwd")
+    L.call("gc_rasterize_fwd", H, W, tb[0], tb[1], ids_s, bins, xys, conics, colors, opac, extra, background, out, out_e, fT, fi)
     return out, out_e, fT, fi
 
 
@@ -231,10 +209,8 @@ def _rasterize_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, backgrou
     dev = xys.device
     v_xy = torch.zeros(N, 2, device=dev); v_conic = torch.zeros(N, 3, device=dev)
     v_col = torch.zeros(N, 3, device=dev); v_op = torch.zeros(N, device=dev)
-    L.check(L.lib().gc_rasterize_bwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.ptr(ids_s), L.ptr(bins),
-                                     L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT),
-                                     L.ptr(fi), L.ptr(v_out), L.ptr(v_alpha), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col),
-                                     L.ptr(v_op), L.stream_ptr()), "gc_rasterize_bwd")
+    L.call("gc_rasterize_bwd", H, W, tb[0], tb[1], N, ids_s, bins, xys, conics, colors, opac, background, fT, fi, v_out, v_alpha,
+           v_xy, v_conic, v_col, v_op)
     return v_xy, v_conic, v_col, v_op
 
 
@@ -245,9 +221,7 @@ def _rasterize_nd_fwd(H, W, tb, ids_s, bins, xys, conics, colors, opac, backgrou
     out = torch.empty(H, W, C, device=dev)
     fT = torch.empty(H, W, device=dev)
     fi = torch.empty(H, W, dtype=torch.int32, device=dev)
-    L.check(L.lib().gc_rasterize_nd_fwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i32(C), L.ptr(ids_s), L.ptr(bins),
-                                        L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(out),
-                                        L.ptr(fT), L.ptr(fi), L.stream_ptr()), "gc_rasterize_nd_fwd")
+    L.call("gc_rasterize_nd_fwd", H, W, tb[0], tb[1], C, ids_s, bins, xys, conics, colors, opac, background, out, fT, fi)
     return out, fT, fi
 
 
@@ -256,10 +230,8 @@ def _rasterize_nd_bwd(H, W, tb, N, ids_s, bins, xys, conics, colors, opac, backg
     C = colors.shape[1]
     v_xy = torch.zeros(N, 2, device=dev); v_conic = torch.zeros(N, 3, device=dev)
     v_col = torch.zeros(N, C, device=dev); v_op = torch.zeros(N, device=dev)
-    L.check(L.lib().gc_rasterize_nd_bwd(L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.i64(N), L.i32(C), L.ptr(ids_s), L.ptr(bins),
-                                        L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opac), L.ptr(background), L.ptr(fT), L.ptr(fi),
-                                        L.ptr(v_out), L.ptr(v_alpha), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
-                                        L.stream_ptr()), "gc_rasterize_nd_bwd")
+    L.call("gc_rasterize_nd_bwd", H, W, tb[0], tb[1], N, C, ids_s, bins, xys, conics, colors, opac, background, fT, fi, v_out, v_alpha,
+           v_xy, v_conic, v_col, v_op)
     return v_xy, v_conic, v_col, v_op
 
 
@@ -371,10 +343,9 @@ def _finalize(ctx, npix, img, dep, fT):
     alpha = torch.empty_like(fT)
     if any(ctx.needs_input_grad[:6]):
         pre_clamp, img = img, torch.empty_like(img)
-        L.check(L.lib().gc_raster_finalize_into(L.i64(npix), L.ptr(pre_clamp), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), L.stream_ptr()),
-                "gc_raster_finalize_into")
+        L.call("gc_raster_finalize_into", npix, pre_clamp, img, dep, fT, alpha)
         return img, alpha, pre_clamp
-    L.check(L.lib().gc_raster_finalize(L.i64(npix), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(alpha), L.stream_ptr()), "gc_raster_finalize")
+    L.call("gc_raster_finalize", npix, img, dep, fT, alpha)
     return img, alpha, None
 
 
@@ -451,26 +422,15 @@ def _composite_bwd(ctx, v_img, v_alpha, v_dep):
     vbuf = torch.zeros(C * N * sum(w for _, w in parts), device=dev)
     v = {k: t.view(*lead, *((w,) if w > 1 else ())) for (k, w), t in zip(parts, vbuf.split([C * N * w for _, w in parts]))}
     v_xy, v_conic, v_col, v_op, v_ex, v_abs = (v.get(k) for k in ("v_xy", "v_conic", "v_col", "v_op", "v_ex", "v_abs"))
-    lib = L.lib()
-    st = L.stream_ptr()
     # (clamp(max=1) backward, gc_model.py:188: applied by the kernel when it loads the pixel's gradient)
+    plain = (C, N, M_cap, shared_op, shared_bg, H, W, tb[0], tb[1], ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp,
+             v_xy, v_conic, v_col, v_op)
     if absgrad:                 # one entry point for both depth forms (NULL quartet = no depth)
-        L.check(lib.gc_rasterize_bwd_abs_views(
-            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-            L.ptr(v_ex), L.ptr(v_abs), st), "gc_rasterize_bwd_abs_views")
+        L.call("gc_rasterize_bwd_abs_views", *plain, depths, dep, vd, v_ex, v_abs)
     elif vd is not None:
-        L.check(lib.gc_rasterize_bwd_depth_views(
-            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(depths), L.ptr(dep), L.ptr(vd),
-            L.ptr(v_ex), st), "gc_rasterize_bwd_depth_views")
+        L.call("gc_rasterize_bwd_depth_views", *plain, depths, dep, vd, v_ex)
     else:
-        L.check(lib.gc_rasterize_bwd_views(
-            L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s),
-            L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac), L.ptr(bg), L.ptr(fT), L.ptr(fi), L.ptr(vo), L.ptr(va),
-            L.ptr(pre_clamp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), st), "gc_rasterize_bwd_views")
+        L.call("gc_rasterize_bwd_views", *plain)
     if ctx.aux is not None:
         ctx.aux.xys_grad = v_xy
         if absgrad:
@@ -485,34 +445,21 @@ def _project_bwd(ctx, v_xy, v_conic, v_col, v_op, v_ex):
     mt = ctx.meta
     C, N, H, W, sh_degree, n_use = mt.C, mt.N, mt.H, mt.W, mt.sh_degree, mt.n_use
     (vm, vls, vq, vop, vdc, vrest), into, acc = _leaf_grad_buffers(ctx.aux, m, ls, q, dc, rest)
-    lib = L.lib()
-    st = L.stream_ptr()
+    grads = (v_xy, v_conic, v_col, v_op, vm, vls, vq, vop, vdc, vrest)
     if mt.single and ctx.comp is None and v_ex is None:
         cam = mt.cams[0]
-        fn = lib.gc_project_sh_bwd_accumulate if acc else lib.gc_project_sh_bwd
-        L.check(fn(
-            L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), L.host_floats(cam["viewmat"]),
-            L.host_floats(cam["fullproj"]), L.host_floats(cam["origin"]), L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]),
-            L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-            L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_accumulate" if acc else "gc_project_sh_bwd")
+        L.call("gc_project_sh_bwd_accumulate" if acc else "gc_project_sh_bwd", N, m, ls, q, op, rgbs, sh_degree, n_use,
+               L.host_floats(cam["viewmat"]), L.host_floats(cam["fullproj"]), L.host_floats(cam["origin"]), cam["fx"], cam["fy"], cam["cx"],
+               cam["cy"], H, W, radii, conics, *grads)
     else:
         CH = mt.cams_host if mt.cams_host is not None else _cams_host(mt.cams)
-        acc = int(acc)
+        lead = (N, C, int(acc), m, ls, q, op, rgbs, sh_degree, n_use, CH, H, W, radii, conics)
         if ctx.comp is not None:    # antialiased: v_op is of the per-view effective opacities; v_depths may be NULL
-            L.check(lib.gc_project_sh_bwd_aa_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(ctx.comp), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op),
-                L.ptr(vm), L.ptr(vls), L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_aa_views")
+            L.call("gc_project_sh_bwd_aa_views", *lead, ctx.comp, *grads, v_ex)
         elif v_ex is not None:      # the compositing's v_extra is the projection's v_depths
-            L.check(lib.gc_project_sh_bwd_depth_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), L.ptr(v_ex), st), "gc_project_sh_bwd_depth_views")
+            L.call("gc_project_sh_bwd_depth_views", *lead, *grads, v_ex)
         else:
-            L.check(lib.gc_project_sh_bwd_views(
-                L.i64(N), L.i32(C), L.i32(acc), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(rgbs), L.i32(sh_degree), L.i32(n_use), CH,
-                L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_col), L.ptr(v_op), L.ptr(vm), L.ptr(vls),
-                L.ptr(vq), L.ptr(vop), L.ptr(vdc), L.ptr(vrest), st), "gc_project_sh_bwd_views")
+            L.call("gc_project_sh_bwd_views", *lead, *grads)
     if ctx.aux is not None and ctx.aux.pose_grad:
         ctx.aux.viewmat_grad = _pose_bwd(ctx, v_xy, v_conic, v_op, v_ex)
     if into is not None:
@@ -527,14 +474,11 @@ def pose_bwd_views(means, log_scales, quats, opacity_logits, cams, radii, conics
     _need_gpu(means, radii)
     N, C = means.shape[0], len(cams)
     H, W = cams[0]["H"], cams[0]["W"]
-    lib = L.lib()
-    nbytes = int(lib.gcx_pose_bwd_views_workspace_bytes(L.i64(N), L.i32(C)))
+    nbytes = L.call("gcx_pose_bwd_views_workspace_bytes", N, C)
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=means.device)
     out = torch.empty(C, 2, 3, 4, dtype=torch.float32, device=means.device)
-    L.check(lib.gcx_pose_bwd_views(
-        L.i64(N), L.i32(C), L.i32(1 if antialiased else 0), L.ptr(means), L.ptr(log_scales), L.ptr(quats), L.ptr(opacity_logits),
-        _cams_host(cams), L.i32(H), L.i32(W), L.ptr(radii), L.ptr(conics), L.ptr(v_xy), L.ptr(v_conic), L.ptr(v_opac), L.ptr(v_depths),
-        L.ptr(ws), L.ptr(out), L.stream_ptr()), "gcx_pose_bwd_views")
+    L.call("gcx_pose_bwd_views", N, C, 1 if antialiased else 0, means, log_scales, quats, opacity_logits, _cams_host(cams), H, W, radii, conics,
+           v_xy, v_conic, v_opac, v_depths, ws, out)
     return out
 
 
@@ -576,8 +520,6 @@ class _RenderView(torch.autograd.Function):
     def forward(ctx, means, log_scales, quats, opacities, features_dc, features_rest, cam, background, want_depth,
                 sh_degree_to_use, aux):
         _need_gpu(means)
-        lib = L.lib()
-        st = L.stream_ptr()
         N = means.shape[0]
         dev = means.device
         H, W = cam["H"], cam["W"]
@@ -594,23 +536,15 @@ class _RenderView(torch.autograd.Function):
         aa = bool(aux is not None and aux.antialiased)
         comp = torch.empty(N, device=dev) if aa else None
         if aa:         # opac is this view's sigmoid(logit) * rho: what the compositing kernels and the tight boxes see
-            L.check(lib.gc_project_sh_fwd_aa_views(
-                L.i64(N), L.i32(1), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree),
-                L.i32(sh_degree_to_use), _cams_host([cam]), L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys),
-                L.ptr(depths), L.ptr(radii), L.ptr(conics), L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), None, st),
-                "gc_project_sh_fwd_aa_views")
-        elif tight:
-            L.check(lib.gc_project_sh_fwd_boxes(
-                L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree),
-                L.i32(sh_degree_to_use), V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]),
-                L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii),
-                L.ptr(conics), L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), st), "gc_project_sh_fwd_boxes")
+            L.call("gc_project_sh_fwd_aa_views", N, 1, m, ls, q, op, dc, rest, sh_degree, sh_degree_to_use, _cams_host([cam]), H, W, tb[0], tb[1],
+                   0.01, xys, depths, radii, conics, nth, rgbs, opac, comp, boxes, None)
         else:
-            L.check(lib.gc_project_sh_fwd(
-                L.i64(N), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree),
-                L.i32(sh_degree_to_use), V, P, O, L.f32(cam["fx"]), L.f32(cam["fy"]), L.f32(cam["cx"]), L.f32(cam["cy"]),
-                L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii),
-                L.ptr(conics), L.ptr(nth), L.ptr(rgbs), L.ptr(opac), st), "gc_project_sh_fwd")
+            plain = (N, m, ls, q, op, dc, rest, sh_degree, sh_degree_to_use, V, P, O, cam["fx"], cam["fy"], cam["cx"], cam["cy"], H, W, tb[0], tb[1],
+                     0.01, xys, depths, radii, conics, nth, rgbs, opac)
+            if tight:
+                L.call("gc_project_sh_fwd_boxes", *plain, boxes)
+            else:
+                L.call("gc_project_sh_fwd", *plain)
         M, keys_s, ids_s, bins, _ = bin_and_sort_gaussians(N, xys, depths, radii, nth, tb, m_cap=None if aux is None else aux.m_cap,
                                                            tile_boxes=boxes)
         bg = _c(background)
@@ -644,8 +578,6 @@ def _views_front(means, log_scales, quats, opacities, features_dc, features_rest
     """Projection / SH, depth order and binning of C cameras of one scene: tight boxes, the sorted-boxes chain (or the pair chain with
     aux.sorted_boxes = False), the antialiased per-view opacities when aux.antialiased."""
     _need_gpu(means)
-    lib = L.lib()
-    st = L.stream_ptr()
     N = means.shape[0]
     dev = means.device
     C = len(cams)
@@ -665,29 +597,23 @@ def _views_front(means, log_scales, quats, opacities, features_dc, features_rest
     shared_op = 0 if aa else 1          # antialiased: per-view effective opacities [C][N], the compositing kernels' shared_opacities = 0
     if aa:
         opac = torch.empty(C, N, **f32); comp = torch.empty(C, N, **f32)
-        L.check(lib.gc_project_sh_fwd_aa_views(
-            L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
-            CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
-            L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(comp), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_aa_views")
+        L.call("gc_project_sh_fwd_aa_views", N, C, m, ls, q, op, dc, rest, sh_degree, sh_degree_to_use, CH, H, W, tb[0], tb[1], 0.01,
+               xys, depths, radii, conics, nth, rgbs, opac, comp, boxes, pairs)
     else:
         opac = torch.empty(N, **f32); comp = None
-        L.check(lib.gc_project_sh_fwd_views(
-            L.i64(N), L.i32(C), L.ptr(m), L.ptr(ls), L.ptr(q), L.ptr(op), L.ptr(dc), L.ptr(rest), L.i32(sh_degree), L.i32(sh_degree_to_use),
-            CH, L.i32(H), L.i32(W), L.i32(tb[0]), L.i32(tb[1]), L.f32(0.01), L.ptr(xys), L.ptr(depths), L.ptr(radii), L.ptr(conics),
-            L.ptr(nth), L.ptr(rgbs), L.ptr(opac), L.ptr(boxes), L.ptr(pairs), st), "gc_project_sh_fwd_views")
+        L.call("gc_project_sh_fwd_views", N, C, m, ls, q, op, dc, rest, sh_degree, sh_degree_to_use, CH, H, W, tb[0], tb[1], 0.01,
+               xys, depths, radii, conics, nth, rgbs, opac, boxes, pairs)
     order = torch.empty(C, N, **i32); cum = torch.empty(C, N, **i32); cnt = torch.empty(C, **i32)
     sorted_boxes = bool(getattr(aux, "sorted_boxes", True)) if aux is not None else True
     if sorted_boxes:      # round 6: the boxes ride through the depth sort, culled Gaussians drop out in its first pass -- no per-Gaussian gathers
         bxs = torch.empty(C, N, **i32); nvis = torch.empty(C, **i32)
-        wb = int(lib.gc_raster_order_boxes_views_workspace_bytes(L.i64(N), L.i32(C)))
+        wb = L.call("gc_raster_order_boxes_views_workspace_bytes", N, C)
         ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-        L.check(lib.gc_raster_order_boxes_views(L.i64(N), L.i32(C), L.ptr(pairs), L.ptr(boxes), L.ptr(order), L.ptr(bxs), L.ptr(cum), L.ptr(cnt),
-                                                L.ptr(nvis), L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_order_boxes_views")
+        L.call("gc_raster_order_boxes_views", N, C, pairs, boxes, order, bxs, cum, cnt, nvis, ws, wb)
     else:                 # the round-5 chain (A/B, cross-check tests)
-        wb = int(lib.gc_raster_depth_order_views_workspace_bytes(L.i64(N), L.i32(C)))
+        wb = L.call("gc_raster_depth_order_views_workspace_bytes", N, C)
         ws = torch.empty(wb, dtype=torch.uint8, device=dev)
-        L.check(lib.gc_raster_depth_order_views(L.i64(N), L.i32(C), None, None, L.ptr(pairs), L.ptr(nth), L.ptr(order), L.ptr(cum), L.ptr(cnt),
-                                                L.ptr(ws), L.C.c_size_t(wb), st), "gc_raster_depth_order_views")
+        L.call("gc_raster_depth_order_views", N, C, None, None, pairs, nth, order, cum, cnt, ws, wb)
     del pairs
     m_cap = None if aux is None else aux.m_cap
     if m_cap is None:                     # one readback of the C counts sizes the lists exactly (the sync-free form passes a capacity)
@@ -695,18 +621,14 @@ def _views_front(means, log_scales, quats, opacities, features_dc, features_rest
     else:
         M_cap = int(m_cap)
     ids_s = torch.empty(C, M_cap, **i32); bins = torch.empty(C, T, 2, **i32); ovf = torch.empty(C, **i32)
-    bb = int(lib.gc_raster_bin_views_workspace_bytes(L.i64(M_cap), L.i32(C)))
+    bb = L.call("gc_raster_bin_views_workspace_bytes", M_cap, C)
     del ws
     bws = torch.empty(bb, dtype=torch.uint8, device=dev)
     if sorted_boxes:
-        L.check(lib.gc_raster_bin_sorted_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(nvis), L.ptr(order), L.ptr(bxs),
-                                               L.ptr(cum), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(bws), L.C.c_size_t(bb), st),
-                "gc_raster_bin_sorted_views")
+        L.call("gc_raster_bin_sorted_views", N, C, M_cap, cnt, ovf, nvis, order, bxs, cum, tb[0], tb[1], ids_s, bins, bws, bb)
         del bxs
     else:
-        L.check(lib.gc_raster_bin_tiles_views(L.i64(N), L.i32(C), L.i64(M_cap), L.ptr(cnt), L.ptr(ovf), L.ptr(order), L.ptr(cum), L.ptr(boxes),
-                                              L.ptr(depths), L.i32(tb[0]), L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), None, L.ptr(bws),
-                                              L.C.c_size_t(bb), st), "gc_raster_bin_tiles_views")
+        L.call("gc_raster_bin_tiles_views", N, C, M_cap, cnt, ovf, order, cum, boxes, depths, tb[0], tb[1], ids_s, bins, None, bws, bb)
     del bws
     return _ViewsFront(N, C, H, W, tb, (m, ls, q, op, dc, rest), sh_degree, CH, xys, depths, radii, conics, nth, rgbs, boxes, opac, comp, shared_op,
                        cnt, ovf, M_cap, ids_s, bins)
@@ -724,18 +646,14 @@ class _RenderViews(torch.autograd.Function):
         N, C, H, W, tb, (m, ls, q, op, dc, rest), sh_degree, CH = fr[:8]
         xys, depths, radii, conics, nth, rgbs, boxes, opac, comp, shared_op, cnt, ovf, M_cap, ids_s, bins = fr[8:]
         del fr
-        lib = L.lib()
-        st = L.stream_ptr()
         f32 = dict(device=means.device, dtype=torch.float32); i32 = dict(device=means.device, dtype=torch.int32)
         bg = _c(backgrounds)
         shared_bg = 1 if bg.dim() == 1 else 0
         assert bg.numel() == (3 if shared_bg else 3 * C)
         img = torch.empty(C, H, W, 3, **f32); fT = torch.empty(C, H, W, **f32); fi = torch.empty(C, H, W, **i32)
         dep = torch.empty(C, H, W, **f32) if want_depth else None
-        L.check(lib.gc_rasterize_fwd_views(L.i32(C), L.i64(N), L.i64(M_cap), L.i32(shared_op), L.i32(shared_bg), L.i32(H), L.i32(W), L.i32(tb[0]),
-                                           L.i32(tb[1]), L.ptr(ids_s), L.ptr(bins), L.ptr(xys), L.ptr(conics), L.ptr(rgbs), L.ptr(opac),
-                                           L.ptr(depths if want_depth else None), L.ptr(bg), L.ptr(img), L.ptr(dep), L.ptr(fT), L.ptr(fi), st),
-                "gc_rasterize_fwd_views")
+        L.call("gc_rasterize_fwd_views", C, N, M_cap, shared_op, shared_bg, H, W, tb[0], tb[1], ids_s, bins, xys, conics, rgbs, opac,
+               depths if want_depth else None, bg, img, dep, fT, fi)
         img, alpha, pre_clamp = _finalize(ctx, C * H * W, img, dep, fT)
         meta = _RenderMeta(C, N, M_cap, shared_op, shared_bg, H, W, tb, sh_degree, int(sh_degree_to_use), cams, CH, False)
         # aux.M: per-view device counts / overflow flags ([C] each)
@@ -777,6 +695,5 @@ def trace_masks_views(means, log_scales, quats, opacities, features_dc, features
     fr = _views_front(means, log_scales, quats, opacities, features_dc, features_rest, list(cams), 0, aux)
     if aux is not None:
         aux.M = (fr.cnt, fr.ovf)
-    L.check(L.lib().gc_trace_mask_views(L.i32(C), L.i64(N), L.i64(fr.M_cap), L.i32(fr.shared_op), L.i32(H), L.i32(W), L.i32(fr.tb[0]),
-                                        L.i32(fr.tb[1]), L.ptr(fr.ids_s), L.ptr(fr.bins), L.ptr(fr.xys), L.ptr(fr.conics), L.ptr(fr.opac),
-                                        L.ptr(mk), L.ptr(w_in), L.ptr(w_all), L.stream_ptr()), "gc_trace_mask_views")
+    L.call("gc_trace_mask_views", C, N, fr.M_cap, fr.shared_op, H, W, fr.tb[0], fr.tb[1], fr.ids_s, fr.bins, fr.xys, fr.conics, fr.opac,
+           mk, w_in, w_all)

@@ -15,7 +15,6 @@ gc_mcmc_relocate.  Under nerfstudio SplatfactoModel's own callbacks stay in char
 (GaussCtrlModelConfig.densify_strategy = "mcmc", gc_trainer.McmcCallback)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -43,14 +42,12 @@ def dead_rows(opacities: torch.Tensor, min_opacity: float):
     n_alive); the two counts are read back (8 bytes: the one synchronisation)."""
     N = int(opacities.shape[0])
     dev = opacities.device
-    lib = L.lib()
     weights = torch.empty(N, dtype=torch.float32, device=dev)
     dead_idx = torch.empty(N, dtype=torch.int32, device=dev)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    nbytes = lib.gc_mcmc_dead_workspace_bytes(L.i64(N))
+    nbytes = L.call("gc_mcmc_dead_workspace_bytes", N)
     ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
-    L.check(lib.gc_mcmc_dead(L.i64(N), L.ptr(opacities), L.f32(min_opacity), L.ptr(weights), L.ptr(dead_idx), L.ptr(counts), L.ptr(ws),
-                             C.c_size_t(nbytes), L.stream_ptr()), "gc_mcmc_dead")
+    L.call("gc_mcmc_dead", N, opacities, min_opacity, weights, dead_idx, counts, ws, nbytes)
     n_dead, n_alive = (int(v) for v in counts.cpu()) if N > 0 else (0, 0)
     return weights, dead_idx, n_dead, n_alive
 
@@ -74,9 +71,8 @@ def _draw(weights: torch.Tensor, n: int, sampled: Optional[torch.Tensor], what: 
 
 def _relocate_call(N, n, rest, sampled, dest, min_opacity, params, moments):
     mult = torch.empty(N, dtype=torch.int32, device=sampled.device)
-    L.check(L.lib().gc_mcmc_relocate(L.i64(N), L.i64(n), L.i32(rest), L.ptr(sampled), L.ptr(dest), L.f32(min_opacity), L.ptr(mult),
-                                     ptr_array(params), moment_ptrs(moments, "exp_avg"), moment_ptrs(moments, "exp_avg_sq"), L.stream_ptr()),
-            "gc_mcmc_relocate")
+    L.call("gc_mcmc_relocate", N, n, rest, sampled, dest, min_opacity, mult, ptr_array(params), moment_ptrs(moments, "exp_avg"),
+           moment_ptrs(moments, "exp_avg_sq"))
     return mult
 
 
@@ -143,6 +139,5 @@ def inject_noise(model, lr: float, noise: Optional[torch.Tensor] = None) -> None
         if noise.dtype != torch.float32 or tuple(noise.shape) != (N, 3):
             raise ValueError(f"mcmc.inject_noise: noise must be float32 of shape [{N}, 3], got {noise.dtype} {tuple(noise.shape)}")
         noise = noise.to(dev).contiguous()
-    L.check(L.lib().gc_mcmc_inject_noise(L.i64(N), L.ptr(model.means.data), L.ptr(model.scales.data), L.ptr(model.quats.data),
-                                         L.ptr(model.opacities.data), L.ptr(noise), L.f32(float(lr) * float(model.config.mcmc_noise_lr)),
-                                         L.stream_ptr()), "gc_mcmc_inject_noise")
+    L.call("gc_mcmc_inject_noise", N, model.means.data, model.scales.data, model.quats.data, model.opacities.data, noise,
+           float(lr) * float(model.config.mcmc_noise_lr))

@@ -11,7 +11,6 @@ the six parameters and their Adam moments [-> gc_refine_reset_opacity].  Under n
 this module serves the stand-alone model (GaussCtrlModelConfig.refine_on_device)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
@@ -76,9 +75,7 @@ class RefineState:
         if r.numel() != Cv * N:
             raise ValueError("refine.accumulate: radii and xys_grad disagree")
         self._ensure(N, g.device)
-        L.check(L.lib().gc_refine_accumulate_views(L.i64(N), L.i32(Cv), L.ptr(g), L.ptr(r), L.f32(1.0 / max(height, width)),
-                                                   L.ptr(self.grad_norm_sum), L.ptr(self.vis_count), L.ptr(self.max_2dsize), L.stream_ptr()),
-                "gc_refine_accumulate_views")
+        L.call("gc_refine_accumulate_views", N, Cv, g, r, 1.0 / max(height, width), self.grad_norm_sum, self.vis_count, self.max_2dsize)
 
     def accumulate(self, model):
         """after a training backward: model._aux.xys_grad -- with config.use_absgrad model._aux.xys_absgrad, the per-pixel absolute sums --
@@ -100,23 +97,19 @@ class RefineState:
         c = model.config
         N = model.means.shape[0]
         dev = model.means.device
-        lib = L.lib()
         action = torch.empty(N, dtype=torch.int32, device=dev)
         ranks = torch.empty(3, N, dtype=torch.int32, device=dev)
         counts = torch.zeros(5, dtype=torch.int32, device=dev)
-        nbytes = lib.gc_refine_plan_workspace_bytes(L.i64(N))
+        nbytes = L.call("gc_refine_plan_workspace_bytes", N)
         ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
         densify = bool(sch.densify)
         cull_by_screen = densify and sch.cull_by_scale and sch.by_screen
         if densify or cull_by_screen:
             self._ensure(N, dev)          # (no view seen since the last refinement: zero statistics, nothing is high)
         stats = (self.grad_norm_sum, self.vis_count, self.max_2dsize) if densify else (None, None, None)
-        L.check(lib.gc_refine_plan(
-            L.i64(N), L.ptr(model.scales.data), L.ptr(model.opacities.data), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(stats[2]),
-            L.i32(densify), L.i32(c.n_split_samples), L.f32(max_dim), L.f32(c.densify_grad_thresh), L.f32(c.densify_size_thresh),
-            L.i32(densify and sch.by_screen), L.f32(c.split_screen_size), L.f32(c.cull_alpha_thresh), L.i32(sch.cull_by_scale),
-            L.f32(c.cull_scale_thresh), L.i32(cull_by_screen), L.f32(c.cull_screen_size), L.ptr(action), L.ptr(ranks), L.ptr(counts),
-            L.ptr(ws), C.c_size_t(nbytes), L.stream_ptr()), "gc_refine_plan")
+        L.call("gc_refine_plan", N, model.scales.data, model.opacities.data, stats[0], stats[1], stats[2], densify, c.n_split_samples, max_dim,
+               c.densify_grad_thresh, c.densify_size_thresh, densify and sch.by_screen, c.split_screen_size, c.cull_alpha_thresh,
+               sch.cull_by_scale, c.cull_scale_thresh, cull_by_screen, c.cull_screen_size, action, ranks, counts, ws, nbytes)
         host = [int(v) for v in counts.cpu()] if N > 0 else [0, 0, 0, 0, 0]       # the one synchronisation of a refinement
         return action, ranks, host
 
@@ -137,8 +130,7 @@ class RefineState:
         if sch.reset:
             st = leaf_states(model, optimizers, "refine")[NAMES.index("opacities")][2]
             m, v = (st["exp_avg"], st["exp_avg_sq"]) if st else (None, None)
-            L.check(L.lib().gc_refine_reset_opacity(L.i64(model.opacities.numel()), L.f32(reset_logit(model.config.cull_alpha_thresh)),
-                                                    L.ptr(model.opacities.data), L.ptr(m), L.ptr(v), L.stream_ptr()), "gc_refine_reset_opacity")
+            L.call("gc_refine_reset_opacity", model.opacities.numel(), reset_logit(model.config.cull_alpha_thresh), model.opacities.data, m, v)
         self.clear()
         return sch
 
@@ -163,10 +155,9 @@ class RefineState:
             samples = None
         moments = [st for _, _, st in states]
         p_out, m_out = new_rows(states, n_out)
-        L.check(L.lib().gc_refine_apply(
-            L.i64(N), L.i32(ns), L.i32(rest_floats(model)), L.i64(n_surv), L.i64(n_split_src), L.i64(n_dup_src), L.ptr(action), L.ptr(ranks),
-            L.ptr(samples), ptr_array([p.data for _, p, _ in states]), moment_ptrs(moments, "exp_avg"), moment_ptrs(moments, "exp_avg_sq"),
-            ptr_array(p_out), moment_ptrs(m_out, "exp_avg"), moment_ptrs(m_out, "exp_avg_sq"), L.stream_ptr()), "gc_refine_apply")
+        L.call("gc_refine_apply", N, ns, rest_floats(model), n_surv, n_split_src, n_dup_src, action, ranks, samples,
+               ptr_array([p.data for _, p, _ in states]), moment_ptrs(moments, "exp_avg"), moment_ptrs(moments, "exp_avg_sq"),
+               ptr_array(p_out), moment_ptrs(m_out, "exp_avg"), moment_ptrs(m_out, "exp_avg_sq"))
         # pure cull: train_mode "sharded" prunes its optimizer-state slices with the same mask
         keep = (action & KEEP) != 0 if n_split_src == 0 and n_dup_src == 0 else None
         swap_rows(model, states, p_out, m_out, keep)

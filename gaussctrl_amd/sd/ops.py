@@ -71,7 +71,7 @@ GC_ATTN_VAR_CSHIFT_MASK, GC_ATTN_VAR_CSHIFT_SHIFT = 0x1f0000, 16
 def gemm_selection(d):
     """what gc_dn_gemm(d) launches (gc_dn_gemm_selection: a host function, no GPU needed) as a dict"""
     sel = GemmSelection()
-    L.check(L.lib().gc_dn_gemm_selection(C.byref(d), C.byref(sel)), "gc_dn_gemm_selection")
+    L.call("gc_dn_gemm_selection", C.byref(d), C.byref(sel))
     r = {n: getattr(sel, n) for n, _ in GemmSelection._fields_}
     r["kernel"] = GEMM_KERNELS[sel.kernel]
     return r
@@ -80,7 +80,7 @@ def gemm_selection(d):
 def attention_selection(d):
     """the kernel gc_dn_attention(d) launches (gc_dn_attention_selection), by name"""
     k = C.c_int(0)
-    L.check(L.lib().gc_dn_attention_selection(C.byref(d), C.byref(k)), "gc_dn_attention_selection")
+    L.call("gc_dn_attention_selection", C.byref(d), C.byref(k))
     return ATTN_KERNELS[k.value]
 
 
@@ -198,30 +198,8 @@ def _dt(t):
         raise L.GaussCtrlHipError(f"denoise kernels take bf16 / f16 activations, got {t.dtype}")
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _gpu(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise L.GaussCtrlHipError("denoise ops need GPU tensors (HIP path only; no CPU fallback)")
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def stream_handle():
-    """raw hipStream_t of torch's current stream on the current device.  The host enqueues ~13 000 launches per 3-view chunk: through
-    torch.cuda.current_stream() this lookup alone was 84 of the 275 ms of host time per chunk (scripts/cpu_bound_check.py)."""
-    if _raw_stream is not None:
-        return _raw_stream(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _stream():
-    return C.c_void_p(stream_handle())
-
+_gpu = L.need_gpu
+stream_handle = L.stream_handle          # (imported from here by the pipeline, the networks and the tests)
 
 _zero_page = {}
 
@@ -250,21 +228,21 @@ DEBUG_FILL = None      # tests only: value the statistics buffers (RowStats / Ch
                        # torch.empty and the consumers trust the producers' slot layout: NaN here exposes any slot read but never written
 
 
-def _run_gemm(d, dev, what, row_stats=None, want_parts=False, gn_groups=32):
+def _run_gemm(d, dev, row_stats=None, want_parts=False, gn_groups=32):
     """-> ChanParts of the output when want_parts and the kernel this problem selects can produce them, else None"""
-    lib = L.lib()
     z = _zero_page.get(dev)
     if z is None:
         z = _zero_page[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
     d.zeros = z.data_ptr()
     d.kernel_variant = OPTIONS.gemm_variant
-    wsb = lib.gc_dn_gemm_workspace_bytes(C.byref(d))
+    ref = C.addressof(d)           # (one reference for the two to four calls; a plain address converts fastest)
+    wsb = L.call("gc_dn_gemm_workspace_bytes", ref)
     ws = None
     if wsb:
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)       # caching allocator: no hipMalloc on the hot path
         d.workspace = ws.data_ptr(); d.workspace_bytes = wsb
     if row_stats is not None:                      # the slab count depends on the kernel the library picks for this problem
-        row_stats.slots = int(lib.gc_dn_gemm_row_stat_slots(C.byref(d)))
+        row_stats.slots = L.call("gc_dn_gemm_row_stat_slots", ref)
         row_stats.buf = torch.empty(row_stats.slots, d.M, 2, dtype=torch.float32, device=dev)
         if DEBUG_FILL is not None:
             row_stats.buf.fill_(DEBUG_FILL)
@@ -273,7 +251,7 @@ def _run_gemm(d, dev, what, row_stats=None, want_parts=False, gn_groups=32):
     if want_parts and d.rows_per_batch >= 256:
         rows, ns, ct = C.c_int64(0), C.c_int(0), C.c_int(0)
         d.gn_groups = gn_groups
-        L.check(lib.gc_dn_gemm_chan_parts_layout(C.byref(d), C.byref(rows), C.byref(ns), C.byref(ct)), "gc_dn_gemm_chan_parts_layout")
+        L.call("gc_dn_gemm_chan_parts_layout", ref, C.byref(rows), C.byref(ns), C.byref(ct))
         if 0 < rows.value and ns.value <= 64:        # (more slabs -- the VAE's 256 x 256 / 512 x 512 maps -- would make the apply prologue the long pole)
             parts = ChanParts(torch.empty(d.M // d.rows_per_batch, ns.value, gn_groups, 2, 2, dtype=torch.float32, device=dev), rows.value, ns.value,
                               0, ct.value, gn_groups)
@@ -284,7 +262,7 @@ def _run_gemm(d, dev, what, row_stats=None, want_parts=False, gn_groups=32):
             d.gn_groups = 0
     if SELECTION_LOG is not None:
         SELECTION_LOG.append(("gemm", d.M, gemm_selection(d)))
-    L.check(lib.gc_dn_gemm(C.byref(d), _stream()), what)
+    L.call("gc_dn_gemm", ref)
     return parts
 
 
@@ -339,7 +317,7 @@ def linear(x, w, bias=None, residual=None, act=0, geglu=False, out_f32=False, sc
     if out_t is not None:
         d.out_t = out_t.data_ptr(); d.ldt = ldt; d.t_batch_stride = t_batch_stride; d.t_col0 = t_col0
     _stats_args(d, ln, group_stats)
-    parts = _run_gemm(d, x.device, "gc_dn_gemm", row_stats, want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
+    parts = _run_gemm(d, x.device, row_stats, want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -374,7 +352,7 @@ def conv3x3(x, w, bias=None, stride=1, upsample=False, rowvec=None, ld_rowvec=No
     d.out_scale = scale; d.act = act
     d.out = out.data_ptr(); d.ldc = N; d.out_f32 = int(out_f32)
     _stats_args(d, None, group_stats)
-    parts = _run_gemm(d, x.device, "gc_dn_gemm(conv3x3)", want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
+    parts = _run_gemm(d, x.device, want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -385,6 +363,10 @@ def _bhwc(x):
     """(B, HW, C) of a channels-last x [B, ..., C]"""
     B, Cc = x.shape[0], x.shape[-1]
     return B, x.numel() // (B * Cc), Cc
+
+
+def _gn_scratch(B, HW, Cc, device):
+    return torch.empty(L.call("gc_dn_groupnorm_workspace_bytes", B, HW, Cc) // 4, dtype=torch.float32, device=device)
 
 
 def groupnorm(x, gamma, beta, groups, eps, silu, parts=None):
@@ -398,18 +380,15 @@ def groupnorm(x, gamma, beta, groups, eps, silu, parts=None):
     if parts is not None:
         assert parts.groups == groups
         y = torch.empty_like(x)
-        L.check(L.lib().gc_dn_groupnorm_apply_parts(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta), C.c_float(eps),
-                                                    int(silu), _p(parts.buf), C.c_int64(parts.rows), parts.nslab, parts.mode, parts.col_tile, _stream()),
-                "gc_dn_groupnorm_apply_parts")
+        L.call("gc_dn_groupnorm_apply_parts", _dt(x), x, y, B, HW, Cc, groups, gamma, beta, eps, int(silu), parts.buf, parts.rows, parts.nslab,
+               parts.mode, parts.col_tile)
         return y
     key = (x.device, B, HW, Cc, stream_handle())      # scratch is per stream: two networks may run concurrently
     ws = _gn_ws.get(key)
     if ws is None:
-        nbytes = L.lib().gc_dn_groupnorm_workspace_bytes(C.c_int64(B), C.c_int64(HW), Cc)
-        ws = _gn_ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        ws = _gn_ws[key] = _gn_scratch(B, HW, Cc, x.device)
     y = torch.empty_like(x)
-    L.check(L.lib().gc_dn_groupnorm(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta),
-                                    C.c_float(eps), int(silu) | (0x100 if OPTIONS.batch_invariant else 0), _p(ws), _stream()), "gc_dn_groupnorm")
+    L.call("gc_dn_groupnorm", _dt(x), x, y, B, HW, Cc, groups, gamma, beta, eps, int(silu) | (0x100 if OPTIONS.batch_invariant else 0), ws)
     return y
 
 
@@ -418,8 +397,7 @@ def groupnorm_apply(x, group_stats, gamma, beta, groups, eps, silu):
     _gpu(x, group_stats)
     B, HW, Cc = _bhwc(x)
     y = torch.empty_like(x)
-    L.check(L.lib().gc_dn_groupnorm_apply(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta),
-                                          C.c_float(eps), int(silu), _p(group_stats), _stream()), "gc_dn_groupnorm_apply")
+    L.call("gc_dn_groupnorm_apply", _dt(x), x, y, B, HW, Cc, groups, gamma, beta, eps, int(silu), group_stats)
     return y
 
 
@@ -433,8 +411,7 @@ def groupnorm_apply_fp8(x, group_stats, gamma, beta, groups, eps, silu, a_scale=
     B, HW, Cc = _bhwc(x)
     Cp = pad128(Cc)
     y = torch.empty(x.shape[:-1] + (Cp,), dtype=torch.uint8, device=x.device)
-    L.check(L.lib().gc_dn_groupnorm_apply_fp8(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, Cp, groups, _p(gamma), _p(beta),
-                                              C.c_float(eps), int(silu), _p(group_stats), int(a_scale), _stream()), "gc_dn_groupnorm_apply_fp8")
+    L.call("gc_dn_groupnorm_apply_fp8", _dt(x), x, y, B, HW, Cc, Cp, groups, gamma, beta, eps, int(silu), group_stats, int(a_scale))
     return y
 
 
@@ -442,7 +419,7 @@ def group_stats(x, gs):
     """per-(batch, GroupNorm group) (sum, sum^2) of x [B, ..., C], ADDED into the zeroed fp32 gs [B, G, 2] (one streaming launch)."""
     _gpu(x, gs)
     B, HW, Cc = _bhwc(x)
-    L.check(L.lib().gc_dn_group_stats(_dt(x), _p(x), C.c_int64(B), C.c_int64(HW), Cc, gs.shape[-2], _p(gs), _stream()), "gc_dn_group_stats")
+    L.call("gc_dn_group_stats", _dt(x), x, B, HW, Cc, gs.shape[-2], gs)
     return gs
 
 
@@ -453,9 +430,8 @@ def groupnorm_apply_parts_fp8(x, parts, gamma, beta, groups, eps, silu, a_scale=
     Cp = pad128(Cc)
     assert parts.groups == groups
     y = torch.empty(x.shape[:-1] + (Cp,), dtype=torch.uint8, device=x.device)
-    L.check(L.lib().gc_dn_groupnorm_apply_parts_fp8(_dt(x), _p(x), _p(y), C.c_int64(B), C.c_int64(HW), Cc, Cp, groups, _p(gamma), _p(beta), C.c_float(eps),
-                                                    int(silu), _p(parts.buf), C.c_int64(parts.rows), parts.nslab, parts.mode, parts.col_tile, int(a_scale),
-                                                    _stream()), "gc_dn_groupnorm_apply_parts_fp8")
+    L.call("gc_dn_groupnorm_apply_parts_fp8", _dt(x), x, y, B, HW, Cc, Cp, groups, gamma, beta, eps, int(silu), parts.buf, parts.rows, parts.nslab,
+           parts.mode, parts.col_tile, int(a_scale))
     return y
 
 
@@ -493,7 +469,7 @@ def conv3x3_fp8(x8, w8, w_scale, out_dtype, bias=None, stride=1, rowvec=None, ld
     d.fp8 = 1; d.w_scale = w_scale.data_ptr(); d.a_scale = int(a_scale)
     _stats_args(d, None, group_stats)
     # chan_parts=True: returns (out, ChanParts | None) -- the k-sliced problems (16 x 16 maps) leave the GroupNorm partials of their output
-    parts = _run_gemm(d, x8.device, "gc_dn_gemm(conv3x3 fp8)", want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
+    parts = _run_gemm(d, x8.device, want_parts=chan_parts and not OPTIONS.batch_invariant, gn_groups=gn_groups)
     return (out, parts) if chan_parts else out
 
 
@@ -523,7 +499,7 @@ def linear_fp8(x8, w8, w_scale, out_dtype, bias=None, residual=None, act=0, scal
         d.out_t = out_t.data_ptr(); d.ldt = ldt; d.t_batch_stride = t_batch_stride; d.t_col0 = t_col0
     d.fp8 = 1; d.w_scale = w_scale.data_ptr(); d.a_scale = int(a_scale)
     _stats_args(d, ln, group_stats)
-    _run_gemm(d, x8.device, "gc_dn_gemm(linear fp8)", row_stats)
+    _run_gemm(d, x8.device, row_stats)
     return out
 
 
@@ -532,8 +508,7 @@ def layernorm_fp8(x, gamma, beta, eps=1e-5, a_scale=127):
     _gpu(x)
     Cc = x.shape[-1]
     y = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    L.check(L.lib().gc_dn_layernorm_fp8(_dt(x), _p(x), _p(y), C.c_int64(x.numel() // Cc), Cc, _p(gamma), _p(beta),
-                                        C.c_float(eps), int(a_scale), _stream()), "gc_dn_layernorm_fp8")
+    L.call("gc_dn_layernorm_fp8", _dt(x), x, y, x.numel() // Cc, Cc, gamma, beta, eps, int(a_scale))
     return y
 
 
@@ -545,8 +520,7 @@ def layernorm(x, gamma, beta, eps=1e-5):
         if z is not None:
             return z
     y = torch.empty_like(x)
-    L.check(L.lib().gc_dn_layernorm(_dt(x), _p(x), _p(y), C.c_int64(x.numel() // Cc), Cc, _p(gamma), _p(beta),
-                                    C.c_float(eps), _stream()), "gc_dn_layernorm")
+    L.call("gc_dn_layernorm", _dt(x), x, y, x.numel() // Cc, Cc, gamma, beta, eps)
     return y
 
 
@@ -562,40 +536,36 @@ def concat_add(a, b, c=None, group_stats=None, chan_parts=False, gn_groups=32):
         if rpb < 256 or OPTIONS.batch_invariant or "gn" in OPTIONS.ablate:
             return concat_add(a, b, c), None
         rows, ns, ct = C.c_int64(0), C.c_int(0), C.c_int(0)
-        L.check(L.lib().gc_dn_concat_parts_layout(C.c_int64(rpb), C1 + C2, gn_groups, C.byref(rows), C.byref(ns), C.byref(ct)), "gc_dn_concat_parts_layout")
+        L.call("gc_dn_concat_parts_layout", rpb, C1 + C2, gn_groups, C.byref(rows), C.byref(ns), C.byref(ct))
         if rows.value == 0:
             return concat_add(a, b, c), None
         parts = ChanParts(torch.empty(a.shape[0], ns.value, gn_groups, 2, 2, dtype=torch.float32, device=a.device), rows.value, ns.value, 1, ct.value, gn_groups)
         if DEBUG_FILL is not None:
             parts.buf.fill_(DEBUG_FILL)
-        L.check(L.lib().gc_dn_concat_add_parts(_dt(a), _p(a), C1, _p(b), _p(c), C2, _p(out), C.c_int64(M), C.c_int64(rpb), gn_groups, _p(parts.buf), _stream()),
-                "gc_dn_concat_add_parts")
+        L.call("gc_dn_concat_add_parts", _dt(a), a, C1, b, c, C2, out, M, rpb, gn_groups, parts.buf)
         return out, parts
-    L.check(L.lib().gc_dn_concat_add(_dt(a), _p(a), C1, _p(b), _p(c), C2, _p(out), C.c_int64(M), C.c_int64(M // a.shape[0]),
-                                     _p(group_stats), 0 if group_stats is None else group_stats.shape[-2], _stream()), "gc_dn_concat_add")
+    L.call("gc_dn_concat_add", _dt(a), a, C1, b, c, C2, out, M, M // a.shape[0], group_stats, 0 if group_stats is None else group_stats.shape[-2])
     return out
 
 
 def axpby(a, sa=1.0, b=None, sb=1.0, act=0):
     _gpu(a, b)
     out = torch.empty_like(a)
-    L.check(L.lib().gc_dn_axpby(_dt(a), _p(a), C.c_float(sa), _p(b), C.c_float(sb), act, _p(out), C.c_int64(a.numel()),
-                                _stream()), "gc_dn_axpby")
+    L.call("gc_dn_axpby", _dt(a), a, sa, b, sb, act, out, a.numel())
     return out
 
 
 def cast_f32(a, dtype, silu=False):
     _gpu(a)
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
-    L.check(L.lib().gc_dn_cast_f32(DT[dtype], _p(a), int(silu), _p(out), C.c_int64(a.numel()), _stream()), "gc_dn_cast_f32")
+    L.call("gc_dn_cast_f32", DT[dtype], a, int(silu), out, a.numel())
     return out
 
 
 def softmax_rows_(s, scale):
     _gpu(s)
     N = s.shape[-1]
-    L.check(L.lib().gc_dn_softmax_rows(_dt(s), _p(s), C.c_int64(s.numel() // N), C.c_int64(N), C.c_int64(s.stride(-2)),
-                                       C.c_float(scale), _stream()), "gc_dn_softmax_rows")
+    L.call("gc_dn_softmax_rows", _dt(s), s, s.numel() // N, N, s.stride(-2), scale)
     return s
 
 
@@ -627,14 +597,15 @@ def attention(q, k, vt, heads, sets, frames_per_half, Lk=None, kref=None, vtref=
     if kref is not None:
         d.Kref = kref.data_ptr(); d.kref_batch_stride = kref.stride(0)
         d.Vtref = vtref.data_ptr(); d.vtref_batch_stride = vtref.stride(0); d.ref_frames_per_half = ref_fph
-    wsb = L.lib().gc_dn_attention_workspace_bytes(C.byref(d))      # head size 160 with several K/V sets: one workgroup per (query block, set)
+    ref = C.addressof(d)
+    wsb = L.call("gc_dn_attention_workspace_bytes", ref)      # head size 160 with several K/V sets: one workgroup per (query block, set)
     if wsb and not OPTIONS.batch_invariant:      # the library takes the set-split form only while the grid is small (nwg < 512: a function of B) and its fp32
                                          # combine rounds differently from the in-register one: batch-invariant mode never offers the workspace
         ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
         d.workspace = ws.data_ptr(); d.workspace_bytes = wsb
     if SELECTION_LOG is not None:
         SELECTION_LOG.append(("attn", B, attention_selection(d)))
-    L.check(L.lib().gc_dn_attention(C.byref(d), _stream()), "gc_dn_attention")
+    L.call("gc_dn_attention", ref)
     return o
 
 
@@ -665,7 +636,7 @@ def transformer_tail(attn_out, resid, x_in, seg_a, seg_kv, seg_b, params, heads,
     d.attn_out = attn_out.data_ptr(); d.resid = resid.data_ptr(); d.x_in = x_in.data_ptr(); d.out = out.data_ptr()
     d.w_a = seg_a.data_ptr(); d.w_kv = seg_kv.data_ptr(); d.w_b = seg_b.data_ptr(); d.params = params.data_ptr(); d.stop_after = stop_after
     d.resid_fragment_layout = int(resid_frags)
-    L.check(L.lib().gc_dn_transformer_tail(C.byref(d), _stream()), "gc_dn_transformer_tail")
+    L.call("gc_dn_transformer_tail", C.addressof(d))
     return out
 
 
@@ -682,21 +653,18 @@ def groupnorm_coef(x, gamma, beta, groups, eps, parts=None):
     B, HW, Cc = _bhwc(x)
     if parts is not None and "gn" not in OPTIONS.ablate:
         coef = torch.empty(B, Cc, 2, dtype=torch.float32, device=x.device)
-        L.check(L.lib().gc_dn_groupnorm_coef_parts(C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta), C.c_float(eps), _p(parts.buf),
-                                                   C.c_int64(parts.rows), parts.nslab, parts.mode, parts.col_tile, _p(coef), _stream()), "gc_dn_groupnorm_coef_parts")
+        L.call("gc_dn_groupnorm_coef_parts", B, HW, Cc, groups, gamma, beta, eps, parts.buf, parts.rows, parts.nslab, parts.mode, parts.col_tile, coef)
         return coef
     key = (x.device, B, HW, Cc, stream_handle())
     ws = _gn_ws.get(key)
     if ws is None:
-        nbytes = L.lib().gc_dn_groupnorm_workspace_bytes(C.c_int64(B), C.c_int64(HW), Cc)
-        ws = _gn_ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        ws = _gn_ws[key] = _gn_scratch(B, HW, Cc, x.device)
     if OPTIONS.ablate:
         z = _ablated("gn", (B, Cc, 2), torch.float32, x.device)
         if z is not None:
             return z
     coef = torch.empty(B, Cc, 2, dtype=torch.float32, device=x.device)
-    L.check(L.lib().gc_dn_groupnorm_coef(_dt(x), _p(x), C.c_int64(B), C.c_int64(HW), Cc, groups, _p(gamma), _p(beta), C.c_float(eps),
-                                         _p(ws), _p(coef), _stream()), "gc_dn_groupnorm_coef")
+    L.call("gc_dn_groupnorm_coef", _dt(x), x, B, HW, Cc, groups, gamma, beta, eps, ws, coef)
     return coef
 
 
@@ -716,7 +684,7 @@ def transformer_head(x, coef, w_stream, params, eps=1e-5, h_frags=False):
     d.dtype = _dt(x); d.channels = Cc; d.M = B * HW; d.rows_per_frame = HW; d.ln_eps = eps
     d.x = x.data_ptr(); d.gn_coef = coef.data_ptr(); d.h = h.data_ptr(); d.qk = qk.data_ptr(); d.vt = vt.data_ptr()
     d.ldvt = HW; d.vt_batch_stride = Cc * HW; d.w = w_stream.data_ptr(); d.params = params.data_ptr(); d.h_fragment_layout = int(h_frags)
-    L.check(L.lib().gc_dn_transformer_head(C.byref(d), _stream()), "gc_dn_transformer_head")
+    L.call("gc_dn_transformer_head", C.addressof(d))
     return h, qk, vt
 
 
@@ -725,9 +693,7 @@ def cfg_ddim_step(eps, latents, xin, guidance, cfg, alpha_t, alpha_prev, nrep):
     _gpu(eps, latents, xin)
     f = latents.shape[0]
     HW = latents.shape[1] * latents.shape[2]
-    L.check(L.lib().gc_dn_cfg_ddim_step(_dt(xin), _p(eps), eps.shape[-1], C.c_int64(f), C.c_int64(HW), C.c_float(guidance),
-                                        int(cfg), C.c_float(alpha_t), C.c_float(alpha_prev), _p(latents), _p(xin), nrep,
-                                        _stream()), "gc_dn_cfg_ddim_step")
+    L.call("gc_dn_cfg_ddim_step", _dt(xin), eps, eps.shape[-1], f, HW, guidance, int(cfg), alpha_t, alpha_prev, latents, xin, nrep)
 
 
 _disp_ws = {}
@@ -742,8 +708,7 @@ def depth_to_disparity(depth, dtype):
         ws = _disp_ws[key] = torch.zeros(1, dtype=torch.int32, device=depth.device)
     d = depth.contiguous()
     out = torch.empty(d.shape[0], d.shape[1], 8, dtype=dtype, device=d.device)
-    L.check(L.lib().gc_dn_depth_to_disparity(DT[dtype], _p(d), C.c_int64(d.numel()), _p(out), _p(ws), _stream()),
-            "gc_dn_depth_to_disparity")
+    L.call("gc_dn_depth_to_disparity", DT[dtype], d, d.numel(), out, ws)
     return out
 
 
@@ -752,6 +717,5 @@ def mask_composite(edited_hwc, unedited_hwc=None, mask_hw=None):
     _gpu(edited_hwc, unedited_hwc, mask_hw)
     H, W = edited_hwc.shape[0], edited_hwc.shape[1]
     out = torch.empty(H, W, 3, dtype=torch.float32, device=edited_hwc.device)
-    L.check(L.lib().gc_dn_mask_composite(_p(edited_hwc), edited_hwc.shape[-1], _p(unedited_hwc), _p(mask_hw), _p(out),
-                                         C.c_int64(H * W), _stream()), "gc_dn_mask_composite")
+    L.call("gc_dn_mask_composite", edited_hwc, edited_hwc.shape[-1], unedited_hwc, mask_hw, out, H * W)
     return out

@@ -7,8 +7,6 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
@@ -19,15 +17,13 @@ class _L1SSIM(torch.autograd.Function):
     def forward(ctx, pred, target, lam, valid):
         if not pred.is_cuda:
             raise L.GaussCtrlHipError("l1_ssim_loss needs GPU tensors (HIP path only; no CPU fallback)")
-        lib = L.lib()
         H, W, Cc = pred.shape
         p = pred.detach().float().contiguous(); t = target.detach().float().contiguous()
-        nbytes = lib.gc_l1_ssim_workspace_bytes(H, W, Cc)
+        nbytes = L.call("gc_l1_ssim_workspace_bytes", H, W, Cc)
         ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=p.device)
         sums = torch.empty(2, dtype=torch.float32, device=p.device)
         v = torch.empty_like(p)
-        L.check(lib.gc_l1_ssim_fwd_bwd(L.ptr(p), L.ptr(t), H, W, Cc, L.f32(lam), L.f32(1.0), int(valid), L.ptr(sums), L.ptr(v), L.ptr(ws),
-                                       C.c_size_t(nbytes), L.stream_ptr()), "gc_l1_ssim_fwd_bwd")
+        L.call("gc_l1_ssim_fwd_bwd", p, t, H, W, Cc, lam, 1.0, int(valid), sums, v, ws, nbytes)
         ctx.save_for_backward(v)
         n = float(H * W * Cc)
         n_ssim = float((H - 10) * (W - 10) * Cc) if valid else n
@@ -51,15 +47,13 @@ class _L1SSIMViews(torch.autograd.Function):
     def forward(ctx, pred, target, lam, valid):
         if not pred.is_cuda:
             raise L.GaussCtrlHipError("l1_ssim_loss_views needs GPU tensors (HIP path only; no CPU fallback)")
-        lib = L.lib()
         B, H, W, Cc = pred.shape
         p = pred.detach().float().contiguous(); t = target.detach().float().contiguous()
-        nbytes = lib.gc_l1_ssim_views_workspace_bytes(B, H, W, Cc)
+        nbytes = L.call("gc_l1_ssim_views_workspace_bytes", B, H, W, Cc)
         ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=p.device)
         sums = torch.empty(B, 2, dtype=torch.float32, device=p.device)
         v = torch.empty_like(p)
-        L.check(lib.gc_l1_ssim_fwd_bwd_views(B, L.ptr(p), L.ptr(t), H, W, Cc, L.f32(lam), L.f32(1.0), int(valid), L.ptr(sums), L.ptr(v), L.ptr(ws),
-                                             C.c_size_t(nbytes), L.stream_ptr()), "gc_l1_ssim_fwd_bwd_views")
+        L.call("gc_l1_ssim_fwd_bwd_views", B, p, t, H, W, Cc, lam, 1.0, int(valid), sums, v, ws, nbytes)
         ctx.save_for_backward(v)
         n = float(H * W * Cc)
         n_ssim = float((H - 10) * (W - 10) * Cc) if valid else n
@@ -83,15 +77,13 @@ class _DepthL1Views(torch.autograd.Function):
             raise L.GaussCtrlHipError("depth_l1_loss needs GPU tensors (HIP path only; no CPU fallback)")
         if pred.dim() != 3 or pred.shape != target.shape:
             raise ValueError("depth_l1_loss_views: pred and target must both be [B,H,W]")
-        lib = L.lib()
         B, H, W = pred.shape
         p = pred.detach().float().contiguous(); t = target.detach().to(p.device).float().contiguous()
-        nbytes = lib.gc_depth_l1_views_workspace_bytes(B, H, W)
+        nbytes = L.call("gc_depth_l1_views_workspace_bytes", B, H, W)
         ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=p.device)
         sums = torch.empty(B, 2, dtype=torch.float32, device=p.device)
         v = torch.empty_like(p)
-        L.check(lib.gc_depth_l1_fwd_bwd_views(B, L.ptr(p), L.ptr(t), H, W, L.f32(1.0), L.ptr(sums), L.ptr(v), L.ptr(ws), C.c_size_t(nbytes),
-                                              L.stream_ptr()), "gc_depth_l1_fwd_bwd_views")
+        L.call("gc_depth_l1_fwd_bwd_views", B, p, t, H, W, 1.0, sums, v, ws, nbytes)
         ctx.save_for_backward(v)
         return sums[:, 0] / sums[:, 1].clamp(min=1.0)
 
@@ -123,8 +115,6 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        lib = L.lib()
-        st = L.stream_ptr()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -144,10 +134,7 @@ class FusedAdam(torch.optim.Optimizer):
                     if not sel.is_cuda or sel.dtype != torch.uint8 or not sel.is_contiguous():
                         raise L.GaussCtrlHipError("FusedAdam.row_select must be a contiguous uint8 GPU tensor")
                     rows = p.shape[0]
-                    L.check(lib.gc_adam_step_rows(L.ptr(p), L.ptr(g), L.ptr(state["exp_avg"]), L.ptr(state["exp_avg_sq"]), L.i64(rows),
-                                                  L.i32(p.numel() // rows if rows else 1), L.ptr(sel), L.f32(group["lr"]), L.f32(b1), L.f32(b2),
-                                                  L.f32(group["eps"]), L.i32(state["step"]), st), "gc_adam_step_rows")
+                    L.call("gc_adam_step_rows", p, g, state["exp_avg"], state["exp_avg_sq"], rows, p.numel() // rows if rows else 1, sel,
+                           group["lr"], b1, b2, group["eps"], state["step"])
                     continue
-                L.check(lib.gc_adam_step(L.ptr(p), L.ptr(g), L.ptr(state["exp_avg"]), L.ptr(state["exp_avg_sq"]), L.i64(p.numel()),
-                                         L.f32(group["lr"]), L.f32(b1), L.f32(b2), L.f32(group["eps"]), L.i32(state["step"]), st),
-                        "gc_adam_step")
+                L.call("gc_adam_step", p, g, state["exp_avg"], state["exp_avg_sq"], p.numel(), group["lr"], b1, b2, group["eps"], state["step"])

@@ -299,7 +299,7 @@ def guard(*modules, nbytes=2 << 30, device="cuda:0", caches=None):
     a proxy over a fresh arena; afterwards every zone must be as it was filled.  The entry points of the library that the body looks up are
     collected in `reached`.
 
-    Device pointers are counted where they leave for the library, at Tensor.data_ptr: _lib.ptr and sd.ops._p call it, and so does the ops
+    Device pointers are counted where they leave for the library, at Tensor.data_ptr: _lib.call and _lib.ptr call it, and so does the ops
     layer where it fills the descriptors of the GEMM, attention and transformer head / tail entry points directly (wrapping ptr and _p
     alone would see no pointer of those).  The share outside the arena (inputs a test built with .to(device), results of torch
     arithmetic, gradients autograd allocated) is logged through within(); no pointer inside at all means the guard was not active, and fails."""

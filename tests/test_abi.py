@@ -6,17 +6,9 @@ import re
 
 import pytest
 
+from _abi_header import names as _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    names = []
-    for fn in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if fn.endswith(".h"):
-            src = open(os.path.join(ROOT, "include", fn)).read()
-            src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-            names += re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src)
-    return sorted(set(names))
 
 
 @pytest.fixture(scope="module")
@@ -494,7 +486,7 @@ def test_options_is_the_only_switch_state(built, monkeypatch):
         monkeypatch.setitem(ops._zero_page, "cpu", type("Z", (), {"data_ptr": lambda self: 64})())
         d = ops.GemmDesc()
         with pytest.raises(Stop):
-            ops._run_gemm(d, "cpu", "test")
+            ops._run_gemm(d, "cpu")
         assert d.kernel_variant == X
     finally:
         ops.configure(keep)

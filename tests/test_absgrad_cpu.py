@@ -1,17 +1,13 @@
 """CPU: the float64 absgrad reference (tests/_absgrad_ref.py) is sound -- its signed sum is the oracle's autograd xys gradient, its absolute
 sum dominates it and is zero on culled Gaussians -- and the absgrad entry point is declared (include/gaussctrl_absgrad.h), listed, exported
 and bound with matching argument counts; the config field and the RenderAux switch exist and default to off."""
-import os
-import re
-
 import numpy as np
 import pytest
 
+import _abi_header as A
 from _absgrad_ref import absgrad_reference
-from test_antialias_abi_cpu import _call_args, _declared
 from test_raster_depth_gpu import BG, _cotangents, _oracle_scene, _scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = "gc_rasterize_bwd_abs_views"
 
 
@@ -41,28 +37,24 @@ def test_reference_signed_sum_is_the_oracle_gradient(name):
 def test_absgrad_symbol_declared_listed_and_exported():
     import ctypes
     from gaussctrl_amd import _lib
-    _, declared = _declared("gaussctrl_absgrad.h")
-    assert declared == {NEW}
+    assert A.names("gaussctrl_absgrad.h") == [NEW]
     assert NEW in _lib.SYMBOLS
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NEW)
-    _, main = _declared("gaussctrl_hip.h")
+    main = A.names("gaussctrl_hip.h")
     assert len(main) == 83 and NEW not in main               # the main header is as it was
 
 
 def test_absgrad_bindings_pass_the_declared_number_of_arguments():
     """the prototype is gc_rasterize_bwd_depth_views' plus v_xy_abs before stream, and the call of gsplat_ops (_composite_bwd, which serves
     render_view and render_views) passes that many arguments"""
-    src, _ = _declared("gaussctrl_absgrad.h")
-    main, _ = _declared("gaussctrl_hip.h")
-    proto = lambda text, name: re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1)
-    params = [" ".join(p.split()) for p in proto(src, NEW).split(",")]
-    base = [" ".join(p.split()) for p in proto(main, "gc_rasterize_bwd_depth_views").split(",")]
-    assert params == base[:-1] + ["float *v_xy_abs", "void *stream"]
-    n = _call_args(src, re.search(r"\b" + NEW + r"\s*\(", src).end() - 1)
+    (proto,) = A.prototypes("gaussctrl_absgrad.h")
+    (base,) = [p for p in A.prototypes("gaussctrl_hip.h") if p.name == "gc_rasterize_bwd_depth_views"]
+    assert proto.name == NEW and proto.ret == base.ret == "int"
+    assert proto.params == base.params[:-1] + [("float *", "v_xy_abs"), ("void *", "stream")]
+    n = len(proto.params)
     assert n == 31
-    host = open(os.path.join(ROOT, "gaussctrl_amd", "gsplat_ops.py")).read()
-    calls = [_call_args(host, m.end() - 1) for m in re.finditer(r"\." + NEW + r"\s*\(", host)]
-    assert calls == [n], calls
+    calls = A.sites("gaussctrl_amd/gsplat_ops.py", "gaussctrl_absgrad.h")
+    assert calls == {NEW: [n]}, calls
 
 
 def test_absgrad_switches_default_to_off():

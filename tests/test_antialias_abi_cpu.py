@@ -1,57 +1,31 @@
 """CPU: the antialiased rasterize_mode's entry points are declared (include/gaussctrl_antialias.h), listed, exported and bound with matching
 argument counts; the config field, the RenderAux switch and the render command's flag exist with the classic default."""
-import os
-import re
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi_header as A
+
 NEW = ("gc_project_sh_fwd_aa_views", "gc_project_sh_bwd_aa_views")
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return src, set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
-
-
-def _call_args(text, start):
-    """number of top-level arguments of the call whose '(' is at text[start]"""
-    depth, n, i = 0, 0, start
-    while True:
-        ch = text[i]
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-            if depth == 0:
-                return n + 1
-        elif ch == "," and depth == 1:
-            n += 1
-        i += 1
 
 
 def test_antialias_symbols_declared_listed_and_exported():
     import ctypes
     from gaussctrl_amd import _lib
-    _, declared = _declared("gaussctrl_antialias.h")
-    assert declared == set(NEW)
+    assert set(A.names("gaussctrl_antialias.h")) == set(NEW)
     for name in NEW:
         assert name in _lib.SYMBOLS, name
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert hasattr(lib, name), name
-    _, main = _declared("gaussctrl_hip.h")
+    main = set(A.names("gaussctrl_hip.h"))
     assert len(main) == 83 and not main & set(NEW)          # the main header is as it was
 
 
 def test_antialias_bindings_pass_the_declared_number_of_arguments():
-    """every lib.gc_project_sh_*_aa_views( call of gsplat_ops passes as many arguments as the header's prototype has parameters"""
-    src, _ = _declared("gaussctrl_antialias.h")
-    declared = {name: _call_args(src, re.search(r"\b" + name + r"\s*\(", src).end() - 1) for name in NEW}
+    """every call("gc_project_sh_*_aa_views", ...) of gsplat_ops passes, with the stream call() appends, as many arguments as the header's
+    prototype has parameters; the binding table has that arity too (_abi_header.sites)"""
+    declared = A.arities("gaussctrl_antialias.h")
     assert declared == {"gc_project_sh_fwd_aa_views": 27, "gc_project_sh_bwd_aa_views": 28}
-    host = open(os.path.join(ROOT, "gaussctrl_amd", "gsplat_ops.py")).read()
-    calls = {name: [_call_args(host, m.end() - 1) for m in re.finditer(r"\." + name + r"\s*\(", host)] for name in NEW}
+    calls = A.sites("gaussctrl_amd/gsplat_ops.py", "gaussctrl_antialias.h")
     sites = {"gc_project_sh_fwd_aa_views": 2, "gc_project_sh_bwd_aa_views": 1}      # the forwards of render_view and render_views; _project_bwd
     for name in NEW:
         assert len(calls[name]) == sites[name] and all(n == declared[name] for n in calls[name]), (name, calls[name])

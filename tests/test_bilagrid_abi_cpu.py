@@ -10,17 +10,13 @@ import types
 import pytest
 import torch
 
+from _abi_header import names as _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["gcx_bilagrid_slice_bwd_views", "gcx_bilagrid_slice_fwd_views", "gcx_bilagrid_tv_fwd_bwd", "gcx_bilagrid_tv_workspace_bytes"]
 EINVAL = -1
 LEAVES = ["features_dc", "features_rest", "means", "opacities", "quats", "scales"]
 GROUPS = ["features_dc", "features_rest", "opacity", "rotation", "scaling", "xyz"]
-
-
-def _declared(header, prefix):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(rf"\b({prefix}_[a-z0-9_]+)\s*\(", src)))
 
 
 @pytest.fixture(scope="module")

@@ -1,16 +1,12 @@
 """CPU: the depth-supervision entry points are declared and loaded, and the config switches exist with their defaults."""
-import os
-import re
+import _abi_header as A
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("gc_rasterize_bwd_depth_views", "gc_project_sh_bwd_depth_views", "gc_depth_l1_views_workspace_bytes", "gc_depth_l1_fwd_bwd_views")
 
 
 def test_depth_symbols_declared_and_listed():
     from gaussctrl_amd import _lib
-    src = open(os.path.join(ROOT, "include", "gaussctrl_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
+    declared = set(A.names("gaussctrl_hip.h"))
     for name in NEW:
         assert name in declared, name
         assert name in _lib.SYMBOLS, name

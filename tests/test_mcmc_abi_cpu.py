@@ -1,45 +1,19 @@
 """CPU: the MCMC densification entry points are declared (include/gaussctrl_mcmc.h), exported and bound with matching argument counts; the
 config fields exist with their defaults and densify_strategy is validated; mcmc.schedule against hand cases; the stand-alone model's callbacks
 and loss keys under both strategies; "mcmc" refuses world_size > 1."""
-import os
-import re
 import types
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi_header as A
+
 NEW = ("gc_mcmc_dead_workspace_bytes", "gc_mcmc_dead", "gc_mcmc_relocate", "gc_mcmc_inject_noise")
-
-
-def _header():
-    src = open(os.path.join(ROOT, "include", "gaussctrl_mcmc.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def _call_args(text, start):
-    """number of top-level arguments of the call whose '(' is at text[start]"""
-    depth, n, i, seen = 0, 0, start, False
-    while True:
-        ch = text[i]
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-            if depth == 0:
-                return n + 1 if seen else 0
-        elif ch == "," and depth == 1:
-            n += 1
-        elif depth >= 1 and not ch.isspace():
-            seen = True
-        i += 1
 
 
 def test_mcmc_symbols_declared_listed_and_exported():
     import ctypes
     from gaussctrl_amd import _lib
-    src = _header()
-    declared = set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
-    assert declared == set(NEW)
+    assert set(A.names("gaussctrl_mcmc.h")) == set(NEW)
     for name in NEW:
         assert name in _lib.SYMBOLS, name
     lib = ctypes.CDLL(_lib.LIB_PATH)
@@ -48,19 +22,14 @@ def test_mcmc_symbols_declared_listed_and_exported():
 
 
 def test_mcmc_bindings_pass_the_declared_number_of_arguments():
-    """every lib.gc_mcmc_*( call of the host layer passes as many arguments as the header's prototype has parameters"""
-    src = _header()
-    declared = {}
-    for name in NEW:
-        m = re.search(r"\b" + name + r"\s*\(", src)
-        declared[name] = _call_args(src, m.end() - 1)
+    """every call("gc_mcmc_*", ...) of the host layer passes, with the stream call() appends, as many arguments as the header's prototype has
+    parameters; the binding table has that arity too (_abi_header.sites)"""
+    declared = A.arities("gaussctrl_mcmc.h")
     assert declared == {"gc_mcmc_dead_workspace_bytes": 1, "gc_mcmc_dead": 9, "gc_mcmc_relocate": 11, "gc_mcmc_inject_noise": 8}
-    host = open(os.path.join(ROOT, "gaussctrl_amd", "mcmc.py")).read()
-    called = set()
-    for m in re.finditer(r"\.(gc_mcmc_[a-z_]+)\s*\(", host):
-        assert _call_args(host, m.end() - 1) == declared[m.group(1)], m.group(1)
-        called.add(m.group(1))
-    assert called == set(NEW)
+    sites = A.sites("gaussctrl_amd/mcmc.py", "gaussctrl_mcmc.h")
+    for name, passed in sites.items():
+        assert all(n == declared[name] for n in passed), (name, passed)
+    assert set(sites) == set(NEW)
 
 
 def test_mcmc_workspace_size_and_refusals_without_a_device():

@@ -7,15 +7,11 @@ import re
 
 import pytest
 
+from _abi_header import names as _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["gcx_pose_bwd_views", "gcx_pose_bwd_views_workspace_bytes"]
 EINVAL = -1
-
-
-def _declared(header, prefix):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(rf"\b({prefix}_[a-z0-9_]+)\s*\(", src)))
 
 
 @pytest.fixture(scope="module")

@@ -1,41 +1,16 @@
 """CPU: the refinement entry points are declared (include/gaussctrl_refine.h), exported and bound with matching argument counts; the config switch and the new
 splatfacto fields exist with their defaults; the schedule predicates of gaussctrl_amd/refine.py against hand-written cases."""
-import os
-import re
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi_header as A
+
 NEW = ("gc_refine_accumulate_views", "gc_refine_plan_workspace_bytes", "gc_refine_plan", "gc_refine_apply", "gc_refine_reset_opacity")
-
-
-def _header():
-    src = open(os.path.join(ROOT, "include", "gaussctrl_refine.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def _call_args(text, start):
-    """number of top-level arguments of the call whose '(' is at text[start]"""
-    depth, n, i, seen = 0, 0, start, False
-    while True:
-        ch = text[i]
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-            if depth == 0:
-                return n + 1 if seen else 0
-        elif ch == "," and depth == 1:
-            n += 1
-        elif depth >= 1 and not ch.isspace():
-            seen = True
-        i += 1
 
 
 def test_refine_symbols_declared_listed_and_exported():
     import ctypes
     from gaussctrl_amd import _lib
-    src = _header()
-    declared = set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
+    declared = set(A.names("gaussctrl_refine.h"))
     for name in NEW:
         assert name in declared, name
         assert name in _lib.SYMBOLS, name
@@ -45,20 +20,15 @@ def test_refine_symbols_declared_listed_and_exported():
 
 
 def test_refine_bindings_pass_the_declared_number_of_arguments():
-    """every lib.gc_refine_*( call of the host layer passes as many arguments as the header's prototype has parameters"""
-    src = _header()
-    declared = {}
-    for name in NEW:
-        m = re.search(r"\b" + name + r"\s*\(", src)
-        declared[name] = _call_args(src, m.end() - 1)
+    """every call("gc_refine_*", ...) of the host layer passes, with the stream call() appends, as many arguments as the header's prototype
+    has parameters; the binding table has that arity too (_abi_header.sites)"""
+    declared = A.arities("gaussctrl_refine.h")
     assert declared == {"gc_refine_accumulate_views": 9, "gc_refine_plan_workspace_bytes": 1, "gc_refine_plan": 24, "gc_refine_apply": 16,
                         "gc_refine_reset_opacity": 6}
-    host = open(os.path.join(ROOT, "gaussctrl_amd", "refine.py")).read()
-    called = set()
-    for m in re.finditer(r"\.(gc_refine_[a-z_]+)\s*\(", host):
-        assert _call_args(host, m.end() - 1) == declared[m.group(1)], m.group(1)
-        called.add(m.group(1))
-    assert called == set(NEW)
+    sites = A.sites("gaussctrl_amd/refine.py", "gaussctrl_refine.h")
+    for name, passed in sites.items():
+        assert all(n == declared[name] for n in passed), (name, passed)
+    assert set(sites) == set(NEW)
 
 
 def test_refine_config_switch_and_defaults():

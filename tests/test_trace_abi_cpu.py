@@ -10,15 +10,11 @@ import types
 import pytest
 import torch
 
+from _abi_header import names as _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["gc_adam_step_rows", "gc_trace_mask_views", "gc_trace_select"]
 EINVAL = -1
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src)))
 
 
 @pytest.fixture(scope="module")
