@@ -233,7 +233,7 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs &g, f32x4 (&acc)[NT
 {
     const int fr = lane & 15, fc = lane >> 4;
     const int64_t n_lane = n_wave + fc * 4;
-    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice`
+    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice` (one of four COPIES: k_gemm, k_gemm8, k_gemm8q, wave_epilogue)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int64_t m = m_wave + mt * 16 + fr;
@@ -619,11 +619,11 @@ __global__ __launch_bounds__(NT, 2) void k_gemm(const GemmArgs g)
         wave_epilogue<T, NTW, 4, NT>(g, acc, m_base, m_base + wm * 64, n_base + wn * (16 * NTW), lane, smem, nullptr, slice);
         return;
     }
-    // ---- epilogue: lane holds out[m = m0 + (lane&15)][n = n0 + 4*(lane>>4) + r], r = 0..3.
+    // ---- epilogue: lane holds out[m = m0 + (lane&15)][n = n0 + 4*(lane>>4) + r], r = 0..3 -- the FULL epilogue is one of four COPIES (k_gemm, k_gemm8, k_gemm8p's subset, k_gemm8q + out_fp8): a fix to one is a fix to all; DESIGN.md 3.2 has what sharing them costs.
     // All operand loads of a row (bias once per lane; row-vector + residual per m-tile) are issued together BEFORE they are
     // used: the naive per-accumulator load->use chain cost ~1 us of latency x 20 accumulators on every launch.
     const int64_t n_lane = n_base + wn * (16 * NTW) + fc * 4;
-    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice`
+    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice` (one of four COPIES: k_gemm, k_gemm8, k_gemm8q, wave_epilogue)
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const int64_t m = m_base + wm * 64 + mt * 16 + fr;
@@ -773,6 +773,204 @@ __device__ __forceinline__ void glds16_s(const void *sbase, unsigned voff, unsig
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
 
+// =====================================================================================================================
+// Shared pieces of the 8-wave LDS-DMA kernels k_gemm8 / k_gemm8p / k_gemm8q: the kernels below are shells that assemble them.  Every piece
+// is a namespace-level __forceinline__ template that takes values, read-only references and always_inline callables.  What the invariant
+// above needs is that no LOOP STATE is advanced through a reference: the KCur cursor and the stage / k-tile counters are by-value loop
+// variables (ring_loop) or returned values (ring_prime, tile_conv); references carry only what is written once per call (the accumulators
+// of mfma_block, the fragment buffer of load_frag) or only read.  EB = bytes per operand element (2: bf16 / f16, 1: e4m3) -- a k-tile is 128
+// bytes per row either way, so the LDS image, the swizzle and the per-lane DMA plan are one text in bytes per element.
+template <int NTW, int MT> struct Tile8 {          // workgroup tile (64 MT) x (32 NTW), waves 4 (M) x 2 (N), wave tile (16 MT) x (16 NTW)
+    static constexpr int BM = 64 * MT, BN = 32 * NTW, STAGE = BM * 128 + BN * 128, NS = 3;
+    static constexpr int AG = BM / 8, WG = BN / 8;           // 8-row groups (one LDS-DMA instruction each)
+    static constexpr int AI = AG / 8, WI = (WG + 7) / 8;     // instructions per wave per tile: A MT, W 2|3
+    static constexpr int NMM = NTW * MT, NPC = AI + WI;      // MFMAs of a block, DMA pieces of a k-tile
+    // LDS-DMA instructions of a wave per k-tile; W3: the wave owns the last W group (wid + 8 (WI - 1) < WG)
+    static constexpr int grpw(bool w3) { return AI + ((w3 || WG % 8 == 0) ? WI : WI - 1); }
+};
+
+// ---- per-lane DMA plan.  Lane (lr = lane >> 3, ls = lane & 7) of wave `wid` writes slot ls of row (wid + 8 i) * 8 + lr in instruction i and
+// therefore fetches the swizzled chunk ls ^ ((row >> 1) & 7) of that row.
+template <int N> struct LaneOff { int v[N]; };
+// aligned plan (K a multiple of the k-tile): rows past the last one re-read it (their outputs are never stored), so a k-tile's DMA is a
+// uniform base + a constant per-lane ELEMENT offset -- no VALU at all in the issue path.  One text for the A rows (base m, M rows, lda) and
+// the W rows (base n, N rows, K): aligned_off is the offset of one (row, chunk); aligned_plan walks a wave's row groups (k_gemm8p, k_gemm8q).
+// k_gemm8 MODE 3 calls aligned_off from the row loops it shares with its other modes: through aligned_plan its 100 instantiations got
+// another prologue (the swizzled chunk hoisted out of the row-group loop), through aligned_off they are the code they were.
+template <int EB> __device__ __forceinline__ int aligned_off(int64_t r, int64_t rows, int ld, int ck) { return (int)(r < rows ? r : rows - 1) * ld + ck * (16 / EB); }
+template <int EB, int N>
+__device__ __forceinline__ LaneOff<N> aligned_plan(int wid, int lane, int64_t base, int64_t rows, int ld)
+{
+    LaneOff<N> o;
+    const int lr = (lane & 63) >> 3, ls = lane & 7;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int row = (wid + 8 * i) * 8 + lr;
+        const int64_t r = base + row;
+        o.v[i] = aligned_off<EB>(r, rows, ld, ls ^ ((row >> 1) & 7));
+    }
+    return o;
+}
+template <int EB> __device__ __forceinline__ void dma_aligned(const unsigned char *base, int kb, int off, unsigned dst)
+{
+    glds16_s(base + (size_t)kb * EB, (unsigned)(off * EB), dst);
+}
+// fast-conv plan (3x3, one tap per k-tile): a lane pointer to the tap origin (oy stride - pad, ox stride - pad) of its pixel and a 9-bit mask
+// of the taps that fall inside the image; a k-tile adds the wave-uniform tap offset of TileSrc (tile_conv below), lanes outside fetch the
+// zero page.  Pointer, mask and the two-line tap DMA are built in each kernel: the pointer is 32-bit element offsets in k_gemm8 (shared with
+// its other conv modes) and 64-bit bytes in k_gemm8q; the mask loop and the tap DMA are marked copies (see k_gemm8).
+struct ConvPixel { int b, y0, x0; };        // output row mm of an implicit-GEMM conv -> batch and the input coordinates of its (0, 0) tap
+__device__ __forceinline__ ConvPixel conv_pixel(const GemmArgs &g, int mm)
+{
+    const int hw = g.Ho * g.Wo;
+    const int b = mm / hw;
+    const int rem = mm - b * hw;
+    const int oy = rem / g.Wo;
+    return ConvPixel{b, oy * g.stride - g.pad, (rem - oy * g.Wo) * g.stride - g.pad};
+}
+// source of one k-tile: W column kb, tap and tap offset (elements) of the fast convs, LDS stage base, and the cursor of the NEXT k-tile
+struct TileSrc { int kb, dy_u, dx_u, tap_off, tap; unsigned sbase; KCur next; };
+__device__ __forceinline__ TileSrc tile_linear(int kb, unsigned sbase) { return TileSrc{kb, 0, 0, 0, 0, sbase, KCur{0, 0}}; }
+template <bool UPS>
+__device__ __forceinline__ TileSrc tile_conv(const KOrder &kord, const KCur c, int cin, int wi, unsigned sbase)
+{
+    TileSrc t;
+    const int ci = kord.ci(c);
+    t.tap = kord.tap(c);
+    t.kb = __builtin_amdgcn_readfirstlane(t.tap * cin + ci);          // W column of this k-tile (= the tile index x k-tile in the tap-outer order)
+    t.dy_u = t.tap / 3; t.dx_u = t.tap - t.dy_u * 3;
+    t.tap_off = UPS ? ci : (t.dy_u * wi + t.dx_u) * cin + ci;
+    t.next = kord.next(c);
+    t.sbase = sbase;
+    return t;
+}
+
+// ---- fragment addressing.  Row = rowbase + 16 t + fr (rowbase % 16 == 0), so the swizzle term ((row >> 1) & 7) does not depend on t:
+// address(t, chunk) = base + chunk offset + t * 2048 -- two VGPRs per operand, everything else is an immediate offset.  Lane group fc reads
+// chunks (fc, fc + 4) of the row's 128 bytes: the two k-halves of a 2-byte k-tile (one ds_read_b128 per MFMA k-step), or both at once as the
+// 32 bytes of k-block fc of an e4m3 k-tile (ONE MFMA k-step; which two chunks a lane group feeds is free there as A and W use the same
+// association, and this pair is conflict-free under the swizzle -- (2 fc, 2 fc + 1) was not: profiles/r05_pmc_gemm8q.txt).
+// The four values are one expression, FRAG_ADDR, expanded in each kernel's body -- a macro because a function is simplified on its own before
+// it is inlined, without the kernel's wm = wid >> 1 and lane = tid & 63, and the address adds of the k loop then come out in another form
+// (k_gemm8p<BF16, 4, 4, 2>: 4 670 -> 4 698 instructions, from (lane, wm, wn), (lane, wid) or (tid, wid) alike).
+struct FragAddr { int fx0, fx1, aw0, aa0; };      // chunk offsets of the two k-halves; W / A row base of this lane
+// (#undef'd behind k_gemm8q, its last user)
+#define FRAG_ADDR(ntw, mt, fr, fc, wm, wn) \
+    {((fc) ^ (((fr) >> 1) & 7)) << 4, (((fc) + 4) ^ (((fr) >> 1) & 7)) << 4, 64 * (mt) * 128 + ((wn) * (16 * (ntw)) + (fr)) * 128, ((wm) * (16 * (mt)) + (fr)) * 128}
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+template <class V, int NTW, int MT> struct Frag { V w[NTW], a[MT]; };      // V = uint4 (2-byte k-half) | i32x8 (e4m3 k-tile)
+__device__ __forceinline__ void frag_read(uint4 &d, const unsigned char *p0, const unsigned char *) { d = *reinterpret_cast<const uint4 *>(p0); }
+__device__ __forceinline__ void frag_read(i32x8 &d, const unsigned char *p0, const unsigned char *p1)
+{       // 8-register MFMA operand assembled ONCE at load time from two ds_read_b128
+    const i32x4 lo = *reinterpret_cast<const i32x4 *>(p0), hi = *reinterpret_cast<const i32x4 *>(p1);
+    d = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// sb = LDS stage; ks = k-half of a 2-byte k-tile (an e4m3 fragment takes both chunks)
+template <class V, int NTW, int MT>
+__device__ __forceinline__ void load_frag(Frag<V, NTW, MT> &f, const unsigned char *sb, const FragAddr &fa, int ks)
+{
+    const int fx = (std::is_same<V, uint4>::value && ks) ? fa.fx1 : fa.fx0;
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) frag_read(f.w[t], sb + fa.aw0 + fx + t * 2048, sb + fa.aw0 + fa.fx1 + t * 2048);
+#pragma unroll
+    for (int t = 0; t < MT; ++t) frag_read(f.a[t], sb + fa.aa0 + fx + t * 2048, sb + fa.aa0 + fa.fx1 + t * 2048);
+}
+
+// ---- one MFMA block: NTW x MT MFMAs on the fragments of one k-step, acc[nt][mt] = mma(nt, w[nt], a[mt], acc[nt][mt]).  After the FIRST MFMA
+// `load_next` issues the fragment reads of the next block (the s_waitcnt for this block's operands then never waits behind fresh reads);
+// with DMA = true the NPC LDS-DMA pieces `piece(p)` of a later k-tile (and their address arithmetic) are spread between the remaining
+// MFMAs, piece p after MFMA index 2 + p (NMM - 3) / NPC, where a few VALU / SALU instructions per MFMA issue for free.
+template <int NTW, int MT, bool DMA, class F, class Mma, class LoadNext, class Piece>
+__device__ __forceinline__ void mfma_block(f32x4 (&acc)[NTW][MT], const F &f, Mma &&mma, LoadNext &&load_next, Piece &&piece)
+{
+    constexpr int NMM = Tile8<NTW, MT>::NMM, NPC = Tile8<NTW, MT>::NPC;
+    static_for<0, NMM>([&](auto m_) __attribute__((always_inline)) {
+        constexpr int m = decltype(m_)::value, nt = m / MT, mt = m % MT;
+        acc[nt][mt] = mma(std::integral_constant<int, nt>{}, f.w[nt], f.a[mt], acc[nt][mt]);
+        if constexpr (m == 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_next();
+            __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (DMA && m >= 2) {
+            static_for<0, NPC>([&](auto p_) __attribute__((always_inline)) {
+                if constexpr (m == 2 + (decltype(p_)::value * (NMM - 3)) / NPC) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    piece(p_);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+        }
+    });
+}
+
+// ---- ring control: 3 LDS stages, LDS-DMA two tiles ahead, ONE barrier per k-tile, counted s_waitcnt vmcnt(N) (never 0 in the steady state).
+// GRPW = LDS-DMA instructions of this wave per k-tile (Tile8::grpw).
+template <int N, int GRPW> __device__ __forceinline__ void wait_tiles()        // N tiles may stay in flight
+{
+    static_assert(2 * GRPW < 64, "vmcnt range");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N * GRPW) : "memory");
+}
+// the first min(nk, 3) k-tiles go into stages 0 .. 2; returns the cursor of k-tile 3
+template <class Issue> __device__ __forceinline__ KCur ring_prime(int nk, const KCur c0, Issue &&issue)
+{
+    KCur cur = issue(0, 0, c0);
+    if (nk > 1) cur = issue(1, 1, cur);
+    if (nk > 2) cur = issue(2, 2, cur);
+    return cur;
+}
+template <int GRPW> __device__ __forceinline__ void ring_wait_first(int nk)    // k-tile 0 has landed (for this wave; the barrier follows)
+{
+    if (nk > 2) wait_tiles<2, GRPW>(); else if (nk > 1) wait_tiles<1, GRPW>(); else wait_tiles<0, GRPW>();
+}
+// the next k-tile is in LDS for every wave and every wave finished reading the current stage; `behind` = a further tile stays in flight
+template <int GRPW> __device__ __forceinline__ void ring_turn(bool behind)
+{
+    if (behind) wait_tiles<1, GRPW>(); else wait_tiles<0, GRPW>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the current stage are complete
+    __builtin_amdgcn_s_barrier();
+}
+// k loop of the 2-byte kernels, entered with k-tile 0 landed for this wave.  Fragment registers double-buffered per k half:
+//   [ MFMAs on F0 = (kt, half 0) | read F1 <- (kt, half 1) ]  wait(tile kt+1 landed) + barrier
+//   [ MFMAs on F1 | read F0 <- (kt+1, half 0) | DMA tile kt+3 -> stage of kt ]
+// The barrier sits between two MFMA blocks whose operands are already in registers; every ds_read has a full MFMA block (16-20 x 16 clk) to
+// land.  The steady state (tiles kt+1 .. kt+3 exist) is a branch-free loop, the last three k-tiles run through the generic tail.
+// begin(kt, stage, cursor) -> TileSrc; block(f, fn, stage_next, half_next, load_next, tile, dma_tag) = one mfma_block; the cursor is a
+// by-value loop variable of this function.  nk and the first cursor arrive as const REFERENCES, read-only: a function is simplified on its own
+// before it is inlined, and with nk as a plain value the steady-state loop is rewritten there into a count-down form (another exit test and
+// induction variable than the loop had inside the kernels); behind a reference it stays opaque until it is inlined, as a lambda's captures are.
+template <int GRPW, class F, class LoadFrag, class Begin, class Block>
+__device__ __forceinline__ void ring_loop(const int &nk, const KCur &cur0, LoadFrag &&load, Begin &&begin, Block &&block)
+{
+    constexpr int NS = 3;
+    const TileSrc tnone = {0, 0, 0, 0, 0, 0u, {0, 0}};
+    F f0, f1;
+    KCur cur = cur0;
+    __builtin_amdgcn_s_barrier();
+    load(f0, 0, 0);
+    int st = 0, kt = 0;                   // st = stage of tile kt
+    for (; kt + 3 < nk; ++kt) {
+        const int st1 = st + 1 == NS ? 0 : st + 1;
+        block(f0, f1, st, 1, true, tnone, std::false_type{});
+        ring_turn<GRPW>(true);
+        const TileSrc t = begin(kt + 3, st, cur);
+        cur = t.next;
+        block(f1, f0, st1, 0, true, t, std::true_type{});
+        st = st1;
+    }
+    for (; kt < nk; ++kt) {
+        const int st1 = st + 1 == NS ? 0 : st + 1;
+        block(f0, f1, st, 1, true, tnone, std::false_type{});
+        const bool more = kt + 1 < nk;
+        if (more) ring_turn<GRPW>(kt + 2 < nk);
+        // ONE copy of this MFMA block (the fragment reads inside are the only difference of the last tile).  With a copy in either arm of
+        // the branch the register allocator kept TWO sets of accumulators here (block 1 wrote set B from set A, block 2 set A from set B):
+        // 16 NTW MT registers more than the steady state needs -- every MT 4 instantiation sat at the 256 cap and MODE 0 / 1 spilled.
+        block(f1, f0, st1, 0, more, tnone, std::false_type{});
+        st = st1;
+    }
+}
+
 // MODE 3 (k_gemm8 only): linear with K % 64 == 0 -- rows past M / N re-read the last valid row (their outputs are never stored),
 // so a k-tile's DMA is a uniform base + constant per-lane offset: no VALU at all in the issue path.
 // MT: m-tiles (of 16) per wave: workgroup tile (64 MT) x (32 NTW), waves 4 (M) x 2 (N), wave tile (16 MT) x (16 NTW).
@@ -796,13 +994,9 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
     // wave's 80 columns of the row: 20 values per lane, 4 lanes per row) and stores the probabilities.
     constexpr bool LNIN = LNV >= 2;
     constexpr bool LEAN = LEAN_ || CS;
-    constexpr int BM = 64 * MT;
+    using G8 = Tile8<NTW, MT>;
+    constexpr int BM = G8::BM, BN = G8::BN, STAGE = G8::STAGE, NS = G8::NS, WG = G8::WG, AI = G8::AI, WI = G8::WI;
     constexpr bool CONVF = MODE == 2 || MODE == 4, UPS = MODE == 4;   // MODE 4 = MODE 2 + fused nearest-x2 upsample
-    constexpr int BN = 32 * NTW;
-    constexpr int STAGE = BM * 128 + BN * 128;
-    constexpr int NS = 3;
-    constexpr int AG = BM / 8, WG = BN / 8;           // 8-row groups (one LDS-DMA instruction each)
-    constexpr int AI = AG / 8, WI = (WG + 7) / 8;     // instructions per wave per tile: A MT, W 2|3
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -825,7 +1019,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         for (int i = tid; i < 4 * BN; i += 512) ctab[i] = 0.f;
     }
 
-    // ---- per-lane DMA coordinates
+    // ---- per-lane DMA coordinates: MODE 3 the aligned plan, MODE 2 the fast-conv plan (shared pieces above); MODE 0 / 1 / 4 per-lane
+    // element offsets with a validity test per k-tile, invalid lanes fetch the zero page
     const int lr = lane >> 3, ls = lane & 7;
     int a_off[AI], a_y[AI], a_x[AI], a_ck[AI];
     bool a_ok[AI];
@@ -837,16 +1032,13 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         a_ok[i] = m < g.M;
         const int mm = a_ok[i] ? (int)m : 0;
         if (MODE == 1 || CONVF) {
-            const int hw = g.Ho * g.Wo;
-            const int b = mm / hw;
-            const int rem = mm - b * hw;
-            const int oy = rem / g.Wo;
-            a_y[i] = oy * g.stride - g.pad; a_x[i] = (rem - oy * g.Wo) * g.stride - g.pad;
-            a_off[i] = b * g.Hi * g.Wi * g.Cin + (CONVF ? a_ck[i] * 8 : 0);
+            const ConvPixel px = conv_pixel(g, mm);
+            a_y[i] = px.y0; a_x[i] = px.x0;
+            a_off[i] = px.b * g.Hi * g.Wi * g.Cin + (CONVF ? a_ck[i] * 8 : 0);
             if (MODE == 2) a_off[i] += (a_y[i] * g.Wi + a_x[i]) * g.Cin;
         } else {
             a_off[i] = mm * (int)g.lda + a_ck[i] * 8;
-            if (MODE == 3) a_off[i] = (int)(m < g.M ? m : g.M - 1) * (int)g.lda + a_ck[i] * 8;
+            if (MODE == 3) a_off[i] = aligned_off<2>(m, g.M, (int)g.lda, a_ck[i]);
             a_y[i] = a_x[i] = 0;
         }
     }
@@ -860,17 +1052,21 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         const int64_t n = n_base + row;
         w_ok[i] = grp < WG && n < g.N;
         w_off[i] = (w_ok[i] ? (int)n : 0) * (int)g.K + w_ck[i] * 8;
-        if (MODE == 3) w_off[i] = (int)(n < g.N ? n : g.N - 1) * (int)g.K + w_ck[i] * 8;
+        if (MODE == 3) w_off[i] = aligned_off<2>(n, g.N, (int)g.K, w_ck[i]);
     }
     const bool ups = CONVF ? UPS : (g.ups != 0);
     const int Hin = ups ? g.Hi * 2 : g.Hi, Win = ups ? g.Wi * 2 : g.Wi;
-    // MODE 2: per-lane source pointer of the centre-less tap origin and a 9-bit mask of the taps that fall inside the image
+    const int64_t wset = (LNV != 0 && g.w_set_rows > 0) ? m_base / g.w_set_rows : 0;          // weight set of this row tile (never straddles: host check)
+    const unsigned char *Ab = (const unsigned char *)g.A, *Wb = (const unsigned char *)g.W + (LNV != 0 ? wset * g.w_set_stride * 2 : 0);
+    const unsigned char *Zp = (const unsigned char *)g.zeros;
     const unsigned char *a_ptr[AI];
     unsigned a_vm[AI];
     if (MODE == 2) {
 #pragma unroll
         for (int i = 0; i < AI; ++i) {
             a_ptr[i] = (const unsigned char *)g.A + (int64_t)a_off[i] * 2;
+            // The mask loop is written out here and in k_gemm8q (two COPIES): as a function (y0, x0, ok, H, W) -> mask it cost a VGPR in
+            // every MODE 2 instantiation (k_gemm8<BF16, 2, 5, 4, CS>: 216 -> 217; k_gemm8q<BF16, 2, 4, 2, CS>: 183 -> 186).
             unsigned vm = 0;
 #pragma unroll
             for (int tp = 0; tp < 9; ++tp) {
@@ -880,9 +1076,6 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
             a_vm[i] = vm;
         }
     }
-    const int64_t wset = (LNV != 0 && g.w_set_rows > 0) ? m_base / g.w_set_rows : 0;          // weight set of this row tile (never straddles: host check)
-    const unsigned char *Ab = (const unsigned char *)g.A, *Wb = (const unsigned char *)g.W + (LNV != 0 ? wset * g.w_set_stride * 2 : 0);
-    const unsigned char *Zp = (const unsigned char *)g.zeros;
     // k order of the fast convs (round 6).  The K axis of W is (tap, ci); the k-tile SEQUENCE j = kt0 + kt may walk it in either order:
     //   tap-inner (default, g.conv_korder = 1): j -> (ci slice j / 9, tap j % 9).  Nine consecutive k-tiles fetch the SAME 64-channel slice of
     //     pixels shifted by one tap: the A lines of a k-tile are L1 / L2 hits of the previous ones (reuse distance one k-tile).
@@ -900,26 +1093,15 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
     if (CONVF && kt0 > 0) cur0 = kord.at(kt0, BK, g.Cin);
 
     // DMA of one k-tile, split into per-instruction pieces so that the main loop can place them between MFMAs.
-    struct TileSrc { int kb, dy_u, dx_u, tap_off, tap; unsigned sbase; KCur next; };
     auto issue_begin = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> TileSrc {
-        TileSrc t;
-        t.kb = (kt0 + kt) * BK; t.dy_u = 0; t.dx_u = 0; t.tap_off = 0; t.tap = 0; t.next = c;
-        if (CONVF) {
-            const int ci = kord.ci(c);
-            t.tap = kord.tap(c);
-            t.kb = __builtin_amdgcn_readfirstlane(t.tap * g.Cin + ci);          // W column of this k-tile (= (kt0 + kt) * BK in the tap-outer order)
-            t.dy_u = t.tap / 3; t.dx_u = t.tap - t.dy_u * 3;
-            t.tap_off = UPS ? ci : (t.dy_u * g.Wi + t.dx_u) * g.Cin + ci;
-            t.next = kord.next(c);
-        }
-        t.sbase = lds0 + stage * STAGE;
-        return t;
+        if constexpr (CONVF) return tile_conv<UPS>(kord, c, g.Cin, g.Wi, lds0 + stage * STAGE);
+        else return tile_linear((kt0 + kt) * BK, lds0 + stage * STAGE);
     };
     auto issue_a = [&](const TileSrc &t, int i) __attribute__((always_inline)) {
         const unsigned dst = t.sbase + (unsigned)((wid + 8 * i) * 1024);
-        if (MODE == 3) { glds16_s(Ab + (size_t)t.kb * 2, (unsigned)(a_off[i] * 2), dst); return; }
-        if (MODE == 2) {     // tap validity from the precomputed mask, address = lane pointer + uniform tap offset
-            const bool okm = (a_vm[i] >> t.tap) & 1u;
+        if (MODE == 3) { dma_aligned<2>(Ab, t.kb, a_off[i], dst); return; }
+        if (MODE == 2) {     // tap validity from the precomputed mask, address = lane pointer + uniform tap offset (a COPY of k_gemm8q's two lines:
+            const bool okm = (a_vm[i] >> t.tap) & 1u;                           // as a function they cost a scheduling slot here and 2 - 3 VGPRs there)
             glds16(okm ? a_ptr[i] + (int64_t)t.tap_off * 2 : Zp, dst);
             return;
         }
@@ -947,11 +1129,12 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         const unsigned char *src = ok ? Ab + (size_t)(unsigned)(off * 2) : Zp;
         glds16(src, dst);
     };
-    // has_w(i): W group i of this wave exists (the last group only for the waves with wid + 8 (WI-1) < WG: "w3" waves)
+    // has: W group i of this wave exists (the last group only for the waves with wid + 8 (WI-1) < WG: "w3" waves)
     auto issue_w = [&](const TileSrc &t, int i, bool has) __attribute__((always_inline)) {
         if (has) {
             const unsigned dst = t.sbase + (unsigned)(BM * 128 + (wid + 8 * i) * 1024);
-            if (MODE == 3 || CONVF) { glds16_s(Wb + (size_t)t.kb * 2, (unsigned)(w_off[i] * 2), dst); return; }   // K % 64 == 0: rows past N re-read row 0
+            if (MODE == 3) { dma_aligned<2>(Wb, t.kb, w_off[i], dst); return; }
+            if (CONVF) { dma_aligned<2>(Wb, t.kb, w_off[i], dst); return; }   // K % 64 == 0: rows past N re-read row 0
             const bool ok = w_ok[i] && (t.kb + w_ck[i] * 8) < (int)g.K;
             const unsigned char *src = ok ? Wb + (size_t)(unsigned)((w_off[i] + t.kb) * 2) : Zp;
             glds16(src, dst);
@@ -972,100 +1155,30 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
 #pragma unroll
         for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, fc = lane >> 4;
-    const int swz = (fr >> 1) & 7;
-    const int fx0 = ((fc ^ swz) << 4), fx1 = (((fc + 4) ^ swz) << 4);
-    const int aw0 = BM * 128 + (wn * (16 * NTW) + fr) * 128, aa0 = (wm * (16 * MT) + fr) * 128;
-    struct Frag { uint4 w[NTW], a[MT]; };
-    auto load_frag = [&](Frag &f, int stage, int ks) __attribute__((always_inline)) {
-        const unsigned char *sb = smem + stage * STAGE;
-        const int fx = ks ? fx1 : fx0;
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) f.w[t] = *reinterpret_cast<const uint4 *>(sb + aw0 + fx + t * 2048);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) f.a[t] = *reinterpret_cast<const uint4 *>(sb + aa0 + fx + t * 2048);
-    };
-    // one MFMA block (NTW x MT MFMAs on the fragments of one k-half).  After the FIRST MFMA the fragment reads of the next
-    // block are issued (the s_waitcnt for this block's operands then never waits behind fresh reads); with DMA = true the LDS-DMA
-    // instructions of a later k-tile (and their address arithmetic) are spread between the remaining MFMAs, where a few VALU /
-    // SALU instructions per MFMA issue for free.
-    constexpr int NMM = NTW * MT, NPC = AI + WI;
-    auto block = [&](const Frag &f, Frag &fn, int st_next, int ks_next, bool load_next, const TileSrc &t, auto dma_tag, auto w3_tag) __attribute__((always_inline)) {
-        constexpr bool DMA = decltype(dma_tag)::value, W3 = decltype(w3_tag)::value;
-        static_for<0, NMM>([&](auto m_) __attribute__((always_inline)) {
-            constexpr int m = decltype(m_)::value, nt = m / MT, mt = m % MT;
-            acc[nt][mt] = T::mfma(f.w[nt], f.a[mt], acc[nt][mt]);
-            if constexpr (m == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (load_next) load_frag(fn, st_next, ks_next);
-                __builtin_amdgcn_sched_barrier(0);
-            } else if constexpr (DMA && m >= 2) {
-                // pieces p = 0 .. NPC-1 after MFMA index 2 + p * (NMM - 3) / NPC
-                static_for<0, NPC>([&](auto p_) __attribute__((always_inline)) {
-                    constexpr int pp = decltype(p_)::value;
-                    if constexpr (m == 2 + (pp * (NMM - 3)) / NPC) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (pp < AI) issue_a(t, pp); else issue_w(t, pp - AI, (pp - AI) < WI - 1 || W3 || WG % 8 == 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                });
-            }
-        });
-    };
-
-    // Software pipeline over k-tiles (3 LDS stages, LDS-DMA two tiles ahead; fragment registers double-buffered per k half):
-    //   [ MFMAs on F0 = (kt, half 0) | read F1 <- (kt, half 1) ]  wait(tile kt+1 landed) + barrier
-    //   [ MFMAs on F1 | read F0 <- (kt+1, half 0) | DMA tile kt+3 -> stage of kt ]
-    // ONE barrier per k-tile, sitting between two MFMA blocks whose operands are already in registers; every ds_read has a full
-    // MFMA block (16-20 x 16 clk) to land.  Counted vmcnt: tile kt+2 stays in flight across the barrier.
+    const FragAddr fa = FRAG_ADDR(NTW, MT, fr, fc, wm, wn);
+    using FragT = Frag<uint4, NTW, MT>;
+    auto load = [&](FragT &f, int stage, int ks) __attribute__((always_inline)) { load_frag(f, smem + stage * STAGE, fa, ks); };
     const bool w3 = (wid + 8 * (WI - 1)) < WG;     // this wave owns the last W group (instructions per tile are wave-uniform)
-    Frag f0, f1;
-    const TileSrc tnone = {0, 0, 0, 0, 0, 0u, {0, 0}};
     // The whole k loop is instantiated twice (W3 = this wave issues WI / WI-1 W loads per tile) so that the counted waits and the
-    // DMA pieces carry no run-time branches; the steady state (tiles kt+1 .. kt+3 exist) is a branch-free loop, the last three
-    // k-tiles run through the generic tail.
+    // DMA pieces carry no run-time branches.
     auto run = [&](auto w3_tag) __attribute__((always_inline)) {
         constexpr bool W3 = decltype(w3_tag)::value;
-        constexpr int GRPW = AI + ((W3 || WG % 8 == 0) ? WI : WI - 1);        // LDS-DMA instructions of this wave per k-tile
-        static_assert(2 * GRPW < 64, "vmcnt range");
-        auto wait_tiles = [&](auto n_) __attribute__((always_inline)) {        // n tiles may stay in flight
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_)::value * GRPW) : "memory");
-        };
-        KCur cur = issue(0, 0, cur0);      // the cursor: a by-value loop variable of this copy of the loop
-        if (nk > 1) cur = issue(1, 1, cur);
-        if (nk > 2) cur = issue(2, 2, cur);
+        constexpr int GRPW = G8::grpw(W3);
+        const KCur cur = ring_prime(nk, cur0, issue);
         // lean LayerNorm-folded consumer: the rows' statistics are summed over the producer's slabs HERE, under the first k-tiles' flight (the
         // prologue ends in vmcnt(0): it waits for those tiles too, which the loop would do next anyway)
         if constexpr (LNIN) row_stats_prologue<BM>(g, m_base, srow);
-        if (nk > 2) wait_tiles(std::integral_constant<int, 2>{}); else if (nk > 1) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
-        __builtin_amdgcn_s_barrier();
-        load_frag(f0, 0, 0);
-        int st = 0, kt = 0;                   // st = stage of tile kt
-        for (; kt + 3 < nk; ++kt) {
-            const int st1 = st + 1 == NS ? 0 : st + 1;
-            block(f0, f1, st, 1, true, tnone, std::false_type{}, w3_tag);
-            wait_tiles(std::integral_constant<int, 1>{});
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of stage st are complete
-            __builtin_amdgcn_s_barrier();    // tile kt+1 is in LDS for every wave; every wave finished reading stage st
-            const TileSrc t = issue_begin(kt + 3, st, cur);
-            cur = t.next;
-            block(f1, f0, st1, 0, true, t, std::true_type{}, w3_tag);
-            st = st1;
-        }
-        for (; kt < nk; ++kt) {
-            const int st1 = st + 1 == NS ? 0 : st + 1;
-            block(f0, f1, st, 1, true, tnone, std::false_type{}, w3_tag);
-            const bool more = kt + 1 < nk;
-            if (more) {
-                if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            // ONE copy of this MFMA block (the fragment reads inside are the only difference of the last tile).  With a copy in either arm of
-            // the branch the register allocator kept TWO sets of accumulators here (block 1 wrote set B from set A, block 2 set A from set B):
-            // 16 NTW MT registers more than the steady state needs -- every MT 4 instantiation sat at the 256 cap and MODE 0 / 1 spilled.
-            block(f1, f0, st1, 0, more, tnone, std::false_type{}, w3_tag);
-            st = st1;
-        }
+        ring_wait_first<GRPW>(nk);
+        ring_loop<GRPW, FragT>(nk, cur, load, issue_begin,
+            [&](const FragT &f, FragT &fn, int st_next, int ks_next, bool load_next, const TileSrc &t, auto dma_tag) __attribute__((always_inline)) {
+                mfma_block<NTW, MT, decltype(dma_tag)::value>(acc, f,
+                    [&](auto, const uint4 w, const uint4 a, const f32x4 c) __attribute__((always_inline)) { return T::mfma(w, a, c); },
+                    [&]() __attribute__((always_inline)) { if (load_next) load(fn, st_next, ks_next); },
+                    [&](auto p_) __attribute__((always_inline)) {
+                        constexpr int pp = decltype(p_)::value;
+                        if constexpr (pp < AI) issue_a(t, pp); else issue_w(t, pp - AI, (pp - AI) < WI - 1 || W3 || WG % 8 == 0);
+                    });
+            });
     };
     if (w3) run(std::true_type{}); else run(std::false_type{});
 
@@ -1074,9 +1187,9 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
                                        (g.row_stats && g.splits == 1) ? srow : nullptr, slice);
         return;
     }
-    // ---- epilogue (same math as k_gemm; MT m-tiles per wave)
+    // ---- epilogue (same math as k_gemm; MT m-tiles per wave) -- the FULL epilogue is one of four COPIES (k_gemm, k_gemm8, k_gemm8p's subset, k_gemm8q + out_fp8): a fix to one is a fix to all; DESIGN.md 3.2 has what sharing them costs
     const int64_t n_lane = n_base + wn * (16 * NTW) + fc * 4;
-    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice`
+    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice` (one of four COPIES: k_gemm, k_gemm8, k_gemm8q, wave_epilogue)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int64_t m = m_base + wm * (16 * MT) + mt * 16 + fr;
@@ -1138,7 +1251,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 2 : 1) void k_gemm8(const GemmArgs g
         return;
     }
     if constexpr (LEAN) {
-        // ---- lean epilogue.  EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
+        // ---- lean epilogue (k_gemm8q's CS epilogue is a COPY of the CS form of this block: a fix to one is a fix to both).
+        // EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
         // absent operands read the zero page), then the tile is computed and stored.  The generic epilogue loads bias / row-vector /
         // residual under per-lane branches inside the m loop: at every control-flow join hipcc falls back to s_waitcnt vmcnt(0), and on
         // gfx9 that counter also holds the STORES in flight -- MT x NTW serialised store round trips per wave (seen in the ISA).
@@ -1371,10 +1485,10 @@ template <class T, int NTW, int MT, int LNV = 0>
 __global__ __launch_bounds__(512, 1) void k_gemm8p(const GemmArgs g)
 {
     static_assert(LNV == 0 || LNV == 2, "persistent kernel: plain or LayerNorm-folded consumer");
-    constexpr int BM = 64 * MT, BN = 32 * NTW, STAGE = BM * 128 + BN * 128, NS = 3;
-    constexpr int AG = BM / 8, WG = BN / 8, AI = AG / 8, WI = (WG + 7) / 8;
-    static_assert(WG % 8 == 0, "every wave issues the same number of W loads");
-    constexpr int GRPW = AI + WI;
+    using G8 = Tile8<NTW, MT>;
+    constexpr int BM = G8::BM, BN = G8::BN, STAGE = G8::STAGE, NS = G8::NS, AI = G8::AI, WI = G8::WI;
+    static_assert(G8::WG % 8 == 0, "every wave issues the same number of W loads");
+    constexpr int GRPW = G8::grpw(true);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1384,7 +1498,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm8p(const GemmArgs g)
     const int nk = (int)(g.K / BK);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
     float *srow = reinterpret_cast<float *>(smem + NS * STAGE);          // LNV 2: [BM][2] row sums of the current tile, behind the ring
-    const int lr = lane >> 3, ls = lane & 7;
     const unsigned char *Ab = (const unsigned char *)g.A, *Wb = (const unsigned char *)g.W;
     // dispatch-order tile d -> XCD d % 8 (gridDim.x is a multiple of 8); remapped so that consecutive tiles share an XCD's L2
     auto tile_of = [&](int64_t d, int64_t &m_base, int64_t &n_base) __attribute__((always_inline)) {
@@ -1394,80 +1507,35 @@ __global__ __launch_bounds__(512, 1) void k_gemm8p(const GemmArgs g)
         dng::tile_coords(bid, (int)((g.M + BM - 1) / BM), nbn, g.pw, mblk, nblk);
         m_base = mblk * BM; n_base = nblk * BN;
     };
-    int a_off[AI], w_off[WI];
-    auto set_offsets = [&](int64_t m_base, int64_t n_base) __attribute__((always_inline)) {
+    // the k loop is k_gemm8's MODE 3 loop on the aligned plan of the tile in flight; the tile walk and the next-tile prefetch are this kernel's own
+    LaneOff<AI> pa;
+    LaneOff<WI> pw;
+    auto issue_begin = [&](int kt, int stage, const KCur) __attribute__((always_inline)) -> TileSrc { return tile_linear(kt * BK, lds0 + stage * STAGE); };
+    auto issue_a = [&](const TileSrc &t, int i) __attribute__((always_inline)) { dma_aligned<2>(Ab, t.kb, pa.v[i], t.sbase + (unsigned)((wid + 8 * i) * 1024)); };
+    auto issue_w = [&](const TileSrc &t, int i) __attribute__((always_inline)) { dma_aligned<2>(Wb, t.kb, pw.v[i], t.sbase + (unsigned)(BM * 128 + (wid + 8 * i) * 1024)); };
+    auto issue = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> KCur {
+        const TileSrc t = issue_begin(kt, stage, c);
 #pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int row = (wid + 8 * i) * 8 + lr;
-            const int64_t m = m_base + row;
-            a_off[i] = (int)(m < g.M ? m : g.M - 1) * (int)g.lda + (ls ^ ((row >> 1) & 7)) * 8;
-        }
+        for (int i = 0; i < AI; ++i) issue_a(t, i);
 #pragma unroll
-        for (int i = 0; i < WI; ++i) {
-            const int row = (wid + 8 * i) * 8 + lr;
-            const int64_t n = n_base + row;
-            w_off[i] = (int)(n < g.N ? n : g.N - 1) * (int)g.K + (ls ^ ((row >> 1) & 7)) * 8;
-        }
+        for (int i = 0; i < WI; ++i) issue_w(t, i);
+        return c;
     };
-    auto issue_a = [&](int kt, int stage, int i) __attribute__((always_inline)) {
-        glds16_s(Ab + (size_t)kt * (BK * 2), (unsigned)(a_off[i] * 2), lds0 + stage * STAGE + (unsigned)((wid + 8 * i) * 1024));
-    };
-    auto issue_w = [&](int kt, int stage, int i) __attribute__((always_inline)) {
-        glds16_s(Wb + (size_t)kt * (BK * 2), (unsigned)(w_off[i] * 2), lds0 + stage * STAGE + (unsigned)(BM * 128 + (wid + 8 * i) * 1024));
-    };
-    auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) issue_a(kt, stage, i);
-#pragma unroll
-        for (int i = 0; i < WI; ++i) issue_w(kt, stage, i);
+    auto first_tiles = [&](int64_t m_base, int64_t n_base) __attribute__((always_inline)) {     // the first min(nk, 3) k-tiles of a tile
+        pa = aligned_plan<2, AI>(wid, lane, m_base, g.M, (int)g.lda);
+        pw = aligned_plan<2, WI>(wid, lane, n_base, g.N, (int)g.K);
+        ring_prime(nk, KCur{0, 0}, issue);
     };
     const int fr = lane & 15, fc = lane >> 4;
-    const int swz = (fr >> 1) & 7;
-    const int fx0 = ((fc ^ swz) << 4), fx1 = (((fc + 4) ^ swz) << 4);
-    const int aw0 = BM * 128 + (wn * (16 * NTW) + fr) * 128, aa0 = (wm * (16 * MT) + fr) * 128;
-    struct Frag { uint4 w[NTW], a[MT]; };
-    auto load_frag = [&](Frag &f, int stage, int ks) __attribute__((always_inline)) {
-        const unsigned char *sb = smem + stage * STAGE;
-        const int fx = ks ? fx1 : fx0;
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) f.w[t] = *reinterpret_cast<const uint4 *>(sb + aw0 + fx + t * 2048);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) f.a[t] = *reinterpret_cast<const uint4 *>(sb + aa0 + fx + t * 2048);
-    };
+    const FragAddr fa = FRAG_ADDR(NTW, MT, fr, fc, wm, wn);
+    using FragT = Frag<uint4, NTW, MT>;
+    auto load = [&](FragT &f, int stage, int ks) __attribute__((always_inline)) { load_frag(f, smem + stage * STAGE, fa, ks); };
     f32x4 acc[NTW][MT];
-    constexpr int NMM = NTW * MT, NPC = AI + WI;
-    auto block = [&](const Frag &f, Frag &fn, int st_next, int ks_next, bool load_next, int dma_kt, int dma_stage, auto dma_tag) __attribute__((always_inline)) {
-        constexpr bool DMA = decltype(dma_tag)::value;
-        static_for<0, NMM>([&](auto m_) __attribute__((always_inline)) {
-            constexpr int m = decltype(m_)::value, nt = m / MT, mt = m % MT;
-            acc[nt][mt] = T::mfma(f.w[nt], f.a[mt], acc[nt][mt]);
-            if constexpr (m == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (load_next) load_frag(fn, st_next, ks_next);
-                __builtin_amdgcn_sched_barrier(0);
-            } else if constexpr (DMA && m >= 2) {
-                static_for<0, NPC>([&](auto p_) __attribute__((always_inline)) {
-                    constexpr int pp = decltype(p_)::value;
-                    if constexpr (m == 2 + (pp * (NMM - 3)) / NPC) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (pp < AI) issue_a(dma_kt, dma_stage, pp); else issue_w(dma_kt, dma_stage, pp - AI);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                });
-            }
-        });
-    };
-    auto wait_tiles = [&](auto n_) __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_)::value * GRPW) : "memory");
-    };
 
     int64_t d = blockIdx.x, m_base, n_base;
     if (d >= ntiles) return;
     tile_of(d, m_base, n_base);
-    set_offsets(m_base, n_base);
-    issue(0, 0);
-    if (nk > 1) issue(1, 1);
-    if (nk > 2) issue(2, 2);
+    first_tiles(m_base, n_base);
     bool first = true;
     for (;;) {
 #pragma unroll
@@ -1475,35 +1543,19 @@ __global__ __launch_bounds__(512, 1) void k_gemm8p(const GemmArgs g)
 #pragma unroll
             for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
         // ---- k loop (the first min(nk, 3) k-tiles of this tile are already in flight)
-        if (first) { if (nk > 2) wait_tiles(std::integral_constant<int, 2>{}); else if (nk > 1) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{}); }
+        if (first) ring_wait_first<GRPW>(nk);
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // prefetched under the previous epilogue (its stores are counted too)
         first = false;
-        __builtin_amdgcn_s_barrier();
-        Frag f0, f1;
-        load_frag(f0, 0, 0);
-        int st = 0, kt = 0;
-        for (; kt + 3 < nk; ++kt) {
-            const int st1 = st + 1 == NS ? 0 : st + 1;
-            block(f0, f1, st, 1, true, 0, 0, std::false_type{});
-            wait_tiles(std::integral_constant<int, 1>{});
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            block(f1, f0, st1, 0, true, kt + 3, st, std::true_type{});
-            st = st1;
-        }
-        for (; kt < nk; ++kt) {
-            const int st1 = st + 1 == NS ? 0 : st + 1;
-            block(f0, f1, st, 1, true, 0, 0, std::false_type{});
-            if (kt + 1 < nk) {
-                if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                block(f1, f0, st1, 0, true, 0, 0, std::false_type{});
-            } else {
-                block(f1, f0, st1, 0, false, 0, 0, std::false_type{});
-            }
-            st = st1;
-        }
+        ring_loop<GRPW, FragT>(nk, KCur{0, 0}, load, issue_begin,
+            [&](const FragT &f, FragT &fn, int st_next, int ks_next, bool load_next, const TileSrc &t, auto dma_tag) __attribute__((always_inline)) {
+                mfma_block<NTW, MT, decltype(dma_tag)::value>(acc, f,
+                    [&](auto, const uint4 w, const uint4 a, const f32x4 c) __attribute__((always_inline)) { return T::mfma(w, a, c); },
+                    [&]() __attribute__((always_inline)) { if (load_next) load(fn, st_next, ks_next); },
+                    [&](auto p_) __attribute__((always_inline)) {
+                        constexpr int pp = decltype(p_)::value;
+                        if constexpr (pp < AI) issue_a(t, pp); else issue_w(t, pp - AI);
+                    });
+            });
         // ---- next tile: its first k-tiles go into the (now idle) ring before this tile's epilogue
         const int64_t cm = m_base, cn = n_base;
         d += gridDim.x;
@@ -1519,12 +1571,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm8p(const GemmArgs g)
         }
         if (more) {
             tile_of(d, m_base, n_base);
-            set_offsets(m_base, n_base);
-            issue(0, 0);
-            if (nk > 1) issue(1, 1);
-            if (nk > 2) issue(2, 2);
+            first_tiles(m_base, n_base);
         }
-        // ---- epilogue of tile (cm, cn): bias, GEGLU / activation, scale, residual; 8-byte stores
+        // ---- epilogue of tile (cm, cn): bias, GEGLU / activation, scale, residual; 8-byte stores -- the FULL epilogue is one of four COPIES (k_gemm, k_gemm8, k_gemm8p's subset, k_gemm8q + out_fp8): a fix to one is a fix to all; DESIGN.md 3.2 has what sharing them costs
         {
             const int64_t n_lane = cn + wn * (16 * NTW) + fc * 4;
             float4 bia[NTW], csm[LNV == 2 ? NTW : 1];
@@ -1604,14 +1653,12 @@ void launch8p(const GemmArgs &g, int nwg, hipStream_t s)
 // plan are the same in bytes; the tile is ONE MFMA k-step: lane (fr, fc) feeds the 32 bytes of k-block fc of row fr (two ds_read_b128).
 // Pipeline: 3-stage ring two tiles ahead, one barrier per k-tile; tile kt+1's fragments are read and tile kt+3's DMA is issued between
 // the MFMAs of tile kt.  Output / epilogue (bf16 or f16, all fusions) = wave_epilogue.
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
 template <class T, int MODE, int NTW, int MT, bool FUSE, bool CS = false>
 __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
 {
     static_assert(MODE == 2 || MODE == 3, "fp8 path: fast conv (2) and aligned linear (3)");
-    constexpr int BM = 64 * MT, BN = 32 * NTW, STAGE = BM * 128 + BN * 128, NS = 3;
-    constexpr int AG = BM / 8, WG = BN / 8, AI = AG / 8, WI = (WG + 7) / 8;
+    using G8 = Tile8<NTW, MT>;
+    constexpr int BM = G8::BM, BN = G8::BN, STAGE = G8::STAGE, NS = G8::NS, WG = G8::WG, AI = G8::AI, WI = G8::WI;
     constexpr int BKB = 128;                       // k-tile: 128 bytes = 128 fp8 elements per row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1637,40 +1684,32 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     if constexpr (CS) {      // zeroed here: the k loop's barriers order it before the epilogue's LDS adds
         for (int i = tid; i < 4 * BN; i += 512) ctab[i] = 0.f;
     }
-    const int lr = lane >> 3, ls = lane & 7;
-    // ---- per-lane DMA plan (bytes)
-    int a_off[AI];
-    unsigned a_vm[AI];
+    // ---- per-lane DMA plan (the shared pieces at 1 byte per element): MODE 2 the fast-conv plan, MODE 3 the aligned plan; W rows always aligned
+    LaneOff<AI> pa = {};
     const unsigned char *a_ptr[AI];
+    unsigned a_vm[AI];
+    if constexpr (MODE == 2) {
+        const int lr = lane >> 3, ls = lane & 7;
 #pragma unroll
-    for (int i = 0; i < AI; ++i) {
-        const int row = (wid + 8 * i) * 8 + lr;
-        const int ck = ls ^ ((row >> 1) & 7);
-        const int64_t m = m_base + row;
-        const bool ok = m < g.M;
-        a_vm[i] = 0; a_ptr[i] = (const unsigned char *)g.A; a_off[i] = 0;
-        if (MODE == 2) {
-            const int mm = ok ? (int)m : 0, hw = g.Ho * g.Wo, b = mm / hw, rem = mm - b * hw, oy = rem / g.Wo;
-            const int y0 = oy * g.stride - g.pad, x0 = (rem - oy * g.Wo) * g.stride - g.pad;
-            a_ptr[i] = (const unsigned char *)g.A + ((int64_t)(b * g.Hi + y0) * g.Wi + x0) * g.Cin + ck * 16;
-            unsigned vm = 0;
+        for (int i = 0; i < AI; ++i) {
+            const int row = (wid + 8 * i) * 8 + lr;
+            const int ck = ls ^ ((row >> 1) & 7);
+            const int64_t m = m_base + row;
+            const bool ok = m < g.M;
+            const ConvPixel px = conv_pixel(g, ok ? (int)m : 0);
+            a_ptr[i] = (const unsigned char *)g.A + ((int64_t)(px.b * g.Hi + px.y0) * g.Wi + px.x0) * g.Cin + ck * 16;
+            unsigned vm = 0;            // (a COPY of the tap mask of k_gemm8 MODE 2: see there)
 #pragma unroll
             for (int tp = 0; tp < 9; ++tp) {
-                const int yi = y0 + tp / 3, xi = x0 + tp % 3;
+                const int yi = px.y0 + tp / 3, xi = px.x0 + tp % 3;
                 if (ok && (unsigned)yi < (unsigned)g.Hi && (unsigned)xi < (unsigned)g.Wi) vm |= 1u << tp;
             }
             a_vm[i] = vm;
-        } else {
-            a_off[i] = (int)(m < g.M ? m : g.M - 1) * (int)g.lda + ck * 16;     // rows past M re-read the last row (never stored)
         }
+    } else {
+        pa = aligned_plan<1, AI>(wid, lane, m_base, g.M, (int)g.lda);
     }
-    int w_off[WI];
-#pragma unroll
-    for (int i = 0; i < WI; ++i) {
-        const int row = (wid + 8 * i) * 8 + lr;
-        const int64_t n = n_base + row;
-        w_off[i] = (int)(n < g.N ? n : g.N - 1) * (int)g.K + (ls ^ ((row >> 1) & 7)) * 16;
-    }
+    const LaneOff<WI> pw = aligned_plan<1, WI>(wid, lane, n_base, g.N, (int)g.K);
     const unsigned char *Ab = (const unsigned char *)g.A, *Wb = (const unsigned char *)g.W, *Zp = (const unsigned char *)g.zeros;
     // (k order of the fast convs: tap-inner by default, as in k_gemm8 -- see the comment there; g.conv_korder = 0 restores tap-outer)
     const bool tap_inner = MODE == 2 && g.conv_korder != 0;
@@ -1678,29 +1717,18 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     const KOrder kord(tap_inner, BKB, g.Cin);
     KCur cur0 = {0, 0};
     if (MODE == 2) cur0 = kord.at(k0, BKB, g.Cin);
-    struct TileSrc { int kb, tap, tap_off; unsigned sbase; KCur next; };
     auto issue_begin = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> TileSrc {
-        TileSrc t;
-        t.kb = (k0 + kt) * BKB; t.tap = 0; t.tap_off = 0; t.next = c;
-        if (MODE == 2) {
-            const int ci = kord.ci(c);
-            t.tap = kord.tap(c);
-            t.kb = __builtin_amdgcn_readfirstlane(t.tap * g.Cin + ci);
-            const int dy = t.tap / 3, dx = t.tap - dy * 3;
-            t.tap_off = (dy * g.Wi + dx) * g.Cin + ci;
-            t.next = kord.next(c);
-        }
-        t.sbase = lds0 + stage * STAGE;
-        return t;
+        if constexpr (MODE == 2) return tile_conv<false>(kord, c, g.Cin, g.Wi, lds0 + stage * STAGE);
+        else return tile_linear((k0 + kt) * BKB, lds0 + stage * STAGE);
     };
     auto issue_a = [&](const TileSrc &t, int i) __attribute__((always_inline)) {
         const unsigned dst = t.sbase + (unsigned)((wid + 8 * i) * 1024);
-        if (MODE == 3) { glds16_s(Ab + (size_t)t.kb, (unsigned)a_off[i], dst); return; }
-        const bool okm = (a_vm[i] >> t.tap) & 1u;
+        if (MODE == 3) { dma_aligned<1>(Ab, t.kb, pa.v[i], dst); return; }
+        const bool okm = (a_vm[i] >> t.tap) & 1u;      // (a COPY of k_gemm8 MODE 2's two lines: see there)
         glds16(okm ? a_ptr[i] + (int64_t)t.tap_off : Zp, dst);
     };
     auto issue_w = [&](const TileSrc &t, int i, bool has) __attribute__((always_inline)) {
-        if (has) glds16_s(Wb + (size_t)t.kb, (unsigned)w_off[i], t.sbase + (unsigned)(BM * 128 + (wid + 8 * i) * 1024));
+        if (has) dma_aligned<1>(Wb, t.kb, pw.v[i], t.sbase + (unsigned)(BM * 128 + (wid + 8 * i) * 1024));
     };
     auto issue = [&](int kt, int stage, const KCur c) __attribute__((always_inline)) -> KCur {
         const TileSrc t = issue_begin(kt, stage, c);
@@ -1717,28 +1745,11 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
 #pragma unroll
         for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, fc = lane >> 4;
-    const int swz = (fr >> 1) & 7;
-    // Which two 16-byte chunks of the row's 128-byte k-tile lane group fc feeds is FREE (the k-tile is ONE MFMA k-step: the dot product runs
-    // over every (lane group, byte) position, and A and W use the same association).  Chunks (fc, fc + 4) -- the bf16 kernel's pair -- make
-    // the two ds_read_b128 conflict-free under this swizzle; the round-4 choice (2 fc, 2 fc + 1) put lane groups fc = 0 and 1 of a
-    // ds_read_b128 lane group on the same 8 bank quartets: SQ_LDS_BANK_CONFLICT = 50 % of SQ_LDS_IDX_ACTIVE (profiles/r05_pmc_gemm8q.txt).
-    const int fx0 = ((fc ^ swz) << 4), fx1 = (((fc + 4) ^ swz) << 4);
-    const int aw0 = BM * 128 + (wn * (16 * NTW) + fr) * 128, aa0 = (wm * (16 * MT) + fr) * 128;
-    // Fragment registers: 8-register MFMA operands assembled ONCE at load time from two ds_read_b128, double-buffered per k-tile (the two
-    // buffers alternate by NAME in the 2x unrolled loop: an in-place reload would cost a register copy per fragment at the back edge).
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
-    struct Frag { i32x8 w[NTW], a[MT]; };
-    auto ld32 = [&](const unsigned char *p0, const unsigned char *p1) __attribute__((always_inline)) -> i32x8 {
-        const i32x4 lo = *reinterpret_cast<const i32x4 *>(p0), hi = *reinterpret_cast<const i32x4 *>(p1);
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto load_frag = [&](Frag &f, int stage) __attribute__((always_inline)) {
-        const unsigned char *sb = smem + stage * STAGE;
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) f.w[t] = ld32(sb + aw0 + fx0 + t * 2048, sb + aw0 + fx1 + t * 2048);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) f.a[t] = ld32(sb + aa0 + fx0 + t * 2048, sb + aa0 + fx1 + t * 2048);
-    };
+    const FragAddr fa = FRAG_ADDR(NTW, MT, fr, fc, wm, wn);
+    // Fragment registers double-buffered per k-tile (the two buffers alternate by NAME in the 2x unrolled loop: an in-place reload would
+    // cost a register copy per fragment at the back edge).
+    using FragT = Frag<i32x8, NTW, MT>;
+    auto load = [&](FragT &f, int stage) __attribute__((always_inline)) { load_frag(f, smem + stage * STAGE, fa, 0); };
     // block scales: the weight row's exponent (constant over k) and the tensor-wide activation exponent, in byte 0 of the scale VGPRs.
     // These are the only compiler-visible global loads of the kernel: they are waited for HERE, before the first LDS-DMA is issued --
     // a compiler-placed vmcnt for them inside the k loop would count (and drain) the inline-asm DMA loads every iteration.
@@ -1752,61 +1763,41 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
 #pragma unroll
     for (int t = 0; t < NTW; ++t) asm volatile("" : "+v"(sw[t]));
     const int sa = g.a_scale;
-    constexpr int NMM = NTW * MT, NPC = AI + WI;
-    auto block = [&](const Frag &f, Frag &fn, int st_next, bool load_next, const TileSrc &t, auto dma_tag, auto w3_tag) __attribute__((always_inline)) {
-        constexpr bool DMA = decltype(dma_tag)::value, W3 = decltype(w3_tag)::value;
-        static_for<0, NMM>([&](auto m_) __attribute__((always_inline)) {
-            constexpr int m = decltype(m_)::value, nt = m / MT, mt = m % MT;
-            acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f.w[nt], f.a[mt], acc[nt][mt], 0, 0, 0, sw[nt], 0, sa);
-            if constexpr (m == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (load_next) load_frag(fn, st_next);
-                __builtin_amdgcn_sched_barrier(0);
-            } else if constexpr (DMA && m >= 2) {
-                static_for<0, NPC>([&](auto p_) __attribute__((always_inline)) {
-                    constexpr int pp = decltype(p_)::value;
-                    if constexpr (m == 2 + (pp * (NMM - 3)) / NPC) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (pp < AI) issue_a(t, pp); else issue_w(t, pp - AI, (pp - AI) < WI - 1 || W3 || WG % 8 == 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                });
-            }
-        });
-    };
     const bool w3 = (wid + 8 * (WI - 1)) < WG;
-    Frag f0, f1;
-    const TileSrc tnone = {0, 0, 0, 0u, {0, 0}};
+    FragT f0, f1;
+    const TileSrc tnone = {0, 0, 0, 0, 0, 0u, {0, 0}};
+    // The loop has another shape than ring_loop (ONE MFMA block per k-tile, tile kt+1's fragments read and tile kt+3's DMA issued between
+    // the MFMAs of tile kt); the priming, the counted waits and the tail's wait ladder are the shared ones.
     auto run = [&](auto w3_tag) __attribute__((always_inline)) {
         constexpr bool W3 = decltype(w3_tag)::value;
-        constexpr int GRPW = AI + ((W3 || WG % 8 == 0) ? WI : WI - 1);
-        auto wait_tiles = [&](auto n_) __attribute__((always_inline)) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_)::value * GRPW) : "memory");
+        constexpr int GRPW = G8::grpw(W3);
+        auto block = [&](const FragT &f, FragT &fn, int st_next, bool load_next, const TileSrc &t, auto dma_tag) __attribute__((always_inline)) {
+            mfma_block<NTW, MT, decltype(dma_tag)::value>(acc, f,
+                [&](auto nt_, const i32x8 w, const i32x8 a, const f32x4 c) __attribute__((always_inline)) {
+                    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, a, c, 0, 0, 0, sw[decltype(nt_)::value], 0, sa);
+                },
+                [&]() __attribute__((always_inline)) { if (load_next) load(fn, st_next); },
+                [&](auto p_) __attribute__((always_inline)) {
+                    constexpr int pp = decltype(p_)::value;
+                    if constexpr (pp < AI) issue_a(t, pp); else issue_w(t, pp - AI, (pp - AI) < WI - 1 || W3 || WG % 8 == 0);
+                });
         };
-        KCur cur = issue(0, 0, cur0);
-        if (nk > 1) cur = issue(1, 1, cur);
-        if (nk > 2) cur = issue(2, 2, cur);
-        if (nk > 2) wait_tiles(std::integral_constant<int, 2>{}); else if (nk > 1) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
+        KCur cur = ring_prime(nk, cur0, issue);
+        ring_wait_first<GRPW>(nk);
         __builtin_amdgcn_s_barrier();
-        load_frag(f0, 0);
+        load(f0, 0);
         int st = 0, kt = 0;                   // st = stage of tile kt (whose fragments are in f0 at the top of an even step)
-        auto step = [&](Frag &fc_, Frag &fn_) __attribute__((always_inline)) {
+        auto step = [&](FragT &fc_, FragT &fn_) __attribute__((always_inline)) {
             const int st1 = st + 1 == NS ? 0 : st + 1;
             if (kt + 3 < nk) {                // steady state: tiles kt+1, kt+2 in flight, tile kt+3 is issued into stage st
-                wait_tiles(std::integral_constant<int, 1>{});
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();                    // tile kt+1 landed for everyone; everyone holds tile kt in registers
+                ring_turn<GRPW>(true);        // tile kt+1 landed for everyone; everyone holds tile kt in registers
                 const TileSrc t = issue_begin(kt + 3, st, cur);
                 cur = t.next;
-                block(fc_, fn_, st1, true, t, std::true_type{}, w3_tag);
+                block(fc_, fn_, st1, true, t, std::true_type{});
             } else {                          // the last three k-tiles: ONE copy of the MFMA block (the accumulators stay in place)
                 const bool more = kt + 1 < nk;
-                if (more) {
-                    if (kt + 2 < nk) wait_tiles(std::integral_constant<int, 1>{}); else wait_tiles(std::integral_constant<int, 0>{});
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                }
-                block(fc_, fn_, st1, more, tnone, std::false_type{}, w3_tag);
+                if (more) ring_turn<GRPW>(kt + 2 < nk);
+                block(fc_, fn_, st1, more, tnone, std::false_type{});
             }
             st = st1; ++kt;
         };
@@ -1820,9 +1811,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
         wave_epilogue<T, NTW, MT, 512>(g, acc, m_base, m_base + wm * (16 * MT), n_base + wn * (16 * NTW), lane, smem, g.row_stats ? srow : nullptr, slice);
         return;
     }
-    // ---- epilogue (same math as k_gemm; MT m-tiles per wave)
+    // ---- epilogue (same math as k_gemm; MT m-tiles per wave) -- the FULL epilogue is one of four COPIES (k_gemm, k_gemm8, k_gemm8p's subset, k_gemm8q + out_fp8): a fix to one is a fix to all; DESIGN.md 3.2 has what sharing them costs
     const int64_t n_lane = n_base + wn * (16 * NTW) + fc * 4;
-    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice`
+    if (g.splits > 1) {   // partial sums of this k-slice: plain 16-byte stores into slab `slice` (one of four COPIES: k_gemm, k_gemm8, k_gemm8q, wave_epilogue)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int64_t m = m_base + wm * (16 * MT) + mt * 16 + fr;
@@ -1839,9 +1830,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
     }
     if constexpr (CS) {
         // ---- lean epilogue + channel partials: a COPY of the CS epilogue of k_gemm8, same arithmetic and layout -- a fix to one is a fix to both.
-        // (Still a copy: as __forceinline__ functions shared by the kernels, this block, the k-slice store and the full epilogue compile to other
-        // code than the same text in the kernel body -- the optimiser simplifies a callee before it inlines it, where GemmArgs is a reference the
-        // stores may alias: +3 .. +420 instructions, other SGPR / scratch figures; with GemmArgs passed by value still +3 .. +24.)  EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
+        // (As one function shared with k_gemm8 it costs VGPRs: 60 instantiations +1 .. +4 through a narrow by-value struct of the fields it reads,
+        // k_gemm8<F16, 1, 5, 3, CS> 181 -> 185; DESIGN.md 3.2 has the figures of every epilogue piece.)
+        // EVERY operand load is issued first, branch-free (rows / columns past the edge re-read a valid element,
         // absent operands read the zero page), then the tile is computed and stored.  The generic epilogue loads bias / row-vector /
         // residual under per-lane branches inside the m loop: at every control-flow join hipcc falls back to s_waitcnt vmcnt(0), and on
         // gfx9 that counter also holds the STORES in flight -- MT x NTW serialised store round trips per wave (seen in the ISA).
@@ -2025,6 +2016,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm8q(const GemmArgs g)
         }
     }
 }
+
+#undef FRAG_ADDR
 
 // The split-K reduce kernels add the slabs in slab order (the result does not depend on the slice -> workgroup assignment), ZC slabs per
 // round trip: the loads of a chunk are all issued before the first add.  (Round 1..4: one slab per iteration = `splits` dependent round trips
@@ -2251,15 +2244,6 @@ void launch8(const GemmArgs &g, dim3 grid, hipStream_t s)
 
 // ---- lean LayerNorm fold (round 5; dn_gemm_ln.hip).  Producer (lnv 1): lean epilogue + row partials.  Consumer (lnv 2): lean or plain epilogue
 // with the rstd / mean correction.  K % 64 == 0 linears (MODE 3) only; NTW 4 | 5; MT 1 (two workgroups per CU) .. 4.
-inline bool ln_lean_producer_of(const GemmArgs &g, int mode, int splits)
-{
-    return g.out_row_stats && !g.row_stats && !g.out_group_stats && !g.chan_parts && splits == 1 && mode == 0 && g.K % 64 == 0 && !g.geglu &&
-           g.act == 0 && !g.out_f32 && !g.out_t && g.out && g.N >= 4 && (!g.rowvec || g.rows_per_batch >= 256);
-}
-inline bool ln_lean_consumer_of(const GemmArgs &g, int mode, int splits)
-{
-    return g.row_stats && !g.out_row_stats && !g.out_group_stats && !g.chan_parts && splits == 1 && mode == 0 && g.K % 64 == 0 && g.N >= 4;
-}
 template <class T, int NTW, int MT>
 void dispatch8ln_m(const GemmArgs &g, int lnv, bool lean, dim3 grid, hipStream_t s)
 {
@@ -2347,7 +2331,7 @@ void dispatch4(const GemmArgs &g, int mode, int ntw, dim3 grid, hipStream_t s)
 
 }  // namespace
 
-// entry points of the three kernel translation units (dtype: DT_BF16 / DT_F16; mode as resolved by gc_dn_gemm: 0 linear, 1 generic conv,
+// entry points of the kernel translation units dn_gemm_{plain,fuse,cs,lean,ln,fp8}.hip (dtype: DT_BF16 / DT_F16; mode as resolved by gc_dn_gemm: 0 linear, 1 generic conv,
 // 2 fast conv; mt8 = 0: 4-wave kernel)
 using dng::GemmArgs;
 void dn_gemm_launch_plain(const GemmArgs &g, int dtype, int mode, int ntw, int mt8, dim3 grid, hipStream_t s);

@@ -1,4 +1,5 @@
-// dn_gemm_plain.hip -- instantiates the GEMM / implicit-conv kernels with the lean epilogue (FUSE = false) and the split-K reduce kernels.
+// dn_gemm_plain.hip -- instantiates the GEMM / implicit-conv kernels with the plain (full, FUSE = false) epilogue and the split-K reduce kernels
+// (the LEAN instantiations are dn_gemm_lean.hip's).
 #include "dn_gemm_kernels.h"
 
 void dn_gemm_launch_plain(const GemmArgs &g, int dtype, int mode, int ntw, int mt8, dim3 grid, hipStream_t s)

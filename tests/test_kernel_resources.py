@@ -107,6 +107,39 @@ def test_allow_list_is_current(kernels):
         assert any(v != (0, 0) for v in hit.values()), p
 
 
+def kernel_vgprs(lib, pattern):
+    """{demangled kernel name: .vgpr_count} of the kernels whose demangled name matches `pattern` (metadata keys only, as above)"""
+    spec = importlib.util.spec_from_file_location("packed_fp32_audit", os.path.join(ROOT, "scripts", "packed_fp32_audit.py"))
+    audit = importlib.util.module_from_spec(spec); spec.loader.exec_module(audit)
+    out = {}
+    for co in audit.code_objects(lib):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co); f.flush()
+            notes = subprocess.run([f"{BIN}/llvm-readelf", "--notes", f.name], capture_output=True, text=True, check=True).stdout
+        lines = notes.splitlines()
+        for i, line in enumerate(lines):
+            m = re.match(r"^(\s+)\.vgpr_count:\s+(\d+)\s*$", line)
+            if m:
+                ind = re.escape(m.group(1))
+                name = next(n.group(1) for n in (re.match(rf"^{ind}\.name:\s+(\S+)\s*$", l) for l in reversed(lines[:i])) if n)
+                out[name.strip("'\"")] = int(m.group(2))
+    names = sorted(out)
+    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
+    return {d: out[n] for d, n in zip(dem, names) if re.search(pattern, d)}
+
+
+def test_persistent_gemm_keeps_one_accumulator_set(built):
+    """k_gemm8p runs k_gemm8's k loop (ring_loop in csrc/dn_gemm_kernels.h): ONE copy of the tail's second MFMA block, so the allocator keeps one
+    set of the 64 accumulators -- 169 VGPRs (LNV 0) / 179 (LNV 2) as built today; with a copy in either arm of the tail's branch it kept two
+    (232 / 242).  ring_loop's form depends on how the optimiser treats it before it is inlined (its trip count arrives by const reference for
+    that reason): a compiler that rewrites it shows here, without a second build to compare with.  More fails."""
+    v = kernel_vgprs(built, r"\bk_gemm8p<")
+    assert len(v) == 4, sorted(v)
+    for k, n in v.items():
+        lim = 179 if re.search(r"k_gemm8p<dn::(BF16|F16), 4, 4, 2>", k) else 169
+        assert n <= lim, (k, n, lim)
+
+
 def test_bench_attention_kernel_uses_no_private_memory(kernels):
     hit = {k: v for k, v in kernels.items() if re.search(BENCH_ATTN5, k)}
     assert len(hit) == 2, sorted(hit)
