@@ -23,6 +23,7 @@ import torch
 
 from _margins import within
 from _redzone import on_device
+from _train_step_ref import depth_l1_ref
 from gaussctrl_amd import synthetic as syn
 from test_raster_gpu import _grad_close, _img_close
 
@@ -299,11 +300,7 @@ def test_depth_l1_loss():
     loss = depth_l1_loss_views(p, _t(target))
     w = _t(np.array([0.5, -2.0, 3.0], np.float32))
     (loss * w).sum().backward()
-    pd, td = pred.astype(np.float64), target.astype(np.float64)
-    valid = (pd != 1000.0) & (td != 1000.0) & np.isfinite(pd) & np.isfinite(td)
-    diff = np.where(valid, pd - np.where(valid, td, 0.0), 0.0)
-    cnt = valid.reshape(B, -1).sum(1)
-    want = np.abs(diff).reshape(B, -1).sum(1) / np.maximum(cnt, 1)
+    valid, diff, cnt, want = depth_l1_ref(pred, target)
     got = loss.detach().cpu().numpy().astype(np.float64)
     assert cnt[2] == 0 and got[2] == 0.0
     within("depth L1 loss, relative", np.abs(got - want).max() / np.abs(want).max(), 1e-6)

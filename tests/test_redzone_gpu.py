@@ -33,7 +33,7 @@ def _both(module_, test_, key="dt", **kw):
 
 
 R, V, ND, DP, AA = "test_raster_gpu", "test_raster_views_gpu", "test_raster_nd_gpu", "test_raster_depth_gpu", "test_raster_antialias_gpu"
-RF, MC, DK, TT = "test_refine_gpu", "test_mcmc_gpu", "test_denoise_kernels_gpu", "test_ttail_gpu"
+RF, MC, DK, TT, TS = "test_refine_gpu", "test_mcmc_gpu", "test_denoise_kernels_gpu", "test_ttail_gpu", "test_train_step_gpu"
 
 CASES = [
     # raster operator surface
@@ -81,6 +81,10 @@ CASES = [
     _c(V, "test_l1_ssim_loss_views_matches_per_image"),
     _c(DP, "test_depth_l1_loss"),
     _c("test_dist_gpu", "test_sharded_adam_slice_update_is_the_fused_adam_kernel"),
+    # training step against float64: below the window, one SSIM pixel, tiles + 1 at C = 4; the batched loss; Adam's chunk tails
+    *[_c(TS, "test_l1_ssim_vs_float64", H=h, W=w, C=c) for h, w, c in ((1, 1, 1), (11, 11, 3), (17, 33, 4))],
+    _c(TS, "test_l1_ssim_views_vs_float64_per_image"),
+    *[_c(TS, "test_adam_vs_float64", n=n) for n in (5, 1025)],
     # densification
     *[_c(RF, "test_accumulate", N=n, C=c) for n in (1, 255, 257) for c in (1, 3)],
     _c(RF, "test_plan_apply_mixed", N=257, ns=2),
