@@ -120,6 +120,8 @@ CASES = [
     *_both(TT, "test_tail_matches_torch_and_the_per_op_path", key="dtype", B=4, HW=128, f=2, Lt=50, gate_shift=0.0),
     *_both(TT, "test_head_matches_torch_and_the_per_op_path", key="dtype", B=2, HW=256),
     *_both("test_conv_cursor_gpu", "test_head_smallest_launch"),
+    # the fused head / tail against the float64 mirror: text attention one key into the second 32-key block, the CFG-shared prefix, the head
+    *[c for n in ("T3-ordinary-Lt33", "chain-halves2-B3-Lt33", "H4-HW128") for c in _both("test_ttail_pin_gpu", "test_case", key="dtype", name=n)],
     _c("test_plugin_gpu", "test_mask_composite_with_real_mask", H=96, W=130, C=3),
 ]
 
@@ -177,13 +179,19 @@ NOT_REACHED = ["gc_abi_version", "gc_last_error_string",                       #
                "gc_raster_pad_intersects", "gc_raster_scan_tiles_views"]
 
 
+# entry points that only the guards of another test module reach (its own arena sizes): when that module is not part of the run (this file
+# run alone or next to a few others) they count as reached; in a run of the whole suite the list above holds as it stands
+ELSEWHERE = {"test_edit_trace_gpu": ["gc_adam_step_rows", "gc_trace_mask_views", "gc_trace_select"]}
+
+
 def test_entry_points_no_guarded_case_reaches():
     """which entry points the guarded cases of this process looked up, against the list above (only when every case ran and passed here)"""
     import _redzone
     from gaussctrl_amd import _lib
     if len(_ran) < len(CASES):
         return
-    missing = sorted(set(_lib.SYMBOLS) - _redzone.reached)
+    elsewhere = {s for module, names in ELSEWHERE.items() if module not in sys.modules for s in names}
+    missing = sorted(set(_lib.SYMBOLS) - _redzone.reached - elsewhere)
     print("not reached:", missing)
     assert missing == sorted(NOT_REACHED), (sorted(set(missing) - set(NOT_REACHED)), sorted(set(NOT_REACHED) - set(missing)))
 

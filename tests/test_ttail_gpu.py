@@ -110,6 +110,18 @@ def test_unet_with_fused_tail_matches_per_op_unet():
     assert 0 < d < 3e-2, d                          # different kernels (not bit-equal), same function
 
 
+def _torch_head(sd, x):
+    """fp32, unfused: GroupNorm, proj_in, LayerNorm1, Q (carries the folded softmax scale: D^-1/2 log2 e) | K | V^T"""
+    F = torch.nn.functional
+    W = lambda n: sd[n].float().to(x.device)
+    xt = F.group_norm(x.float().transpose(1, 2), 32, W(P + ".norm.weight"), W(P + ".norm.bias"), 1e-6).transpose(1, 2)
+    ht = F.linear(xt, W(P + ".proj_in.weight").view(C, C), W(P + ".proj_in.bias"))
+    nt = F.layer_norm(ht, (C,), W(T + ".norm1.weight"), W(T + ".norm1.bias"), 1e-5)
+    qt = F.linear(nt, W(T + ".attn1.to_q.weight")) * ((C // H) ** -0.5 * 1.4426950408889634)
+    kt = F.linear(nt, W(T + ".attn1.to_k.weight")); vtt = F.linear(nt, W(T + ".attn1.to_v.weight")).transpose(1, 2)
+    return ht, qt, kt, vtt
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("B,HW", [(2, 256), (3, 1024)])
 def test_head_matches_torch_and_the_per_op_path(dtype, B, HW):
@@ -131,13 +143,7 @@ def test_head_matches_torch_and_the_per_op_path(dtype, B, HW):
     n1 = ops.layernorm(h_ref, w[T + ".norm1.weight"], w[T + ".norm1.bias"])
     vt_ref = torch.empty(B, C, HW, dtype=dtype, device=dev)
     qk_ref = ops.linear(n1, w[T + ".attn1.to_qkv.weight"], None, rows_per_batch=HW, out_t=vt_ref, ldt=HW, t_batch_stride=C * HW, t_col0=2 * C, out_cols=2 * C)
-    # fp32 torch (Q carries the folded softmax scale: D^-1/2 log2 e)
-    W = lambda n: sd[n].float().to(dev)
-    xt = F.group_norm(x.float().transpose(1, 2), 32, W(P + ".norm.weight"), W(P + ".norm.bias"), 1e-6).transpose(1, 2)
-    ht = F.linear(xt, W(P + ".proj_in.weight").view(C, C), W(P + ".proj_in.bias"))
-    nt = F.layer_norm(ht, (C,), W(T + ".norm1.weight"), W(T + ".norm1.bias"), 1e-5)
-    qt = F.linear(nt, W(T + ".attn1.to_q.weight")) * ((C // H) ** -0.5 * 1.4426950408889634)
-    kt = F.linear(nt, W(T + ".attn1.to_k.weight")); vtt = F.linear(nt, W(T + ".attn1.to_v.weight")).transpose(1, 2)
+    ht, qt, kt, vtt = _torch_head(sd, x)
     bar = 2e-2 if dtype == torch.bfloat16 else 3e-3
     for name, got, ref, tt in (("h", h, h_ref, ht), ("q", qk[..., :C], qk_ref[..., :C], qt), ("k", qk[..., C:], qk_ref[..., C:], kt), ("vt", vt, vt_ref, vtt)):
         sc = tt.abs().max()
