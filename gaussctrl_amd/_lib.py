@@ -89,6 +89,16 @@ EXT_SYMBOLS = list(ABI["gaussctrl_bilagrid.h"])
 POSE_SYMBOLS = list(ABI["gaussctrl_pose.h"])
 EXT_SETS = {"gaussctrl_bilagrid.h": EXT_SYMBOLS, "gaussctrl_pose.h": POSE_SYMBOLS}
 
+# Extension headers in subdirectories of include/ (same alphabet, prefix gcx_): bound and called like every entry of ABI, kept in a table of
+# their own so that the views above stay what they were.  tests/test_distort_cpu.py holds it to include/ext/*.h.
+EXT_ABI = {
+    "ext/gaussctrl_distort.h": {
+        "gcx_distort_fwd_views": "e:iqqiiiiippppppiffpps", "gcx_distort_bwd_views": "e:iqqiiiiippppppiffpppppppps",
+    },
+}
+EXT_SIGNATURES = {name: sig for names in EXT_ABI.values() for name, sig in names.items()}
+_BOUND = {**SIGNATURES, **EXT_SIGNATURES}
+
 ARG_TYPES = {"i": C.c_int, "q": C.c_int64, "f": C.c_float, "z": C.c_size_t, "p": C.c_void_p, "s": C.c_void_p}
 RETURN_TYPES = {"e": C.c_int, "i": C.c_int, "z": C.c_size_t, "c": C.c_char_p, "v": None}
 
@@ -100,7 +110,7 @@ def _plan(sig):
     return kind, len(letters) - stream, stream, tuple(i for i, c in enumerate(letters) if c == "p")
 
 
-_PLANS = {name: _plan(sig) for name, sig in SIGNATURES.items()}
+_PLANS = {name: _plan(sig) for name, sig in _BOUND.items()}
 _HAS_DATA_PTR = {}          # type of a pointer argument -> it is a tensor (has data_ptr), not None / an int / a host ctypes object
 
 _lib = None
@@ -118,10 +128,10 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
         l = C.CDLL(LIB_PATH)
-        for s in SIGNATURES:
+        for s in _BOUND:
             if not hasattr(l, s):
                 raise GaussCtrlHipError(f"libgaussctrl_hip.so does not export {s}")
-        for s, sig in SIGNATURES.items():
+        for s, sig in _BOUND.items():
             kind, letters = sig.split(":")
             fn = getattr(l, s)
             fn.restype = RETURN_TYPES[kind]

@@ -117,6 +117,17 @@ class GaussCtrlModelConfig(_ModelConfigBase):
                                                   # a number: constant Adam learning rate of the group (eps 1e-15), as bilagrid_lr
     camera_opt_trans_l2_penalty: float = 1e-2     # loss += this * mean |tau|      [nerfstudio's default, as recalled]
     camera_opt_rot_l2_penalty: float = 1e-3       # loss += this * mean |omega|    [nerfstudio's default, as recalled]
+    distortion_loss_mult: float = 0.0             # 0: off, the reference's behaviour.  > 0: in training mode get_outputs also returns
+                                                  # "distortion" [H,W,1], per pixel the weighted spread in depth of the splats composited there
+                                                  # (the Mip-NeRF 360 / 2DGS regulariser against floaters; ops.RenderAux.distort on the kernels of
+                                                  # csrc/raster_distort.hip), get_loss_dict adds "distortion_loss" = this * its mean and
+                                                  # get_metrics_dict "distortion".  Evaluation, get_outputs_for_camera[s] and render_reverse never
+                                                  # compute it.  The formulas are recalled from the papers and gsplat 1.x, not checked against their
+                                                  # source (include/ext/gaussctrl_distort.h is the contract)
+    distortion_depth_map: str = "linear"          # "linear": t = z, the camera-space depth; "ndc": t = far (z - near) / ((far - near) z), which
+                                                  # weighs the spread near the camera more
+    distortion_near: float = 0.2                  # the two planes of "ndc" (0 < near < far); "linear" does not read them
+    distortion_far: float = 100.0
 
     def __post_init__(self):
         parent = getattr(super(), "__post_init__", None)
@@ -126,6 +137,22 @@ class GaussCtrlModelConfig(_ModelConfigBase):
         _mcmc(self.densify_strategy)
         _bilagrid(self)
         _camera_opt(self)
+        _distortion(self)
+
+
+def _distortion(cfg) -> bool:
+    """distortion_loss_mult > 0; a depth map that is not one of the two names is a ValueError (as are, under "ndc", planes without
+    0 < near < far, and a negative multiplier)"""
+    from .gsplat_ops import DISTORT_DEPTH_MAPS
+    name = getattr(cfg, "distortion_depth_map", "linear")
+    if name not in DISTORT_DEPTH_MAPS:
+        raise ValueError(f"distortion_depth_map must be one of {DISTORT_DEPTH_MAPS}, got {name!r}")
+    mult = float(getattr(cfg, "distortion_loss_mult", 0.0))
+    if not mult >= 0:
+        raise ValueError(f"distortion_loss_mult must be >= 0, got {mult!r}")
+    if name == "ndc" and not 0 < float(cfg.distortion_near) < float(cfg.distortion_far) < float("inf"):
+        raise ValueError(f"distortion_depth_map 'ndc' needs 0 < distortion_near < distortion_far, got {cfg.distortion_near!r}, {cfg.distortion_far!r}")
+    return mult > 0
 
 
 RASTERIZE_MODES = ("classic", "antialiased")
@@ -297,6 +324,10 @@ class GaussCtrlModel(_ModelBase):
         aux.depth_grad = train_depth
         aux.absgrad = bool(self.training and getattr(self.config, "use_absgrad", False))
         want_depth = train_depth or not self.training
+        if self.training and getattr(self.config, "distortion_loss_mult", 0.0) > 0:      # the render also leaves aux.distort_map (the other
+            # fields were validated in __post_init__; the operator layer and the entry points check the map name and the planes again)
+            aux.distort, aux.distort_depth_map = True, self.config.distortion_depth_map
+            aux.distort_near, aux.distort_far = float(self.config.distortion_near), float(self.config.distortion_far)
         if pose_row is not None and torch.is_grad_enabled() and pose_row.requires_grad:
             aux.pose_grad = True             # the projection backward also leaves aux.viewmat_grad, which the link chains to the row
             p[0] = camera_opt.link(p[0], pose_row, aux, c2w_plain)
@@ -305,7 +336,10 @@ class GaussCtrlModel(_ModelBase):
         if aux.M == 0:                                                          # :155-156
             return {"rgb": background.repeat(H, W, 1)}
         depth_im = depth[..., None] if want_depth else None
-        return {"rgb": rgb, "depth": depth_im, "accumulation": alpha[..., None]}
+        outputs = {"rgb": rgb, "depth": depth_im, "accumulation": alpha[..., None]}
+        if aux.distort_map is not None:
+            outputs["distortion"] = aux.distort_map[..., None]
+        return outputs
 
     forward = get_outputs
 
@@ -376,6 +410,8 @@ class GaussCtrlModel(_ModelBase):
         if pose is not None:             # camera_optimizer_mode "SO3xR3": how far the poses have moved, mean over the views
             metrics["camera_opt_translation"] = pose.detach()[:, :3].norm(dim=-1).mean()
             metrics["camera_opt_rotation"] = pose.detach()[:, 3:].norm(dim=-1).mean()
+        if outputs.get("distortion") is not None:        # distortion_loss_mult > 0, training mode: the mean of the map
+            metrics["distortion"] = outputs["distortion"].detach().mean()
         return metrics
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, torch.Tensor]:
@@ -383,7 +419,8 @@ class GaussCtrlModel(_ModelBase):
         config.densify_strategy = "mcmc" adds the strategy's two regularisers (plain torch: two reductions over N, not the hot path).
         The stand-alone model with config.use_bilateral_grid, in training mode, takes the main loss on the render sliced through the grid
         of batch["image_idx"] and adds "tv_loss"; outputs["rgb"] itself, the metrics and everything at evaluation stay un-gridded.
-        With config.camera_optimizer_mode = "SO3xR3" it adds, in training mode, "camera_opt_regularizer" (camera_opt.regularizer)."""
+        With config.camera_optimizer_mode = "SO3xR3" it adds, in training mode, "camera_opt_regularizer" (camera_opt.regularizer).
+        With config.distortion_loss_mult > 0 it adds, in training mode, "distortion_loss" = mult * mean of outputs["distortion"]."""
         from .train_ops import l1_ssim_loss
         gt = batch["image"].to(self.device)
         grid = getattr(self, "bilateral_grid", None) if (not HAVE_NERFSTUDIO and self.training) else None
@@ -402,4 +439,6 @@ class GaussCtrlModel(_ModelBase):
         if pose is not None:             # camera_optimizer_mode "SO3xR3": keep the adjustments small (plain torch over [V, 6])
             from .camera_opt import regularizer
             loss["camera_opt_regularizer"] = regularizer(pose, self.config.camera_opt_trans_l2_penalty, self.config.camera_opt_rot_l2_penalty)
+        if outputs.get("distortion") is not None:        # distortion_loss_mult > 0, training mode (get_outputs leaves no key otherwise)
+            loss["distortion_loss"] = self.config.distortion_loss_mult * outputs["distortion"].mean()
         return loss

@@ -335,6 +335,29 @@ class RenderAux:
     # either.  With the switch off nothing new runs; on, every output and leaf gradient is computed by the same launches as without it.
     pose_grad = False
     viewmat_grad = None
+    # distortion loss (include/ext/gaussctrl_distort.h; the formulas are recalled from Mip-NeRF 360 / 2DGS and the header is the contract):
+    # True (with parameters that require grad) makes the render also leave `distort_map`, per pixel the weighted spread in mapped depth of
+    # the splats composited there: [H, W] from render_view, [C, H, W] from render_views, a differentiable output of the same autograd node.
+    # distort_depth_map "linear" (t = z) or "ndc" (t = far (z - near) / ((far - near) z) with distort_near / distort_far).  When the map
+    # received a cotangent, gcx_distort_bwd_views runs after the compositing backward and adds into its v_xy / v_conic / v_opacity and the
+    # depth slice of the same zeroed buffer (there whether or not depth_grad is set); the projection backward then takes its depth form.
+    # So grad_into, antialiased and pose_grad work as they are, aux.xys_grad includes the distortion's pull, and xys_absgrad (per-pixel
+    # magnitudes of the image losses) does not.  False: nothing new is allocated or launched, every launch gets the arguments it always got.
+    distort = False
+    distort_depth_map = "linear"
+    distort_near = 0.2
+    distort_far = 100.0
+    distort_map = None
+
+
+DISTORT_DEPTH_MAPS = ("linear", "ndc")
+
+
+def distort_depth_mode(name) -> int:
+    """RenderAux.distort_depth_map -> depth_map of gcx_distort_*_views; anything but the two names is a ValueError"""
+    if name not in DISTORT_DEPTH_MAPS:
+        raise ValueError(f"distort_depth_map must be one of {DISTORT_DEPTH_MAPS}, got {name!r}")
+    return DISTORT_DEPTH_MAPS.index(name)
 
 
 def _finalize(ctx, npix, img, dep, fT):
@@ -382,7 +405,23 @@ def _leaf_params(means, log_scales, quats, opacities, features_dc, features_rest
 _RenderMeta = collections.namedtuple("_RenderMeta", "C N M_cap shared_op shared_bg H W tb sh_degree n_use cams cams_host single")
 
 
-def _end_forward(ctx, aux, want_depth, meta, comp, saved, depths, dep, nth, M, boxes, keys_s):
+def _distort_fwd(ctx, aux, C, N, M_cap, shared_op, H, W, tb, ids_s, bins, xys, conics, opac, depths, single):
+    """RenderAux.distort: the distortion map of the lists the compositing forward just walked.  Returns (map, wt, (depth_map, near, far)),
+    or (None, None, None) with the switch off or nothing to differentiate.  Empty lists (a view that sees no Gaussian: ids_sorted has no
+    element and no address) composite nothing: the map is zero without a launch, as the entry point leaves it for an empty scene"""
+    if aux is None or not aux.distort or not any(ctx.needs_input_grad[:6]):
+        return None, None, None
+    how = (distort_depth_mode(aux.distort_depth_map), float(aux.distort_near), float(aux.distort_far))
+    shape = (H, W) if single else (C, H, W)
+    if ids_s.numel() == 0:
+        return torch.zeros(shape, device=xys.device), torch.zeros(shape, device=xys.device), how
+    dmap = torch.empty(shape, device=xys.device)
+    wt = torch.empty_like(dmap)
+    L.call("gcx_distort_fwd_views", C, N, M_cap, shared_op, H, W, tb[0], tb[1], ids_s, bins, xys, conics, opac, depths, *how, dmap, wt)
+    return dmap, wt, how
+
+
+def _end_forward(ctx, aux, want_depth, meta, comp, saved, depths, dep, nth, M, boxes, keys_s, wt=None, how=None):
     """What both fused forwards do last: fill `aux` (the gradients of an earlier backward are dropped), keep the backward's bookkeeping on
     ctx and save the tensors -- with the two depth tensors when the depth image is differentiable (RenderAux.depth_grad); otherwise depth
     is marked non-differentiable.  Returns the depth output (empty when there is none)."""
@@ -390,24 +429,28 @@ def _end_forward(ctx, aux, want_depth, meta, comp, saved, depths, dep, nth, M, b
     if aux is not None:
         aux.xys, aux.radii, aux.num_tiles_hit, aux.M, aux.depths, aux.tile_boxes = xys, radii, nth, M, depths, boxes
         aux.gaussian_ids_sorted, aux.tile_bins, aux.final_index, aux.isect_ids_sorted = ids_s, bins, fi, keys_s
-        aux.xys_grad = aux.xys_absgrad = aux.viewmat_grad = None
+        aux.xys_grad = aux.xys_absgrad = aux.viewmat_grad = aux.distort_map = None
         aux.compensation = comp
     ctx.meta, ctx.aux = meta, aux
     ctx.comp = comp          # (not an input or output of the function: kept as an attribute)
     ctx.depth_grad = bool(want_depth and aux is not None and aux.depth_grad and any(ctx.needs_input_grad[:6]))
+    ctx.distort = how        # RenderAux.distort: (depth_map, near, far); the backward's two tensors come last among the saved ones
+    tail = (depths, wt) if how is not None else ()
+    if ctx.depth_grad or how is not None:
+        ctx.set_materialize_grads(False)     # an unused depth or distortion map arrives as None in backward, which then takes the path without it
     if ctx.depth_grad:
-        ctx.set_materialize_grads(False)     # an unused depth arrives as None in backward, which then takes the path without depth
-        ctx.save_for_backward(*saved, depths, dep)
+        ctx.save_for_backward(*saved, depths, dep, *tail)
     else:
-        ctx.save_for_backward(*saved)
+        ctx.save_for_backward(*saved, *tail)
         if dep is not None:
             ctx.mark_non_differentiable(dep)
     return dep if dep is not None else torch.empty(0, device=m.device)
 
 
-def _composite_bwd(ctx, v_img, v_alpha, v_dep):
+def _composite_bwd(ctx, v_img, v_alpha, v_dep, want_ex=False):
     """The compositing backward of render_view (C = 1, the batched entry points' single-view case) and render_views: ONE zeroed buffer for
-    every output, the entry point picked by the switches.  Returns (v_xy, v_conic, v_col, v_op, v_ex | None, v_abs | None), shaped [N, ..]
+    every output, the entry point picked by the switches; want_ex: the buffer has the v_ex slice even without a depth cotangent (the distortion
+    backward adds into it).  Returns (v_xy, v_conic, v_col, v_op, v_ex | None, v_abs | None), shaped [N, ..]
     for render_view and [C, N, ..] for render_views, and leaves aux.xys_grad / aux.xys_absgrad (views of the buffer)."""
     conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp = ctx.saved_tensors[7:17]
     mt = ctx.meta
@@ -418,7 +461,7 @@ def _composite_bwd(ctx, v_img, v_alpha, v_dep):
     va = _c(v_alpha) if v_alpha is not None else None
     absgrad = ctx.aux is not None and ctx.aux.absgrad
     depths, dep, vd = (ctx.saved_tensors[17], ctx.saved_tensors[18], _c(v_dep)) if ctx.depth_grad and v_dep is not None else (None, None, None)
-    parts = [("v_xy", 2), ("v_conic", 3), ("v_col", 3), ("v_op", 1)] + ([("v_ex", 1)] if vd is not None else []) + ([("v_abs", 2)] if absgrad else [])
+    parts = [("v_xy", 2), ("v_conic", 3), ("v_col", 3), ("v_op", 1)] + ([("v_ex", 1)] if vd is not None or want_ex else []) + ([("v_abs", 2)] if absgrad else [])
     vbuf = torch.zeros(C * N * sum(w for _, w in parts), device=dev)
     v = {k: t.view(*lead, *((w,) if w > 1 else ())) for (k, w), t in zip(parts, vbuf.split([C * N * w for _, w in parts]))}
     v_xy, v_conic, v_col, v_op, v_ex, v_abs = (v.get(k) for k in ("v_xy", "v_conic", "v_col", "v_op", "v_ex", "v_abs"))
@@ -426,7 +469,7 @@ def _composite_bwd(ctx, v_img, v_alpha, v_dep):
     plain = (C, N, M_cap, shared_op, shared_bg, H, W, tb[0], tb[1], ids_s, bins, xys, conics, rgbs, opac, bg, fT, fi, vo, va, pre_clamp,
              v_xy, v_conic, v_col, v_op)
     if absgrad:                 # one entry point for both depth forms (NULL quartet = no depth)
-        L.call("gc_rasterize_bwd_abs_views", *plain, depths, dep, vd, v_ex, v_abs)
+        L.call("gc_rasterize_bwd_abs_views", *plain, depths, dep, vd, v_ex if vd is not None else None, v_abs)
     elif vd is not None:
         L.call("gc_rasterize_bwd_depth_views", *plain, depths, dep, vd, v_ex)
     else:
@@ -510,8 +553,23 @@ def _pose_bwd(ctx, v_xy, v_conic, v_op, v_ex):
     return chain_viewmat_grad(raw, ctx.meta.cams)
 
 
-def _render_bwd(ctx, v_img, v_alpha, v_dep):
-    v_xy, v_conic, v_col, v_op, v_ex, _ = _composite_bwd(ctx, v_img, v_alpha, v_dep)
+def _distort_bwd(ctx, v_dist, v_xy, v_conic, v_op, v_ex):
+    """RenderAux.distort: the distortion map's cotangent, added into the compositing backward's four arrays"""
+    conics, xys, _, opac, ids_s, bins, _, fT, fi = ctx.saved_tensors[7:16]
+    depths, wt = ctx.saved_tensors[-2:]
+    mt = ctx.meta
+    if ids_s.numel() == 0:          # empty lists: the map is identically zero, nothing to add
+        return
+    depth_map, near, far = ctx.distort
+    L.call("gcx_distort_bwd_views", mt.C, mt.N, mt.M_cap, mt.shared_op, mt.H, mt.W, mt.tb[0], mt.tb[1], ids_s, bins, xys, conics, opac, depths,
+           depth_map, near, far, fT, fi, wt, _c(v_dist), v_xy, v_conic, v_op, v_ex)
+
+
+def _render_bwd(ctx, v_img, v_alpha, v_dep, v_dist=None):
+    distort = ctx.distort is not None and v_dist is not None
+    v_xy, v_conic, v_col, v_op, v_ex, _ = _composite_bwd(ctx, v_img, v_alpha, v_dep, distort)
+    if distort:
+        _distort_bwd(ctx, v_dist, v_xy, v_conic, v_op, v_ex)
     return _project_bwd(ctx, v_xy, v_conic, v_col, v_op, v_ex)
 
 
@@ -552,9 +610,10 @@ class _RenderView(torch.autograd.Function):
         img, dep, fT, fi = _rasterize_fwd(H, W, tb, ids_s, bins, xys, conics, rgbs, opac, extra, bg)
         img, alpha, pre_clamp = _finalize(ctx, H * W, img, dep, fT)
         meta = _RenderMeta(1, N, ids_s.numel(), 1, 1, H, W, tb, sh_degree, int(sh_degree_to_use), [cam], None, True)
+        dmap, wt, how = _distort_fwd(ctx, aux, 1, N, ids_s.numel(), 1, H, W, tb, ids_s, bins, xys, conics, opac, depths, True)
         dep = _end_forward(ctx, aux, want_depth, meta, comp, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
-                           depths, dep, nth, M, boxes, keys_s)
-        return img, alpha, dep
+                           depths, dep, nth, M, boxes, keys_s, wt, how)
+        return img, alpha, dep, dmap
 
     backward = staticmethod(_render_bwd)
 
@@ -564,8 +623,11 @@ def render_view(means, log_scales, quats, opacities, features_dc, features_rest,
     """Fused get_outputs core.  cam: dict(viewmat[12], fullproj[16], origin[3], fx, fy, cx, cy, H, W) of HOST floats.
     Returns (rgb[H,W,3] clamped to <=1, alpha[H,W], depth[H,W] (normalised, 1000 where alpha==0) or empty).  depth carries no gradient
     unless aux.depth_grad is set (RenderAux)."""
-    return _RenderView.apply(means, log_scales, quats, opacities, features_dc, features_rest, cam, background, want_depth,
-                             sh_degree_to_use, aux)
+    img, alpha, dep, dmap = _RenderView.apply(means, log_scales, quats, opacities, features_dc, features_rest, cam, background, want_depth,
+                                              sh_degree_to_use, aux)
+    if dmap is not None:          # RenderAux.distort: the fourth output of the node lives on aux
+        aux.distort_map = dmap
+    return img, alpha, dep
 
 
 # --------------------------------------------------------------------------------------------- batched views
@@ -657,9 +719,10 @@ class _RenderViews(torch.autograd.Function):
         img, alpha, pre_clamp = _finalize(ctx, C * H * W, img, dep, fT)
         meta = _RenderMeta(C, N, M_cap, shared_op, shared_bg, H, W, tb, sh_degree, int(sh_degree_to_use), cams, CH, False)
         # aux.M: per-view device counts / overflow flags ([C] each)
+        dmap, wt, how = _distort_fwd(ctx, aux, C, N, M_cap, shared_op, H, W, tb, ids_s, bins, xys, conics, opac, depths, False)
         dep = _end_forward(ctx, aux, want_depth, meta, comp, (m, ls, q, op, dc, rest, radii, conics, xys, rgbs, opac, ids_s, bins, bg, fT, fi, pre_clamp),
-                           depths, dep, nth, (cnt, ovf), boxes, None)
-        return img, alpha, dep
+                           depths, dep, nth, (cnt, ovf), boxes, None, wt, how)
+        return img, alpha, dep, dmap
 
     backward = staticmethod(_render_bwd)
 
@@ -669,8 +732,11 @@ def render_views(means, log_scales, quats, opacities, features_dc, features_rest
     """render_view for a LIST of cameras of one scene in one set of launches.  backgrounds: [3] (shared) or [C,3].
     Returns (rgb [C,H,W,3] clamped to <= 1, alpha [C,H,W], depth [C,H,W] or empty).  aux.M = (count [C], overflow [C]) device tensors;
     aux.m_cap = per-view intersection capacity for the sync-free form (else the C counts are read back once to size the lists)."""
-    return _RenderViews.apply(means, log_scales, quats, opacities, features_dc, features_rest, list(cams), backgrounds, want_depth,
-                              sh_degree_to_use, aux)
+    img, alpha, dep, dmap = _RenderViews.apply(means, log_scales, quats, opacities, features_dc, features_rest, list(cams), backgrounds, want_depth,
+                                               sh_degree_to_use, aux)
+    if dmap is not None:          # RenderAux.distort: the fourth output of the node lives on aux
+        aux.distort_map = dmap
+    return img, alpha, dep
 
 
 # --------------------------------------------------------------------------------------------- edit-region tracing
